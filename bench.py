@@ -8,16 +8,26 @@ regulariser -> backward -> [N>1: RCCL all-reduce of decoder grads, latent Adam u
 runs).  Workload at N=1 = BASELINE.json configs[1]; N>1 = configs[2] (512 scenes sharded, weak scaling).
 
   python bench.py --gpus 1 --steps 50 --warmup 10
+  python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy
+  python bench.py --full                                                      # + every figure listed below
   python bench.py --code-length 2 --scenes-per-batch 10 --samples 16000      # the reference's shipped 8x512 experiment shape (not the headline)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Beside the contract's line (value / ms_per_step over the barrier-bracketed timed region) rank 0 reports, at N=1:
+A plain run sets up, runs --init-steps untimed steps (code-object loading, runtime pools; reported as init_steps) and the
+--warmup steps, times --steps steps, writes --dump-outputs and prints the contract's line (value / ms_per_step over the
+barrier-bracketed timed region); its step_time_ms, roofline and cpu_baseline are null.
+
+--dump-outputs DIR writes what a caller of the timed step holds after the last timed step, before anything else runs:
+loss.npy (that step's loss), decoder_params.npy (the flat parameter arena in the reference's named_parameters() order) and
+latent_codes.npy (the latent table; latent_codes_rank<r>.npy per rank at N>1), float32, at most 64 MB in all (an array
+above its share: a fixed, seeded sample of its elements).  Every input is seeded: the same arguments give the same inputs.
+
+With --full, after the timed steps (and the dump), rank 0 also reports, at N=1:
   step_time_ms    median / p10 / p90 of single steps (device time between per-step events on the compute stream)
   roofline        dominant kernel: algorithmic FLOP / HIP-event time; `traffic` (HBM bytes per launch) and `executed_frac`
                   (MFMA FLOPs actually issued, from SQ counters) measured by rocprofv3 --pmc child passes of THIS command
   cpu_baseline    the step in stock torch ops (oracle/torch_native.py) on this host, timed AFTER the PMC child passes have been joined
                   (nothing else of the bench alive): a thread-count scan incl. k = 1, k = 64 (one socket) and k = all; value = the best
-  init_steps      untimed steps in front of the contract's --warmup steps (code-object loading, runtime pools)
   config.one_scene_ms_per_step   the locality extreme B=1 x S=16384
   config.inference_forward       --config bf16 only: the bf16 forward alone (one code x the step's points)
   config.gemm_split              headline config only: ms/step of the same workload with the opt-in gemm_split
@@ -56,6 +66,7 @@ NETWORKS = {
                  defaults=dict(code_length=2, scenes_per_batch=10, samples=16000)),
 }
 L = HEADLINE["code_length"]      # (tools/ scripts that build the headline net import this)
+DUMP_BYTES = 64 * 10**6          # --dump-outputs: at most 64 MB of arrays in all
 
 
 def synth_batches(n_batches, scene_lo, scene_hi, device, seed, scenes_per_batch, samples):
@@ -166,6 +177,21 @@ def pmc_children(result, bench_extra):
         result["error"] = f"{type(e).__name__}: {e}"
 
 
+def dump_outputs(out_dir, arrays, budget):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32.  If they hold more than `budget` bytes in all,
+    an array above its proportional share keeps a fixed, seeded sample of its elements (distinct sorted flat indices, seed 0)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if total > budget:
+            n = max(1, (budget * a.size) // total)
+            if n < a.size:
+                a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -192,11 +218,19 @@ def main():
                     help="untimed steps in FRONT of the contract's --warmup steps (reported in the line as init_steps; 0 = only --warmup): "
                          "the first ~100 kernel launches of a process load the code objects and grow the runtime's kernarg / signal pools "
                          "(one-off stalls of 80-90 ms were observed as late as the 4th step), a cost a trainer pays once per process")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event instrumented pass")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (HBM traffic, MFMA counters)")
-    ap.add_argument("--no-extras", action="store_true", help="skip per-step percentiles and the one-scene extreme")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: per-step percentiles, the "
+                         "HIP-event instrumented pass (roofline), the one-scene / gemm_split / inference-forward extras, the rocprofv3 "
+                         "--pmc child passes and the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, decoder parameters, latent codes) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the HIP-event instrumented pass")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc child passes (HBM traffic, MFMA counters)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip per-step percentiles and the one-scene extreme")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     from deepsdf_amd import _lib
     from deepsdf_amd.engine import Engine
@@ -220,7 +254,7 @@ def main():
     torch.cuda.set_device(dev)
 
     pmc_res = {}
-    want_pmc = rank == 0 and world == 1 and not args.no_pmc and "ROCPROFILER" not in " ".join(os.environ.keys()).upper()
+    want_pmc = args.full and rank == 0 and world == 1 and not args.no_pmc and "ROCPROFILER" not in " ".join(os.environ.keys()).upper()
 
     bf16 = args.config in ("bf16", "bf16split")
     split = args.config in ("f32split", "bf16split")
@@ -265,6 +299,12 @@ def main():
     loss = float(loss_t.item())
     if not math.isfinite(loss):
         raise SystemExit("non-finite loss in the timed region")
+    # the last timed step's outputs, before any --full pass steps the same engine again
+    if args.dump_outputs is not None:
+        outs = {"latent_codes" if world == 1 else f"latent_codes_rank{rank}": fused.lat}
+        if rank == 0:
+            outs.update(loss=loss_t, decoder_params=eng.params)
+        dump_outputs(args.dump_outputs, outs, DUMP_BYTES // world)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = n_global * args.steps / elapsed
@@ -273,7 +313,7 @@ def main():
 
     # ---- single-step distribution: events on the compute stream around every step (separate pass: outside the timed region) ----
     step_stats = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         k = min(args.steps, 200)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(k + 1)]
         evs[0].record()
@@ -287,7 +327,7 @@ def main():
 
     # ---- instrumented pass: HIP events around every launch of each kernel class, same steps, same stream ----
     roofline = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         lib = _lib.lib()
         lib.dsdf_profile_enable(1)
         for i in range(args.steps):
@@ -328,7 +368,7 @@ def main():
 
     # ---- the locality extreme of config 2: ONE scene x 16384 samples per step ----
     one_scene = None
-    if rank == 0 and world == 1 and headline and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and headline and not args.no_extras:
         ob = synth_batches(2, 0, 1, dev, 77, 1, 16384)
         olat = (torch.randn(1, L, generator=torch.Generator().manual_seed(5)) / math.sqrt(L)).to(dev)
         ofused = FusedTrainStep(eng, olat, clamp_dist=0.1, code_reg=True, code_reg_lambda=1e-4, code_bound=1.0, grad_clip=None, seed=3)
@@ -344,7 +384,7 @@ def main():
 
     # ---- headline config only: the same step with NetworkSpecs gemm_split (opt-in), so that the record carries both ----
     split_extra = None
-    if rank == 0 and world == 1 and args.config == "fp32" and not args.no_extras and args.network == "8x512":
+    if args.full and rank == 0 and world == 1 and args.config == "fp32" and not args.no_extras and args.network == "8x512":
         n_it = max(10, min(100, (100 * 16384) // n_local))
         seng = Engine(NetSpec(L, gemm_split=True, **NET), dev)
         seng.init_like_reference(torch.Generator().manual_seed(0))
@@ -375,7 +415,7 @@ def main():
 
     # ---- config 5 only: its INFERENCE forward alone (one code x the step's points: dsdf_decode_latent = hoist + the 8-wave kernel) ----
     bf16_fwd = None
-    if rank == 0 and world == 1 and bf16 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and bf16 and not args.no_extras:
         z = (torch.randn(L, generator=torch.Generator().manual_seed(9)) / math.sqrt(L)).to(dev)
         q = (torch.rand(n_local, 3, generator=torch.Generator().manual_seed(10)) * 2 - 1).to(dev)
         for _ in range(10):
@@ -397,7 +437,7 @@ def main():
         extra = ["--scenes-per-batch", str(B), "--samples", str(S), "--config", args.config, "--code-length", str(L), "--network", args.network]
         pmc_children(pmc_res, extra)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not bf16:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not bf16:
         torch.cuda.synchronize()
         cpu = cpu_baseline(L, B, S, headline, NET)
     if roofline is not None:

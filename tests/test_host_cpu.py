@@ -189,7 +189,8 @@ def test_decoder_state_dict_roundtrip_with_reference_keys():
         assert torch.equal(sd[k], params[k])
     # DataParallel-prefixed keys (what the reference's checkpoints carry) load through a DataParallel wrapper
     torch.nn.DataParallel(dec).load_state_dict({"module." + k: v * 2 for k, v in params.items()})
-    assert torch.equal(dec.state_dict()["lin0.bias"], params["lin0.bias"] * 2)
+    # (where a GPU is visible, DataParallel has moved the module to cuda:0: compare on the host)
+    assert torch.equal(dec.state_dict()["lin0.bias"].cpu(), params["lin0.bias"] * 2)
     assert dec.geom_dimension == 3
     assert sum(p.numel() for p in dec.parameters()) == dec.spec.n_params
     with pytest.raises(Exception, match="no CPU fallback"):
@@ -217,7 +218,7 @@ def test_checkpoint_written_by_the_reference_trainer_loads(tmp_path):
     L = specs["CodeLength"]
     dec = Decoder(L, **specs["NetworkSpecs"])
     assert ws.load_model_parameters(exp, "latest", torch.nn.DataParallel(dec)) == 3
-    sd = dec.state_dict()
+    sd = {k: v.cpu() for k, v in dec.state_dict().items()}      # on cuda:0 where a GPU is visible (DataParallel moved it)
     assert ["module." + k for k in sd.keys()] == m["model_keys"]
     for k in sd:
         assert torch.equal(sd[k], g.get("model/module." + k)), k

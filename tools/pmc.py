@@ -3,7 +3,7 @@
 Used two ways:
   * by bench.py itself (rank 0, N = 1): the passes run as CHILD processes while the parent times the CPU baseline, so the
     bench line's roofline.traffic / executed_frac are measured in the same invocation;
-  * stand-alone on the GPU box:   python tools/pmc.py <tag>    -> gpurun_out/<tag>_pmc_traffic.json, <tag>_mfma_util.json
+  * stand-alone on the GPU box:   python tools/pmc.py <tag>    -> $OUT/<tag>_pmc_traffic.json, <tag>_mfma_util.json (OUT: profile_out/)
     (copy them to profiles/).
 
 Rules followed (MI355X_MICROARCH.md, HBM / rocprofv3 PMC slots): FETCH_SIZE and WRITE_SIZE in SEPARATE passes (TCC has 4
@@ -123,15 +123,16 @@ if __name__ == "__main__" and len(sys.argv) > 2 and sys.argv[1] == "--script":  
 elif __name__ == "__main__":
     tag = sys.argv[1] if len(sys.argv) > 1 else "pmc"
     extra = sys.argv[2:]
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+    out = os.environ.get("OUT") or os.path.join(ROOT, "profile_out")      # the folder tools/final_profiles.sh writes to
+    os.makedirs(out, exist_ok=True)
     m = mfma(CHILD_ARGS + extra)
-    json.dump(m, open(os.path.join(ROOT, "gpurun_out", f"{tag}_mfma_util.json"), "w"), indent=1)
+    json.dump(m, open(os.path.join(out, f"{tag}_mfma_util.json"), "w"), indent=1)
     for k, e in sorted(m.items(), key=lambda kv: -kv[1].get("duration_us", 0)):
         print(f"{k:28s} {e.get('duration_us', 0):8.1f} us  exec {e.get('exec_tflops', 0):6.1f} TF ({100 * e.get('exec_frac_of_peak', 0):5.1f} %)"
               f"  mfma_busy {100 * e.get('mfma_busy_frac', 0):5.1f} %  clock {e.get('clock_ghz', 0):.2f} GHz"
               f"  mops/inst {e.get('mops_per_mfma_inst', 0):.2f}  busy cyc/inst {e.get('mfma_busy_cycles_per_inst', 0):.1f}", flush=True)
     t = traffic(CHILD_ARGS + extra)
-    json.dump(t, open(os.path.join(ROOT, "gpurun_out", f"{tag}_pmc_traffic.json"), "w"), indent=1)
+    json.dump(t, open(os.path.join(out, f"{tag}_pmc_traffic.json"), "w"), indent=1)
     for k, v in sorted(t.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch"]):
         print(f"{k:28s} fetch {v['FETCH_SIZE_KB_per_launch'] / 1024:8.1f} MiB  write {v['WRITE_SIZE_KB_per_launch'] / 1024:8.1f} MiB  "
               f"-> HBM {v['hbm_bytes_per_launch'] / 1e6:8.1f} MB/launch")

@@ -6,7 +6,7 @@ tail -5 gpurun_out/r4_dist.log; [ $rc -eq 0 ] || { echo "FAILED: dist tests rc $
 timeout -k 10 600 python3 -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "phased" > gpurun_out/r4_phased.log 2>&1; rc=$?
 tail -3 gpurun_out/r4_phased.log; [ $rc -eq 0 ] || { echo "FAILED: phased tests rc $rc"; exit 1; }
 timeout -k 10 300 bash tools/lab_dw_stamps.sh || { echo "FAILED: dw stamps"; exit 1; }
-one() { python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-pmc --no-extras 2>/dev/null | tail -n 1 | python3 -c "
+one() { python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-pmc --no-extras 2>/dev/null | tail -n 1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$1', round(d['ms_per_step'],4), 'ms/step', {k: (round(v['avg_us'],1), v['launches_per_step']) for k,v in d['roofline']['kernels'].items()})"; }
 { one "default:"; DSDF_NO_RIDE=1 one "DSDF_NO_RIDE=1:"; } > gpurun_out/r4_ride_ab.log 2>&1
 cat gpurun_out/r4_ride_ab.log
