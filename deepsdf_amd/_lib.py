@@ -6,7 +6,7 @@ import os
 from .build import LIB
 
 MAX_LAYERS = 16
-ABI_VERSION = 15
+ABI_VERSION = 16
 MAX_BUCKETS = 8
 
 
@@ -90,6 +90,10 @@ PROTOTYPES = {
     "dsdf_decode_latent_supported": [_NET],
     "dsdf_sample_batch": [_P, C.c_int32, _P, _P, _P, _P, _P, _I64, _I64, C.c_uint64, _P, _P, _P],
     "dsdf_sample_batch_seq": [_P, C.c_int32, _P, _P, _P, _P, _P, _I64, _I64, C.c_uint64, C.c_uint64, _P, _P, _P, _P],
+    "dsdf_mc_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_SZ)],
+    "dsdf_mc_count": [_P, _I32, _I32, _I32, _F, _P, _P, _SZ, _P],
+    "dsdf_mc_emit": [_P, _I32, _I32, _I32, _F, C.POINTER(_F), C.POINTER(_F), _I64, _I64, _P, _P, _P, _SZ, _P],
+    "dsdf_mc_case_table": [_P, _SZ, C.POINTER(_I32)],
 }
 
 _lib = None

@@ -19,6 +19,7 @@
 #include "fused_bf16x8.hpp"
 #include "gemm.hpp"
 #include "kernels.hpp"
+#include "mcubes.hpp"
 
 using namespace dsdf;
 
@@ -1900,6 +1901,97 @@ int dsdf_dropout_mask(uint32_t key, float p, int64_t rows, int64_t cols, int64_t
   hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, key,
                      (uint32_t)thr, (int)rows, (int)cols, (uint32_t)row_offset, out);
   LAUNCH_OK("dropout_mask_kernel");
+  return 0;
+}
+
+// ---- marching cubes (mcubes.hpp) ----------------------------------------------------------------------
+namespace {
+struct McPlan {
+  int64_t npts, nblocks;
+  size_t mask, cas, vbase, bv, bf, ov, of, total;
+};
+
+int mc_plan(int32_t nx, int32_t ny, int32_t nz, McPlan* P) {
+  if (nx < 2 || ny < 2 || nz < 2 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
+    return fail(DSDF_E_INVALID, "marching cubes: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
+  P->npts = (int64_t)nx * ny * nz;
+  P->nblocks = (P->npts + MC_BLOCK - 1) / MC_BLOCK;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o = (size_t)rup((int64_t)(o + bytes), 256); return at; };
+  P->mask = take((size_t)P->npts);
+  P->cas = take((size_t)P->npts);
+  P->vbase = take((size_t)P->npts * 4);
+  P->bv = take((size_t)P->nblocks * 4);
+  P->bf = take((size_t)P->nblocks * 4);
+  P->ov = take((size_t)(P->nblocks + 1) * 8);
+  P->of = take((size_t)(P->nblocks + 1) * 8);
+  P->total = o;
+  return 0;
+}
+
+int mc_setup(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, void* ws, size_t ws_bytes, McGrid* g,
+             McWs* w, McPlan* P) {
+  TRY(mc_plan(nx, ny, nz, P));
+  if (!sdf || !ws) return fail(DSDF_E_INVALID, "marching cubes: NULL sdf or workspace");
+  if (ws_bytes < P->total) return fail(DSDF_E_WORKSPACE, "marching cubes: workspace %zu < %zu bytes", ws_bytes, P->total);
+  g->sdf = sdf; g->nx = nx; g->ny = ny; g->nz = nz; g->level = level; g->npts = P->npts;
+  char* b = (char*)ws;
+  w->mask = (uint8_t*)(b + P->mask); w->cas = (uint8_t*)(b + P->cas); w->vbase = (int32_t*)(b + P->vbase);
+  w->bv = (int32_t*)(b + P->bv); w->bf = (int32_t*)(b + P->bf); w->ov = (int64_t*)(b + P->ov); w->of = (int64_t*)(b + P->of);
+  w->nblocks = P->nblocks;
+  return 0;
+}
+}  // namespace
+
+int dsdf_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes) {
+  McPlan P;
+  TRY(mc_plan(nx, ny, nz, &P));
+  if (!bytes) return fail(DSDF_E_INVALID, "NULL bytes");
+  *bytes = P.total;
+  return 0;
+}
+
+int dsdf_mc_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* totals, void* ws, size_t ws_bytes,
+                  void* stream) {
+  McGrid g; McWs w; McPlan P;
+  TRY(mc_setup(sdf, nx, ny, nz, level, ws, ws_bytes, &g, &w, &P));
+  if (!totals) return fail(DSDF_E_INVALID, "marching cubes: NULL totals");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)P.nblocks), dim3(MC_BLOCK), 0, st, g, w);
+  LAUNCH_OK("mc_classify_kernel");
+  hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w, totals);
+  LAUNCH_OK("mc_scan_kernel");
+  return 0;
+}
+
+int dsdf_mc_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing, const float* origin,
+                 int64_t n_verts, int64_t n_faces, float* verts, int32_t* faces, void* ws, size_t ws_bytes, void* stream) {
+  McGrid g; McWs w; McPlan P;
+  TRY(mc_setup(sdf, nx, ny, nz, level, ws, ws_bytes, &g, &w, &P));
+  if (n_verts < 0 || n_faces < 0 || n_verts > INT32_MAX || n_faces > INT32_MAX)
+    return fail(DSDF_E_INVALID, "marching cubes: %lld vertices / %lld faces (int32 indices hold at most %d)", (long long)n_verts,
+                (long long)n_faces, INT32_MAX);
+  if (!spacing || !origin) return fail(DSDF_E_INVALID, "marching cubes: NULL spacing or origin");
+  if ((n_verts > 0 && !verts) || (n_faces > 0 && !faces)) return fail(DSDF_E_INVALID, "marching cubes: NULL verts or faces");
+  if (n_verts == 0 && n_faces == 0) return 0;
+  McOut o;
+  for (int a = 0; a < 3; ++a) { o.spacing[a] = spacing[a]; o.origin[a] = origin[a]; }
+  o.verts = verts; o.faces = faces; o.nv = n_verts; o.nf = n_faces;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mc_vertex_kernel, dim3((unsigned)P.nblocks), dim3(MC_BLOCK), 0, st, g, w, o);
+  LAUNCH_OK("mc_vertex_kernel");
+  if (n_faces > 0) {
+    hipLaunchKernelGGL(mc_face_kernel, dim3((unsigned)P.nblocks), dim3(MC_BLOCK), 0, st, g, w, o);
+    LAUNCH_OK("mc_face_kernel");
+  }
+  return 0;
+}
+
+int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width) {
+  if (width) *width = MC_TABLE_W;
+  if (!table) return width ? 0 : fail(DSDF_E_INVALID, "NULL table and width");
+  if (table_bytes < sizeof(mc_tri_h)) return fail(DSDF_E_INVALID, "case table needs %zu bytes", sizeof(mc_tri_h));
+  memcpy(table, mc_tri_h, sizeof(mc_tri_h));
   return 0;
 }
 

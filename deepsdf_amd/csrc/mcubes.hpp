@@ -1,0 +1,214 @@
+// mcubes.hpp -- marching cubes over a dense fp32 grid sdf[nx][ny][nz] (z fastest) on the device (gfx950).
+//
+// A grid point is inside iff v < level (strictly).  One vertex per grid edge whose endpoints lie on different sides; edge
+// (p, a) runs from grid point p to p + e_a.  Output order is fixed by prefix sums, no atomics: vertices by grid-point linear
+// index, then axis x, y, z; faces by cell linear index (a cell is named by its lower corner), then table order.
+//
+// Passes (one thread per grid point, MC_BLOCK points per workgroup, linear order):
+//   1. classify:  mask[p] = 3-bit crossing mask of p's edges, cas[p] = 8-bit case of the cell at p (0 off the cell range);
+//                 per workgroup, its vertex and triangle totals
+//   2. scan:      one workgroup turns the per-workgroup totals into 64-bit exclusive offsets (+ the two grand totals)
+//   3. vertices:  workgroup scan of popcount(mask) + offset -> vbase[p] (id of p's first vertex) and the interpolated positions
+//   4. faces:     workgroup scan of the triangle counts + offset; edge (corner c of cell p, axis a) has vertex id
+//                 vbase[q] + popcount(mask[q] & ((1 << a) - 1)), q = p + offset(c): no edge-id map
+// The case table is generated (deepsdf_amd/mc_table.py -> mc_table.hpp).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mc_table.hpp"
+
+namespace dsdf {
+
+constexpr int MC_BLOCK = 256;
+constexpr int MC_SCAN_THREADS = 1024;
+constexpr int MC_SCAN_PER_THREAD = 8;
+constexpr int MC_MAX_DIM = 1024;
+
+__constant__ int8_t mc_tri_d[256][MC_TABLE_W] = DSDF_MC_TRI_INIT;
+__constant__ uint8_t mc_ntri_d[256] = DSDF_MC_NTRI_INIT;
+__constant__ uint8_t mc_edge_d[12][2] = DSDF_MC_EDGES_INIT;
+static const int8_t mc_tri_h[256][MC_TABLE_W] = DSDF_MC_TRI_INIT;   // what dsdf_mc_case_table returns
+
+struct McGrid {
+  const float* sdf;
+  int nx, ny, nz;
+  float level;
+  int64_t npts;
+};
+
+struct McWs {             // carved from the caller's workspace (mc_plan in dsdf_api.hip)
+  uint8_t* mask;          // [npts]
+  uint8_t* cas;           // [npts]
+  int32_t* vbase;         // [npts]
+  int32_t* bv;            // [nblocks] vertices per workgroup
+  int32_t* bf;            // [nblocks] triangles per workgroup
+  int64_t* ov;            // [nblocks + 1] exclusive offsets
+  int64_t* of;            // [nblocks + 1]
+  int64_t nblocks;
+};
+
+struct McOut {
+  float spacing[3], origin[3];
+  float* verts;           // [nv][3]
+  int32_t* faces;         // [nf][3]
+  int64_t nv, nf;         // sizes of the caller's buffers: nothing is written past them
+};
+
+// Inclusive scan of one int per thread over the MC_BLOCK threads of a workgroup (Hillis-Steele in LDS).
+__device__ __forceinline__ int mc_block_scan(int x, int* s) {
+  const int t = threadIdx.x;
+  s[t] = x;
+  __syncthreads();
+  for (int d = 1; d < MC_BLOCK; d <<= 1) {
+    const int y = t >= d ? s[t - d] : 0;
+    __syncthreads();
+    s[t] += y;
+    __syncthreads();
+  }
+  return s[t];
+}
+
+__device__ __forceinline__ void mc_coords(int64_t p, const McGrid& g, int& i, int& j, int& k) {
+  const int64_t syz = (int64_t)g.ny * g.nz;
+  i = (int)(p / syz);
+  const int r = (int)(p - (int64_t)i * syz);
+  j = r / g.nz;
+  k = r - j * g.nz;
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void mc_classify_kernel(McGrid g, McWs w) {
+  __shared__ int s[MC_BLOCK];
+  const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
+  int nv = 0, nt = 0;
+  if (p < g.npts) {
+    int i, j, k;
+    mc_coords(p, g, i, j, k);
+    const int64_t syz = (int64_t)g.ny * g.nz;
+    const float* v = g.sdf + p;
+    const bool in0 = v[0] < g.level;
+    const bool hx = i + 1 < g.nx, hy = j + 1 < g.ny, hz = k + 1 < g.nz;
+    uint32_t m = 0;
+    if (hx && (v[syz] < g.level) != in0) m |= 1u;
+    if (hy && (v[g.nz] < g.level) != in0) m |= 2u;
+    if (hz && (v[1] < g.level) != in0) m |= 4u;
+    uint32_t cs = 0;
+    if (hx && hy && hz) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int64_t off = (c & 1) * syz + ((c >> 1) & 1) * (int64_t)g.nz + ((c >> 2) & 1);
+        cs |= (uint32_t)(v[off] < g.level) << c;
+      }
+    }
+    w.mask[p] = (uint8_t)m;
+    w.cas[p] = (uint8_t)cs;
+    nv = __popc(m);
+    nt = mc_ntri_d[cs];
+  }
+  // both counts in one scan: a workgroup has at most 3 * 256 vertices and 5 * 256 triangles (< 2^16 each)
+  const int tot = mc_block_scan(nv | (nt << 16), s);
+  if (threadIdx.x == MC_BLOCK - 1) {
+    w.bv[blockIdx.x] = tot & 0xFFFF;
+    w.bf[blockIdx.x] = tot >> 16;
+  }
+}
+
+// One workgroup: exclusive 64-bit scans of bv and bf into ov / of, the grand totals into ov[nb], of[nb] and totals[0..1].
+__global__ __launch_bounds__(MC_SCAN_THREADS) void mc_scan_kernel(McWs w, int64_t* totals) {
+  __shared__ int64_t sv[MC_SCAN_THREADS], sf[MC_SCAN_THREADS];
+  const int t = threadIdx.x;
+  const int64_t nb = w.nblocks;
+  int64_t carry_v = 0, carry_f = 0;
+  for (int64_t base = 0; base < nb; base += (int64_t)MC_SCAN_THREADS * MC_SCAN_PER_THREAD) {
+    const int64_t b0 = base + (int64_t)t * MC_SCAN_PER_THREAD;
+    int64_t xv = 0, xf = 0;
+    for (int q = 0; q < MC_SCAN_PER_THREAD; ++q) {
+      if (b0 + q < nb) {
+        xv += w.bv[b0 + q];
+        xf += w.bf[b0 + q];
+      }
+    }
+    sv[t] = xv;
+    sf[t] = xf;
+    __syncthreads();
+    for (int d = 1; d < MC_SCAN_THREADS; d <<= 1) {
+      const int64_t yv = t >= d ? sv[t - d] : 0, yf = t >= d ? sf[t - d] : 0;
+      __syncthreads();
+      sv[t] += yv;
+      sf[t] += yf;
+      __syncthreads();
+    }
+    int64_t ev = carry_v + sv[t] - xv, ef = carry_f + sf[t] - xf;     // exclusive offset of element b0
+    for (int q = 0; q < MC_SCAN_PER_THREAD; ++q) {
+      if (b0 + q < nb) {
+        w.ov[b0 + q] = ev;
+        w.of[b0 + q] = ef;
+        ev += w.bv[b0 + q];
+        ef += w.bf[b0 + q];
+      }
+    }
+    carry_v += sv[MC_SCAN_THREADS - 1];
+    carry_f += sf[MC_SCAN_THREADS - 1];
+    __syncthreads();     // every thread has read the last entries before the next chunk overwrites them
+  }
+  if (t == 0) {
+    w.ov[nb] = carry_v;
+    w.of[nb] = carry_f;
+    totals[0] = carry_v;
+    totals[1] = carry_f;
+  }
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void mc_vertex_kernel(McGrid g, McWs w, McOut o) {
+  __shared__ int s[MC_BLOCK];
+  const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
+  const uint32_t m = p < g.npts ? w.mask[p] : 0u;
+  const int n = __popc(m);
+  const int inc = mc_block_scan(n, s);
+  if (p >= g.npts) return;
+  int64_t id = w.ov[blockIdx.x] + inc - n;
+  w.vbase[p] = (int32_t)id;          // the host refuses totals above INT32_MAX before this launch
+  if (!m) return;
+  int i, j, k;
+  mc_coords(p, g, i, j, k);
+  const int64_t stride[3] = {(int64_t)g.ny * g.nz, (int64_t)g.nz, 1};
+  const int idx[3] = {i, j, k};
+  const float v0 = g.sdf[p];
+  for (int a = 0; a < 3; ++a) {
+    if (!((m >> a) & 1u)) continue;
+    const float v1 = g.sdf[p + stride[a]];
+    // v0 and v1 lie on different sides of the level, so v1 != v0.  Every operation rounds on its own (no contraction).
+    const float t = __fdiv_rn(__fsub_rn(g.level, v0), __fsub_rn(v1, v0));
+    if (id < o.nv) {
+      float* out = o.verts + id * 3;
+      for (int b = 0; b < 3; ++b) {
+        const float x = b == a ? __fadd_rn((float)idx[b], t) : (float)idx[b];
+        out[b] = __fadd_rn(o.origin[b], __fmul_rn(x, o.spacing[b]));
+      }
+    }
+    ++id;
+  }
+}
+
+__global__ __launch_bounds__(MC_BLOCK) void mc_face_kernel(McGrid g, McWs w, McOut o) {
+  __shared__ int s[MC_BLOCK];
+  const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
+  const uint32_t cs = p < g.npts ? w.cas[p] : 0u;
+  const int n = mc_ntri_d[cs];
+  const int inc = mc_block_scan(n, s);
+  if (p >= g.npts || n == 0) return;
+  const int64_t first = w.of[blockIdx.x] + inc - n;
+  const int64_t syz = (int64_t)g.ny * g.nz;
+  for (int tr = 0; tr < n; ++tr) {
+    if (first + tr >= o.nf) break;
+    int32_t* out = o.faces + (first + tr) * 3;
+    for (int r = 0; r < 3; ++r) {
+      const int e = mc_tri_d[cs][3 * tr + r];
+      const int c = mc_edge_d[e][0], a = mc_edge_d[e][1];
+      const int64_t q = p + (c & 1) * syz + ((c >> 1) & 1) * (int64_t)g.nz + ((c >> 2) & 1);
+      out[r] = w.vbase[q] + __popc(w.mask[q] & ((1u << a) - 1u));
+    }
+  }
+}
+
+}  // namespace dsdf

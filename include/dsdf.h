@@ -27,7 +27,7 @@ extern "C" {
 #endif
 
 #define DSDF_MAX_LAYERS 16
-#define DSDF_ABI_VERSION 15
+#define DSDF_ABI_VERSION 16
 #define DSDF_MAX_BUCKETS 8
 
 enum {
@@ -272,6 +272,26 @@ int dsdf_sample_batch_seq(const float* data, int32_t geom_dim, const int64_t* po
                           const int64_t* neg_start, const int64_t* n_neg, const int64_t* scene_ids, int64_t n_batch_scenes,
                           int64_t subsample, uint64_t key0, uint64_t key_step, const int64_t* counter, float* xyz_out, float* sdf_out,
                           void* stream);
+
+/* ---- marching cubes: deep_sdf/mesh.py convert_sdf_samples_to_ply's skimage.measure.marching_cubes, on the device ---------
+ * sdf [nx][ny][nz] fp32 (z fastest, axis 0 = x: the reference's reshape(N, N, N)), 2 <= nx, ny, nz <= 1024.  A grid point is
+ * inside iff v < level (strictly); one vertex per grid edge whose endpoints lie on different sides, shared by every cell touching
+ * it, at origin[a] + (p[a] + t) * spacing[a] along the edge axis a (t = (level - v0) / (v1 - v0), fp32, every operation rounded
+ * on its own) and origin[b] + p[b] * spacing[b] on the other two.  Order, without atomics (two runs give identical bytes):
+ * vertices by grid-point linear index, then axis x, y, z; faces by cell linear index, then case-table order.  Faces are
+ * counter-clockwise seen from increasing sdf (right-hand normals point outward).  Ambiguous cube faces separate the inside corners.
+ * Use: dsdf_mc_count (writes {n_verts, n_faces} as int64 to device memory), read the totals, allocate, dsdf_mc_emit with the
+ * SAME grid, level and workspace (the emit pass reads what the count pass left there).  Totals above INT32_MAX are refused
+ * (DSDF_E_INVALID) before anything is written. */
+int dsdf_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes);                     /* [host] */
+int dsdf_mc_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* totals /*[2], device*/, void* ws,
+                  size_t ws_bytes, void* stream);
+/* verts [n_verts][3] fp32, faces [n_faces][3] int32 (vertex ids); spacing, origin [host] 3 floats each */
+int dsdf_mc_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing, const float* origin,
+                 int64_t n_verts, int64_t n_faces, float* verts, int32_t* faces, void* ws, size_t ws_bytes, void* stream);
+/* [host] the compiled-in case table (generated by deepsdf_amd/mc_table.py): *width = entries per case (edge ids of its
+ * triangles, -1 terminated); table (may be NULL) receives 256 * width int8. */
+int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width);
 
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */

@@ -4,10 +4,12 @@
 The fork deleted upstream's reconstruct.py (README.md:139,185 still advertise it); this script restores the workflow on
 top of the artefacts the fork keeps (deep_sdf/workspace.py:122-149): codes are written to
 ``<experiment>/Reconstructions/<epoch>/Codes/<dataset>/<class>/<instance>.pth`` (a [1, 1, L] tensor, as upstream wrote).
-Meshes are NOT produced (marching cubes / FlexiCubes are out of scope).  All shapes of the split are
+With ``--mesh [N]`` (off by default) every reconstructed code is also meshed on an N^3 grid (default 256) through
+deep_sdf.mesh.create_mesh (GPU grid decode, HIP marching cubes) into
+``<experiment>/Reconstructions/<epoch>/Meshes/<dataset>/<class>/<instance>.ply``.  All shapes of the split are
 reconstructed TOGETHER in batches (deepsdf_amd/reconstruct.py), not one after the other.
 
-    python reconstruct.py -e <experiment_dir> -c latest -d <data_dir> -s <split.json> [--iters 800] [--skip]
+    python reconstruct.py -e <experiment_dir> -c latest -d <data_dir> -s <split.json> [--iters 800] [--skip] [--mesh [N]]
 """
 import argparse
 import json
@@ -17,6 +19,7 @@ import os
 import torch
 
 import deep_sdf
+import deep_sdf.mesh
 import deep_sdf.workspace as ws
 from deepsdf_amd.data import DeviceSampleCache, get_instance_filenames
 from deepsdf_amd.reconstruct import reconstruct
@@ -31,6 +34,8 @@ if __name__ == "__main__":
     ap.add_argument("--samples", dest="num_samples", default=8000, type=int, help="SDF samples per shape per iteration")
     ap.add_argument("--shapes_per_batch", default=64, type=int)
     ap.add_argument("--skip", dest="skip", action="store_true", help="skip shapes whose code file already exists")
+    ap.add_argument("--mesh", dest="mesh_resolution", nargs="?", const=256, default=None, type=int,
+                    help="also write a PLY mesh of every reconstructed code on an N^3 grid (N default 256)")
     deep_sdf.add_common_args(ap)
     args = ap.parse_args()
     deep_sdf.configure_logging(args)
@@ -69,3 +74,8 @@ if __name__ == "__main__":
         for (f, out), code in zip(chunk, z.cpu()):
             os.makedirs(os.path.dirname(out), exist_ok=True)
             torch.save(code.view(1, 1, -1), out)
+            if args.mesh_resolution:
+                ds, cls, inst = f[:-4].split(os.sep)
+                mesh_out = ws.get_reconstructed_mesh_filename(args.experiment_directory, saved_epoch, ds, cls, inst)
+                os.makedirs(os.path.dirname(mesh_out), exist_ok=True)
+                deep_sdf.mesh.create_mesh(decoder, code.view(-1), mesh_out, N=args.mesh_resolution)
