@@ -6,7 +6,7 @@ import os
 from .build import LIB
 
 MAX_LAYERS = 16
-ABI_VERSION = 16
+ABI_VERSION = 17
 MAX_BUCKETS = 8
 
 
@@ -94,6 +94,9 @@ PROTOTYPES = {
     "dsdf_mc_count": [_P, _I32, _I32, _I32, _F, _P, _P, _SZ, _P],
     "dsdf_mc_emit": [_P, _I32, _I32, _I32, _F, C.POINTER(_F), C.POINTER(_F), _I64, _I64, _P, _P, _P, _SZ, _P],
     "dsdf_mc_case_table": [_P, _SZ, C.POINTER(_I32)],
+    "dsdf_msdf_plan": [_I64, _I64, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_I32)],
+    "dsdf_msdf_prepare": [_P, _I64, _P, _I64, _P, _SZ, _P],
+    "dsdf_msdf_query": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P],
 }
 
 _lib = None

@@ -20,6 +20,7 @@
 #include "gemm.hpp"
 #include "kernels.hpp"
 #include "mcubes.hpp"
+#include "meshsdf.hpp"
 
 using namespace dsdf;
 
@@ -1992,6 +1993,96 @@ int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width) {
   if (!table) return width ? 0 : fail(DSDF_E_INVALID, "NULL table and width");
   if (table_bytes < sizeof(mc_tri_h)) return fail(DSDF_E_INVALID, "case table needs %zu bytes", sizeof(mc_tri_h));
   memcpy(table, mc_tri_h, sizeof(mc_tri_h));
+  return 0;
+}
+
+// ---- mesh SDF (meshsdf.hpp) ----------------------------------------------------------------------------
+namespace {
+struct MsdfPlan {
+  int32_t n_splits, chunk;
+  int64_t qblocks;
+  size_t tri, ws;
+};
+
+int msdf_plan(int64_t nf, int64_t nq, MsdfPlan* P) {
+  if (nf <= 0) return fail(DSDF_E_INVALID, "mesh sdf: %lld faces (need at least one)", (long long)nf);
+  if (nq < 0) return fail(DSDF_E_INVALID, "mesh sdf: %lld queries", (long long)nq);
+  if (nf > INT32_MAX || nq > INT32_MAX)
+    return fail(DSDF_E_INVALID, "mesh sdf: %lld faces / %lld queries (the kernels index in int32: at most %d)", (long long)nf,
+                (long long)nq, INT32_MAX);
+  P->qblocks = (nq + MSDF_BLOCK - 1) / MSDF_BLOCK;
+  int64_t ns = 1;
+  if (P->qblocks > 0 && P->qblocks < MSDF_TARGET_WG) {
+    ns = (MSDF_TARGET_WG + P->qblocks - 1) / P->qblocks;
+    ns = std::min<int64_t>(ns, std::min<int64_t>(nf / MSDF_MIN_SPLIT_FACES, MSDF_MAX_SPLITS));
+    ns = std::max<int64_t>(ns, 1);
+  }
+  P->n_splits = (int32_t)ns;
+  P->chunk = (int32_t)((nf + ns - 1) / ns);
+  P->tri = (size_t)nf * sizeof(MsdfTri);
+  P->ws = (size_t)ns * (size_t)nq * 12;          // d2, face, winding per (split, query)
+  return 0;
+}
+}  // namespace
+
+int dsdf_msdf_plan(int64_t n_faces, int64_t n_queries, size_t* tri_bytes, size_t* ws_bytes, int32_t* n_splits) {
+  MsdfPlan P;
+  TRY(msdf_plan(n_faces, n_queries, &P));
+  if (!tri_bytes && !ws_bytes && !n_splits) return fail(DSDF_E_INVALID, "mesh sdf plan: every output is NULL");
+  if (tri_bytes) *tri_bytes = P.tri;
+  if (ws_bytes) *ws_bytes = P.ws;
+  if (n_splits) *n_splits = P.n_splits;
+  return 0;
+}
+
+int dsdf_msdf_prepare(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* tri, size_t tri_bytes,
+                      void* stream) {
+  MsdfPlan P;
+  TRY(msdf_plan(n_faces, 0, &P));
+  if (n_verts <= 0 || n_verts > INT32_MAX)
+    return fail(DSDF_E_INVALID, "mesh sdf: %lld vertices (need 1 .. %d)", (long long)n_verts, INT32_MAX);
+  if (!verts || !faces || !tri) return fail(DSDF_E_INVALID, "mesh sdf prepare: NULL verts, faces or record buffer");
+  if (tri_bytes < P.tri) return fail(DSDF_E_WORKSPACE, "mesh sdf prepare: record buffer %zu < %zu bytes", tri_bytes, P.tri);
+  if (((uintptr_t)tri & 15) != 0) return fail(DSDF_E_INVALID, "mesh sdf prepare: record buffer not 16-byte aligned");
+  const unsigned blocks = (unsigned)((n_faces + MSDF_PREP_BLOCK - 1) / MSDF_PREP_BLOCK);
+  hipLaunchKernelGGL(msdf_prepare_kernel, dim3(blocks), dim3(MSDF_PREP_BLOCK), 0, (hipStream_t)stream, verts, (int)n_verts,
+                     faces, (int)n_faces, (MsdfTri*)tri);
+  LAUNCH_OK("msdf_prepare_kernel");
+  return 0;
+}
+
+int dsdf_msdf_query(const void* tri, int64_t n_faces, const float* queries, int64_t n_queries, float* sdf, float* sqr_dist,
+                    int32_t* face, float* closest, float* winding, int32_t flip_sign, void* ws, size_t ws_bytes, void* stream) {
+  MsdfPlan P;
+  TRY(msdf_plan(n_faces, n_queries, &P));
+  if (!sdf && !sqr_dist && !face && !closest && !winding) return fail(DSDF_E_INVALID, "mesh sdf query: every output is NULL");
+  if (n_queries == 0) return 0;
+  if (!tri || !queries) return fail(DSDF_E_INVALID, "mesh sdf query: NULL record buffer or queries");
+  if (((uintptr_t)tri & 15) != 0) return fail(DSDF_E_INVALID, "mesh sdf query: record buffer not 16-byte aligned");
+  if (!ws) return fail(DSDF_E_INVALID, "mesh sdf query: NULL workspace");
+  if (ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "mesh sdf query: workspace %zu < %zu bytes", ws_bytes, P.ws);
+  const bool dist = sdf || sqr_dist || face || closest, wind = sdf || winding;
+  const size_t slab = (size_t)P.n_splits * (size_t)n_queries;
+  MsdfPartial part;
+  part.d2 = (float*)ws;
+  part.face = (int32_t*)((char*)ws + slab * 4);
+  part.wind = (float*)((char*)ws + slab * 8);
+  const MsdfTri* t = (const MsdfTri*)tri;
+  const int nf = (int)n_faces, nq = (int)n_queries;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)P.qblocks, (unsigned)P.n_splits);
+  if (dist && wind)
+    hipLaunchKernelGGL((msdf_query_kernel<true, true>), grid, dim3(MSDF_BLOCK), 0, st, t, nf, P.chunk, queries, nq, part);
+  else if (dist)
+    hipLaunchKernelGGL((msdf_query_kernel<true, false>), grid, dim3(MSDF_BLOCK), 0, st, t, nf, P.chunk, queries, nq, part);
+  else
+    hipLaunchKernelGGL((msdf_query_kernel<false, true>), grid, dim3(MSDF_BLOCK), 0, st, t, nf, P.chunk, queries, nq, part);
+  LAUNCH_OK("msdf_query_kernel");
+  MsdfOut o;
+  o.sdf = sdf; o.d2 = sqr_dist; o.face = face; o.closest = closest; o.winding = winding; o.flip = flip_sign != 0;
+  hipLaunchKernelGGL(msdf_combine_kernel, dim3((unsigned)P.qblocks), dim3(MSDF_BLOCK), 0, st, t, queries, nq, P.n_splits,
+                     (int)dist, (int)wind, part, o);
+  LAUNCH_OK("msdf_combine_kernel");
   return 0;
 }
 

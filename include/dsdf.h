@@ -27,7 +27,7 @@ extern "C" {
 #endif
 
 #define DSDF_MAX_LAYERS 16
-#define DSDF_ABI_VERSION 16
+#define DSDF_ABI_VERSION 17
 #define DSDF_MAX_BUCKETS 8
 
 enum {
@@ -292,6 +292,31 @@ int dsdf_mc_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float lev
 /* [host] the compiled-in case table (generated by deepsdf_amd/mc_table.py): *width = entries per case (edge ids of its
  * triangles, -1 terminated); table (may be NULL) receives 256 * width int8. */
 int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width);
+
+/* ---- mesh SDF: sdf_sampler/sdf_sampler.py SDFfromMesh (igl.point_mesh_squared_distance + an embree inside test), on the device
+ * Brute force over every face.  Per query p:
+ *   sqr_dist  min over faces of |p - c|^2, c the closest point of the closed triangle, |p - c|^2 from the difference vector;
+ *             a zero-area face counts as its longest edge (or its point).  face = the LOWEST index attaining the minimum,
+ *             closest = c on that face.
+ *   winding   sum over faces of 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) / 4 pi, a, b, c = vertices - p
+ *             (Van Oosterom-Strackee); zero-area faces add nothing.
+ *   sdf       p is inside iff floor(|winding| + 0.5) is odd: sdf = inside ? -sqrt(sqr_dist) : sqrt(sqr_dist), negated when
+ *             flip_sign.  For a closed mesh this is the parity of a ray test and does not depend on face orientation.
+ * Use: dsdf_msdf_plan, dsdf_msdf_prepare once per mesh (verts [n_verts][3] fp32, faces [n_faces][3] int32, 0-based; indices are
+ * clamped into [0, n_verts) on the device -- range-check them on the host), then dsdf_msdf_query as often as needed with the
+ * record buffer `tri`.  Every output of dsdf_msdf_query may be NULL, not all of them: sdf needs both passes, winding alone skips
+ * the distance work, sqr_dist / face / closest alone skip the winding work.
+ * Split rule (n_splits): the query pass runs ceil(n_queries / 256) workgroups of 256 queries; when they are fewer than 2048 the
+ * face range is cut into n_splits = min(ceil(2048 / that), floor(n_faces / 1024), 64) contiguous pieces (at least 1), one
+ * workgroup per (query block, piece), combined in piece order without atomics: sqr_dist, face and closest do not depend on
+ * the split, winding only through its summation order.  Two identical calls give identical bytes.
+ * n_faces and n_queries must fit int32.  n_queries == 0 is valid and launches nothing. */
+int dsdf_msdf_plan(int64_t n_faces, int64_t n_queries, size_t* tri_bytes, size_t* ws_bytes, int32_t* n_splits); /* [host] */
+int dsdf_msdf_prepare(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* tri, size_t tri_bytes,
+                      void* stream);
+/* queries [n_queries][3]; sdf, sqr_dist, winding [n_queries] fp32; face [n_queries] int32; closest [n_queries][3] fp32 */
+int dsdf_msdf_query(const void* tri, int64_t n_faces, const float* queries, int64_t n_queries, float* sdf, float* sqr_dist,
+                    int32_t* face, float* closest, float* winding, int32_t flip_sign, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */
