@@ -6,7 +6,7 @@ import os
 from .build import LIB
 
 MAX_LAYERS = 16
-ABI_VERSION = 17
+ABI_VERSION = 18
 MAX_BUCKETS = 8
 
 
@@ -49,6 +49,23 @@ PROF_NAMES = ("gemm_nt_kernel", "gemm_tn_kernel", "last_layer_kernel", "fused_fo
 class DsdfProfile(C.Structure):
     _fields_ = [("ms", C.c_double * PROF_CLASSES), ("flops", C.c_double * PROF_CLASSES),
                 ("count", C.c_int64 * PROF_CLASSES), ("dropped", C.c_int32)]
+
+
+class DsdfMsGrid(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("tiling", C.c_int32 * 3)]
+
+
+class DsdfMsSpline(C.Structure):
+    _fields_ = [("degree", C.c_int32 * 3), ("n_cp", C.c_int32 * 3), ("n_knots", C.c_int32 * 3),
+                ("knots_host", C.POINTER(C.c_float) * 3), ("knots_dev", C.c_void_p), ("cp", C.c_void_p), ("ncp", C.c_int64),
+                ("L", C.c_int32)]
+
+
+class DsdfMsCap(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("cap", C.c_int32), ("m", C.c_float), ("c", C.c_float)]
+
+
+MS_MAX_CAPS = 6
 
 
 class DsdfError(RuntimeError):
@@ -96,6 +113,8 @@ PROTOTYPES = {
     "dsdf_mc_case_table": [_P, _SZ, C.POINTER(_I32)],
     "dsdf_msdf_plan": [_I64, _I64, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_I32)],
     "dsdf_msdf_prepare": [_P, _I64, _P, _I64, _P, _SZ, _P],
+    "dsdf_ms_rows": [C.POINTER(DsdfMsSpline), C.POINTER(DsdfMsGrid), _I64, _I64, _P, _I32, _I32, _P, _P],
+    "dsdf_ms_caps": [C.POINTER(DsdfMsGrid), _I64, _I64, C.POINTER(DsdfMsCap), _I32, _P, _P],
     "dsdf_msdf_query": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P],
 }
 

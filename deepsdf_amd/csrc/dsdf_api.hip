@@ -21,6 +21,7 @@
 #include "kernels.hpp"
 #include "mcubes.hpp"
 #include "meshsdf.hpp"
+#include "msgrid.hpp"
 
 using namespace dsdf;
 
@@ -2083,6 +2084,108 @@ int dsdf_msdf_query(const void* tri, int64_t n_faces, const float* queries, int6
   hipLaunchKernelGGL(msdf_combine_kernel, dim3((unsigned)P.qblocks), dim3(MSDF_BLOCK), 0, st, t, queries, nq, P.n_splits,
                      (int)dist, (int)wind, part, o);
   LAUNCH_OK("msdf_combine_kernel");
+  return 0;
+}
+
+// ---- microstructure grids (msgrid.hpp) -------------------------------------------------------------------
+namespace {
+int ms_grid(const DsdfMsGrid* in, MsGrid* g, int64_t* npts) {
+  if (!in) return fail(DSDF_E_INVALID, "microstructure: NULL grid");
+  *npts = 1;
+  for (int a = 0; a < 3; ++a) {
+    const int n = in->dims[a], t = in->tiling[a];
+    if (n < 4 || n > MC_MAX_DIM) return fail(DSDF_E_INVALID, "microstructure: padded grid size %d outside 4 .. %d", n, MC_MAX_DIM);
+    if (t < 1) return fail(DSDF_E_INVALID, "microstructure: tiling %d < 1", t);
+    const double vs = 2.0 / (double)(n - 1 - 2), p = 2.0 / (double)t;
+    g->n[a] = n;
+    g->vs[a] = (float)vs;
+    g->org[a] = (float)(-1.0 - vs);
+    g->sub[a] = (float)(t % 2);
+    g->mod[a] = (float)(p * 2.0);
+    g->p[a] = (float)p;
+    g->scale[a] = (float)(2.0 / p);
+    *npts *= n;
+  }
+  return 0;
+}
+
+int ms_spline(const DsdfMsSpline* in, MsSpline* s) {
+  if (!in) return fail(DSDF_E_INVALID, "microstructure: NULL spline");
+  if (in->L < 1) return fail(DSDF_E_INVALID, "microstructure: %d latent columns", in->L);
+  int64_t ncp = 1;
+  int off = 0;
+  for (int a = 0; a < 3; ++a) {
+    const int p = in->degree[a], n = in->n_cp[a];
+    if (p < 1 || p > MS_MAX_DEG) return fail(DSDF_E_INVALID, "microstructure: degree %d of axis %d outside 1 .. %d", p, a, MS_MAX_DEG);
+    if (n <= p || n > (1 << 20)) return fail(DSDF_E_INVALID, "microstructure: %d control points on axis %d (degree %d)", n, a, p);
+    if (in->n_knots[a] != n + p + 1)
+      return fail(DSDF_E_INVALID, "microstructure: knot vector %d has %d entries, needs n + p + 1 = %d", a, in->n_knots[a], n + p + 1);
+    const float* U = in->knots_host[a];
+    if (!U) return fail(DSDF_E_INVALID, "microstructure: NULL knot vector %d", a);
+    for (int i = 0; i < n + p + 1; ++i) {
+      if (!std::isfinite(U[i])) return fail(DSDF_E_INVALID, "microstructure: knot %d of axis %d is not finite", i, a);
+      if (i > 0 && U[i] < U[i - 1]) return fail(DSDF_E_INVALID, "microstructure: knot vector %d is decreasing at entry %d", a, i);
+    }
+    if (!(U[p] < U[n])) return fail(DSDF_E_INVALID, "microstructure: knot vector %d has an empty range", a);
+    s->deg[a] = p; s->ncp[a] = n; s->koff[a] = off;
+    off += n + p + 1;
+    ncp *= n;
+  }
+  if (in->ncp != ncp) return fail(DSDF_E_INVALID, "microstructure: %lld control points, the axes give %lld", (long long)in->ncp, (long long)ncp);
+  if (ncp * (int64_t)in->L > INT32_MAX) return fail(DSDF_E_INVALID, "microstructure: control net of %lld floats (at most %d)", (long long)(ncp * in->L), INT32_MAX);
+  if (!in->knots_dev || !in->cp) return fail(DSDF_E_INVALID, "microstructure: NULL device knots or control points");
+  s->knots = in->knots_dev; s->cp = in->cp; s->L = in->L;
+  return 0;
+}
+}  // namespace
+
+int dsdf_ms_rows(const DsdfMsSpline* spline, const DsdfMsGrid* grid, int64_t start, int64_t end, const float* points,
+                 int32_t inside_test, int32_t with_xyz, float* rows, void* stream) {
+  MsGrid g; MsSpline s;
+  int64_t npts;
+  TRY(ms_grid(grid, &g, &npts));
+  TRY(ms_spline(spline, &s));
+  if (!rows) return fail(DSDF_E_INVALID, "microstructure rows: NULL rows");
+  if (end <= start) return fail(DSDF_E_INVALID, "microstructure rows: empty range [%lld, %lld)", (long long)start, (long long)end);
+  if (!points && (start < 0 || end > npts))
+    return fail(DSDF_E_INVALID, "microstructure rows: range [%lld, %lld) outside the grid's %lld points", (long long)start, (long long)end, (long long)npts);
+  const int64_t n = end - start;
+  if (n > INT32_MAX) return fail(DSDF_E_INVALID, "microstructure rows: %lld points in one call (at most %d)", (long long)n, INT32_MAX);
+  const int64_t blocks = (n + MS_TILE - 1) / MS_TILE;
+  const int64_t first = points ? 0 : start;
+  const int test = points ? (int)(inside_test != 0) : 1, xyz = (int)(with_xyz != 0);
+  if (s.deg[0] == 1 && s.deg[1] == 1 && s.deg[2] == 1)
+    hipLaunchKernelGGL((ms_rows_kernel<true>), dim3((unsigned)blocks), dim3(MS_BLOCK), 0, (hipStream_t)stream, g, s, first, n, points,
+                       test, xyz, rows);
+  else
+    hipLaunchKernelGGL((ms_rows_kernel<false>), dim3((unsigned)blocks), dim3(MS_BLOCK), 0, (hipStream_t)stream, g, s, first, n, points,
+                       test, xyz, rows);
+  LAUNCH_OK("ms_rows_kernel");
+  return 0;
+}
+
+int dsdf_ms_caps(const DsdfMsGrid* grid, int64_t start, int64_t end, const DsdfMsCap* caps, int32_t n_caps, float* sdf, void* stream) {
+  MsGrid g;
+  int64_t npts;
+  TRY(ms_grid(grid, &g, &npts));
+  if (!sdf) return fail(DSDF_E_INVALID, "microstructure caps: NULL sdf");
+  if (end <= start || start < 0 || end > npts)
+    return fail(DSDF_E_INVALID, "microstructure caps: range [%lld, %lld) empty or outside the grid's %lld points", (long long)start, (long long)end, (long long)npts);
+  if (n_caps < 0 || n_caps > MS_MAX_CAPS) return fail(DSDF_E_INVALID, "microstructure caps: %d records (0 .. %d)", n_caps, MS_MAX_CAPS);
+  if (n_caps > 0 && !caps) return fail(DSDF_E_INVALID, "microstructure caps: NULL records");
+  MsCaps c;
+  c.n = n_caps;
+  for (int r = 0; r < n_caps; ++r) {
+    if (caps[r].dim < 0 || caps[r].dim > 2) return fail(DSDF_E_INVALID, "microstructure caps: record %d names axis %d", r, caps[r].dim);
+    if (caps[r].cap != -1 && caps[r].cap != 1) return fail(DSDF_E_INVALID, "microstructure caps: record %d has cap %d (must be -1 or 1)", r, caps[r].cap);
+    if (caps[r].m != -1.f && caps[r].m != 1.f) return fail(DSDF_E_INVALID, "microstructure caps: record %d has multiplier %g (must be -1 or 1)", r, (double)caps[r].m);
+    if (!std::isfinite(caps[r].c)) return fail(DSDF_E_INVALID, "microstructure caps: record %d has a non-finite plane", r);
+    c.r[r].dim = caps[r].dim; c.r[r].cap = caps[r].cap; c.r[r].m = caps[r].m; c.r[r].c = caps[r].c;
+  }
+  const int64_t n = end - start;
+  hipLaunchKernelGGL(ms_caps_kernel, dim3((unsigned)((n + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, (hipStream_t)stream, g, c,
+                     start, n, sdf);
+  LAUNCH_OK("ms_caps_kernel");
   return 0;
 }
 

@@ -7,12 +7,15 @@ convert_sdf_samples_to_ply :86-155) with every step on the GPU.
     mesh   marching_cubes   HIP marching cubes (csrc/mcubes.hpp, dsdf_mc_count / dsdf_mc_emit): one host sync per mesh, to
                             read the two totals and allocate exact outputs
     file   write_ply        one header + two buffer writes, byte for byte what plyfile writes for the reference's dtypes
+    tiled  microstructure_sdf_grid / create_mesh_microstructure / sdf_struct: a B-spline latent field over mirrored unit cells
+                            (create_mesh_microstructure :157-342): rows and caps by csrc/msgrid.hpp around the same decode
 
 There is no CPU path: the grid and the marching cubes need a HIP device (a grid handed in on the host is moved there).
 """
 import ctypes as C
 import logging
 import time
+from typing import TypedDict
 
 import numpy as np
 import torch
@@ -197,3 +200,189 @@ def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_s
         verts = verts - torch.as_tensor(offset, dtype=torch.float32, device=verts.device)
     write_ply(ply_filename_out, verts, faces)
     logger.debug("converting to ply format and writing to file took %f s", time.time() - start)
+
+
+# ---- microstructures: a spline latent field over tiled, mirrored unit cells ------------------------------------------------
+# deep_sdf/mesh.py create_mesh_microstructure and analysis/geometry.py sdf_struct.  Per chunk of the padded grid the row kernel
+# (dsdf_ms_rows) writes [spline latent | folded xyz], the decoder turns rows into SDF values, the cap kernel (dsdf_ms_caps) cuts
+# the borders in place; the grid never leaves the device.
+location_lookup = {"x0": (0, -1), "x1": (0, 1), "y0": (1, -1), "y1": (1, 1), "z0": (2, -1), "z1": (2, 1)}
+
+CapType = TypedDict("CapType", {"cap": int, "measure": float})
+CapBorderDict = TypedDict("CapBorderDict", {loc: CapType for loc in location_lookup}, total=False)
+
+
+def default_cap_border_dict():
+    """Cap -1 (cut the structure flush) with measure 0 on all six faces."""
+    return {loc: {"cap": -1, "measure": 0} for loc in location_lookup}
+
+
+def _int_triple(x, what):
+    if isinstance(x, (list, tuple, np.ndarray)):
+        if len(x) != 3:
+            raise ValueError(f"{what} must be a list of 3 integers")
+        return [int(v) for v in x]
+    if isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+        return [int(x)] * 3
+    raise ValueError(f"{what} must be a list or an integer")
+
+
+def _ms_grid(tiling, N):
+    """DsdfMsGrid of the padded grid (N + 2 per axis) and its voxel sizes as the reference computes them (double)."""
+    t, n = _int_triple(tiling, "Tiling"), _int_triple(N, "Number of grid points")
+    if min(t) < 1:
+        raise ValueError(f"Tiling must be positive, got {t}")
+    if min(n) < 2:
+        raise ValueError(f"Number of grid points must be at least 2 per axis, got {n}")
+    g = _lib.DsdfMsGrid()
+    for a in range(3):
+        g.dims[a], g.tiling[a] = n[a] + 2, t[a]
+    return g, [2.0 / (n[a] + 2 - 1 - 2) for a in range(3)]
+
+
+def cap_records(cap_border_dict):
+    """The ordered (dim, m, measure, cap) records of a cap dictionary, in the dictionary's own iteration order (a min and a max do
+    not commute).  None, or the CapBorderDict class itself (the reference's default argument): the defaults."""
+    if cap_border_dict is None or cap_border_dict is CapBorderDict:
+        cap_border_dict = default_cap_border_dict()
+    if len(cap_border_dict) > _lib.MS_MAX_CAPS:
+        raise ValueError(f"at most {_lib.MS_MAX_CAPS} cap entries, got {len(cap_border_dict)}")
+    recs = (_lib.DsdfMsCap * max(len(cap_border_dict), 1))()
+    for r, (loc, d) in enumerate(cap_border_dict.items()):
+        if loc not in location_lookup:
+            raise ValueError(f"unknown cap location {loc!r} (one of {list(location_lookup)})")
+        cap, measure = d["cap"], d["measure"]
+        if cap not in (-1, 1):
+            raise ValueError("Cap must be -1 or 1")
+        dim, m = location_lookup[loc]
+        recs[r].dim, recs[r].cap, recs[r].m, recs[r].c = dim, int(cap), float(m), float(m * (1 - measure))
+    return recs, len(cap_border_dict)
+
+
+def ms_grid_rows(field, tiling, N, start, end, device=None):
+    """Decoder input rows [end - start, L + 3] = [spline latent | folded xyz] of points [start, end) of the padded grid."""
+    from .spline import as_field
+    field = as_field(field)
+    g, _ = _ms_grid(tiling, N)
+    device = torch.device("cuda" if device is None else device)
+    with torch.cuda.device(device):
+        s, _keep = field.c_spline(device)
+        rows = torch.empty(max(end - start, 0), s.L + 3, dtype=torch.float32, device=device)
+        _lib.check(_lib.lib().dsdf_ms_rows(C.byref(s), C.byref(g), start, end, None, 1, 1, _ptr(rows), _stream()))
+    return rows
+
+
+def ms_point_rows(field, tiling, points, inside_test=False, with_xyz=True):
+    """Rows for an explicit list of points [n, 3] (device tensor): [spline latent | folded xyz], or the latent columns alone.
+    inside_test: rows of points outside [-1, 1]^3 get zero latents as on the grid; off, the point is clamped to the knot range."""
+    from .spline import as_field
+    field = as_field(field)
+    g, _ = _ms_grid(tiling, 2)
+    pts = points.detach().to(torch.float32).contiguous()
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.device.type != "cuda":
+        raise ValueError("ms_point_rows expects a device tensor [n, 3]")
+    with torch.cuda.device(pts.device):
+        s, _keep = field.c_spline(pts.device)
+        rows = torch.empty(pts.shape[0], s.L + (3 if with_xyz else 0), dtype=torch.float32, device=pts.device)
+        if pts.shape[0] > 0:
+            _lib.check(_lib.lib().dsdf_ms_rows(C.byref(s), C.byref(g), 0, pts.shape[0], _ptr(pts), int(bool(inside_test)),
+                                               int(bool(with_xyz)), _ptr(rows), _stream()))
+    return rows
+
+
+def ms_apply_caps(sdf, N, start, end, cap_border_dict=None):
+    """Caps in place on sdf [end - start] (contiguous fp32 device tensor), the values of points [start, end) of the padded grid."""
+    g, _ = _ms_grid(1, N)
+    recs, n = cap_records(cap_border_dict)
+    if sdf.dtype != torch.float32 or not sdf.is_contiguous() or sdf.numel() != end - start or sdf.device.type != "cuda":
+        raise ValueError("ms_apply_caps expects a contiguous fp32 device tensor of end - start values")
+    with torch.cuda.device(sdf.device):
+        _lib.check(_lib.lib().dsdf_ms_caps(C.byref(g), start, end, recs, n, _ptr(sdf), _stream()))
+    return sdf
+
+
+def microstructure_sdf_grid(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None, apply_caps=True):
+    """The capped SDF of a microstructure on the padded grid, a device tensor [Nx + 2, Ny + 2, Nz + 2] (axis 0 = x).
+
+    The design domain [-1, 1]^3 is tiled with tiling[a] mirrored copies of the unit cell per axis; `field` (a BSplineField, or a
+    splinepy BSpline) gives every point its latent code.  This package's Decoder decodes through its Engine, weights
+    materialised once; any other nn.Module is called on the rows.  The result does not depend on max_batch."""
+    from .spline import as_field
+    field = as_field(field)
+    dec = _unwrap(decoder)
+    hip = _is_hip_decoder(dec)
+    if hip:
+        device = dec._arena.device
+    elif device is None:
+        device = torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DsdfError("microstructure_sdf_grid needs a HIP device (no CPU fallback)")
+    g, _ = _ms_grid(tiling, N)
+    recs, n_caps = cap_records(cap_border_dict)
+    dims = list(g.dims)
+    n = dims[0] * dims[1] * dims[2]
+    max_batch = int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"max_batch must be positive, got {max_batch}")
+    lib = _lib.lib()
+    with torch.no_grad(), torch.cuda.device(device):
+        s, _keep = field.c_spline(device)
+        out = torch.empty(n, dtype=torch.float32, device=device)
+        rows = torch.empty(min(n, max_batch), s.L + 3, dtype=torch.float32, device=device)
+        if hip:
+            eng = dec.engine()
+            eng.materialize()
+        for b in range(0, n, max_batch):
+            e = min(n, b + max_batch)
+            r = rows[:e - b]
+            _lib.check(lib.dsdf_ms_rows(C.byref(s), C.byref(g), b, e, None, 1, 1, _ptr(r), _stream()))
+            y = eng.decode(r) if hip else dec(r)
+            out[b:e] = y.reshape(-1)
+            if apply_caps:
+                _lib.check(lib.dsdf_ms_caps(C.byref(g), b, e, recs, n_caps, C.c_void_p(out.data_ptr() + 4 * b), _stream()))
+    return out.view(*dims)
+
+
+def create_mesh_microstructure(tiling, decoder, latent_vec_interpolation, filename, N=256, max_batch=32 ** 3, offset=None,
+                               scale=None, cap_border_dict=None, save_ply_file=False, use_flexicubes=False, device=None,
+                               output_tetmesh=False, compute_derivatives=False):
+    """deep_sdf/mesh.py create_mesh_microstructure: mesh the zero level set of the tiled, capped structure.
+
+    save_ply_file: writes ``filename + ".ply"`` (vertices + voxel origin, / scale, - offset) and returns None; otherwise returns
+    (verts [V, 3] float64, faces [F, 3] int32) as numpy arrays, verts = (index-space vertices * voxel_size - voxel_size) / 2,
+    which maps the design domain onto [0, 1]^3."""
+    tiling = _int_triple(tiling, "Tiling")
+    n = _int_triple(N, "Number of grid points")
+    if use_flexicubes or output_tetmesh or compute_derivatives:
+        raise NotImplementedError("use_flexicubes / output_tetmesh / compute_derivatives need kaolin's FlexiCubes, which this "
+                                  "package does not carry: only marching cubes is implemented")
+    start = time.time()
+    decoder.eval()
+    _, voxel_size = _ms_grid(tiling, n)
+    voxel_origin = [-1 - v for v in voxel_size]
+    grid = microstructure_sdf_grid(tiling, decoder, latent_vec_interpolation, n, max_batch, cap_border_dict, device)
+    logger.debug("sampling takes: %f", time.time() - start)
+    if save_ply_file:
+        convert_sdf_samples_to_ply(grid, voxel_origin, voxel_size, filename + ".ply", offset, scale)
+        return None
+    verts, faces = marching_cubes(grid, 0.0, voxel_size)
+    vs = np.array(voxel_size)
+    return (verts.cpu().numpy() - vs) / 2, faces.cpu().numpy()
+
+
+def sdf_struct(decoder, queries, tiling, latent_vec_interpolation, device=None):
+    """analysis/geometry.py sdf_struct: the structure's SDF (no caps) at queries [n, 3], a numpy array [n].  The spline is
+    evaluated at every query (clamped to its knot range), the decoder at the folded coordinate."""
+    dec = _unwrap(decoder)
+    hip = _is_hip_decoder(dec)
+    if hip:
+        device = dec._arena.device
+    elif device is None:
+        device = torch.device("cuda")
+    q = torch.as_tensor(queries, dtype=torch.float32).to(device)
+    tiling = _int_triple(tiling, "Tiling")
+    with torch.no_grad():
+        rows = ms_point_rows(latent_vec_interpolation, tiling, q, inside_test=False)
+        y = dec.engine().decode(rows) if hip else dec(rows)
+    return y.reshape(-1).detach().cpu().numpy()

@@ -27,7 +27,7 @@ extern "C" {
 #endif
 
 #define DSDF_MAX_LAYERS 16
-#define DSDF_ABI_VERSION 17
+#define DSDF_ABI_VERSION 18
 #define DSDF_MAX_BUCKETS 8
 
 enum {
@@ -317,6 +317,57 @@ int dsdf_msdf_prepare(const float* verts, int64_t n_verts, const int32_t* faces,
 /* queries [n_queries][3]; sdf, sqr_dist, winding [n_queries] fp32; face [n_queries] int32; closest [n_queries][3] fp32 */
 int dsdf_msdf_query(const void* tri, int64_t n_faces, const float* queries, int64_t n_queries, float* sdf, float* sqr_dist,
                     int32_t* face, float* closest, float* winding, int32_t flip_sign, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- microstructure grids: deep_sdf/mesh.py create_mesh_microstructure / analysis/geometry.py sdf_struct, the parts in front of
+ * and behind the decoder (csrc/msgrid.hpp) ----------------------------------------------------------------------------------
+ * The padded grid has dims[a] = N[a] + 2 points per axis (linear index, z fastest).  Unfolded coordinate of index i on axis a:
+ *   xo = (fp32(i) * voxel_size) + voxel_origin, voxel_size = 2 / (dims[a] - 3), voxel_origin = -1 - voxel_size, both computed in
+ *   double and rounded to fp32 once; one rounded multiply and one rounded add, never an FMA.
+ * Folded coordinate, t = tiling[a], p = 2 / t:  (2/p) * |((xo - t%2) mod 2p) - p| - 1, mod the floored remainder (fmodf, plus 2p
+ * when the result is non-zero and negative), every operation rounded on its own, constants rounded from double once.
+ * Inside: -1 <= xo <= 1 on all three axes.
+ * dsdf_ms_rows writes rows [n][L + 3] (or [n][L] when with_xyz == 0) fp32 = [spline(xo) | folded xo]:
+ *   grid mode   (points == NULL): points [start, end) of the padded grid, n = end - start; rows of outside points have exact
+ *               zeros in the latent columns (inside_test is ignored: it is always on)
+ *   point mode  (points != NULL, device [n][3], n = end - start, start is ignored): xo is the given point.  inside_test != 0: as
+ *               the grid; inside_test == 0: every row gets the spline at the point clamped to the knot range (sdf_struct).
+ * The spline: degree 1..3 per axis, knot vectors with n_cp[a] + degree[a] + 1 non-decreasing entries and a non-empty range
+ * knots[degree] < knots[n_cp]; control points cp [ncp][L], ncp = n_cp[0] * n_cp[1] * n_cp[2], first parametric axis fastest.
+ * The parametric coordinate is clamped to the knot range and the span search stops at the last non-empty span, so the right
+ * end evaluates to the end value.  knots_host are checked on the host; knots_dev is the device copy the kernel reads (the three
+ * vectors one after another, axis 0 first) and must hold the same values.
+ * dsdf_ms_caps works in place on sdf [end - start], the values of grid points [start, end): first the n_caps records in the
+ * order given -- border = (xo[dim] - c) * -m; cap -1: sdf = max(sdf, -border); cap 1: sdf = min(sdf, border); m = -1 or 1,
+ * c = m * (1 - measure) rounded from double by the caller -- then the six planes of the unit cube with max (x-, x+, y-, y+,
+ * z-, z+).  Every argument error returns DSDF_E_INVALID before anything is launched. */
+#define DSDF_MS_MAX_CAPS 6
+typedef struct DsdfMsGrid {
+  int32_t dims[3];                 /* padded: N + 2, each 4 .. 1024 */
+  int32_t tiling[3];               /* >= 1 */
+} DsdfMsGrid;
+
+typedef struct DsdfMsSpline {
+  int32_t degree[3];               /* 1 .. 3 */
+  int32_t n_cp[3];                 /* control points per axis, > degree */
+  int32_t n_knots[3];              /* must equal n_cp + degree + 1 */
+  const float* knots_host[3];      /* [host] */
+  const float* knots_dev;          /* device, n_knots[0] + n_knots[1] + n_knots[2] floats */
+  const float* cp;                 /* device [ncp][L] */
+  int64_t ncp;                     /* must equal n_cp[0] * n_cp[1] * n_cp[2] */
+  int32_t L;                       /* >= 1 */
+} DsdfMsSpline;
+
+typedef struct DsdfMsCap {
+  int32_t dim;                     /* 0 .. 2 */
+  int32_t cap;                     /* -1 or 1 */
+  float m;                         /* -1 or 1 */
+  float c;                         /* m * (1 - measure) */
+} DsdfMsCap;
+
+int dsdf_ms_rows(const DsdfMsSpline* spline, const DsdfMsGrid* grid, int64_t start, int64_t end, const float* points,
+                 int32_t inside_test, int32_t with_xyz, float* rows, void* stream);
+int dsdf_ms_caps(const DsdfMsGrid* grid, int64_t start, int64_t end, const DsdfMsCap* caps /*[host]*/, int32_t n_caps, float* sdf,
+                 void* stream);
 
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */

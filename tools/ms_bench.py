@@ -1,0 +1,177 @@
+"""Time of one microstructure mesh (deepsdf_amd/mesh.py create_mesh_microstructure) split into its steps, and the row kernel
+against the same rows composed from torch ops.  One JSON line per (net, L) and one per L for the row kernel.
+
+    python tools/ms_bench.py [--nets 8x512 4x64] [--L 16 256] [--N 256] [--tiling 4 4 4] [--max-batch 32768] [--reps 5]
+
+mesh lines   rows_ms / decode_ms / caps_ms: HIP events around each step of every chunk, summed over the grid (the loop of
+             microstructure_sdf_grid restated with events between the steps); mc_ms: events around marching_cubes; total_ms: host
+             clock around microstructure_sdf_grid + marching_cubes as the library runs them, ending in a synchronise.  Median of
+             --reps after one warm-up, with min and max of the total.
+row lines    dsdf_ms_rows on one range of --row-points grid points, 20 launches after 3 warm-ups: median, min, max; the bytes it
+             must write ((L + 3) * 4 per point) over the median as GB/s, beside the measured HBM copy rate of MI355X (6.29 TB/s
+             for reading and writing, MI355X_MICROARCH.md); and the same rows from torch ops on the device (index arithmetic, the
+             fold, a degree-1 basis and a matmul for the spline, a concatenation), checked against the kernel's before timing.
+
+Nets: seeded (nn.Linear init) decoders of bench.py's NetworkSpecs with CodeLength L; the output bias is shifted so that the zero
+level set crosses the structure.  A (net, L) pair for which no net exists (4x64 with L = 256) is reported as skipped.  The field: degree 1, 2 x 2 x 2 seeded codes.
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from deepsdf_amd.decoder import Decoder  # noqa: E402
+from deepsdf_amd.mesh import marching_cubes, microstructure_sdf_grid, ms_apply_caps, ms_grid_rows  # noqa: E402
+from deepsdf_amd.spline import BSplineField  # noqa: E402
+
+HBM_COPY_TBS = 6.29
+
+
+def make_field(L):
+    cp = torch.randn(8, L, generator=torch.Generator().manual_seed(2)) * (0.5 / math.sqrt(L))
+    return BSplineField([1, 1, 1], [[-1, -1, 1, 1]] * 3, cp.numpy())
+
+
+def make_decoder(name, L, field, tiling):
+    torch.manual_seed(0)
+    dec = Decoder(L, **bench.NETWORKS[name]["net"]).cuda().eval()
+    with torch.no_grad():
+        y = microstructure_sdf_grid(tiling, dec, field, 32, apply_caps=False)
+        last = getattr(dec, f"lin{dec.spec.n_layers - 1}")
+        last.bias -= torch.atanh(y[1:-1, 1:-1, 1:-1].median())
+    return dec
+
+
+def ev():
+    return torch.cuda.Event(enable_timing=True)
+
+
+def staged(dec, field, tiling, N, max_batch):
+    """The chunk loop of microstructure_sdf_grid with events between its steps: (rows_ms, decode_ms, caps_ms)."""
+    n = (N + 2) ** 3
+    out = torch.empty(n, dtype=torch.float32, device="cuda")
+    eng = dec.engine()
+    eng.materialize()
+    marks = []
+    with torch.no_grad():
+        for b in range(0, n, max_batch):
+            e = min(n, b + max_batch)
+            m = [ev() for _ in range(4)]
+            m[0].record()
+            rows = ms_grid_rows(field, tiling, N, b, e)
+            m[1].record()
+            out[b:e] = eng.decode(rows).reshape(-1)
+            m[2].record()
+            ms_apply_caps(out[b:e], N, b, e)
+            m[3].record()
+            marks.append(m)
+    torch.cuda.synchronize()
+    return tuple(sum(m[i].elapsed_time(m[i + 1]) for m in marks) for i in range(3))
+
+
+def whole(dec, field, tiling, N, max_batch):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    grid = microstructure_sdf_grid(tiling, dec, field, N, max_batch)
+    e0, e1 = ev(), ev()
+    e0.record()
+    h = 2.0 / (N - 1)
+    v, f = marching_cubes(grid, 0.0, (h, h, h))
+    e1.record()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, e0.elapsed_time(e1), v.shape[0], f.shape[0]
+
+
+def torch_rows(cp, tiling, N, start, end):
+    """The rows of dsdf_ms_rows for a degree-1, 2 x 2 x 2 field from torch ops on the device."""
+    n = N + 2
+    vs = 2.0 / (n - 1 - 2)
+    idx = torch.arange(start, end, dtype=torch.int64, device=cp.device)
+    xo = torch.stack([(idx // n) // n, (idx // n) % n, idx % n], 1).to(torch.float32) * vs + (-1 - vs)
+    inside = ((xo >= -1) & (xo <= 1)).all(1, keepdim=True)
+    u = ((xo + 1) * 0.5).clamp(0, 1)
+    B = torch.stack([1 - u, u], 2)                                           # [n, axis, 2]
+    w = torch.einsum("pi,pj,pk->pkji", B[:, 0], B[:, 1], B[:, 2]).reshape(-1, 8)
+    lat = (w @ cp) * inside
+    cols = []
+    for a, t in enumerate(tiling):
+        p = 2.0 / t
+        cols.append((2 / p) * torch.abs((xo[:, a] - t % 2) % (p * 2) - p) - 1)
+    return torch.cat([lat, torch.stack(cols, 1)], 1)
+
+
+def timed(fn, reps, warm):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = ev(), ev()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nets", nargs="+", default=["8x512", "4x64"], choices=sorted(bench.NETWORKS))
+    ap.add_argument("--L", nargs="+", type=int, default=[16, 256])
+    ap.add_argument("--N", type=int, default=256)
+    ap.add_argument("--tiling", nargs=3, type=int, default=[4, 4, 4])
+    ap.add_argument("--max-batch", type=int, default=32 ** 3, help="chunk (create_mesh_microstructure's max_batch)")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--row-points", type=int, default=1 << 21, help="points of the row-kernel measurement")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ms_bench.py needs an AMD GPU: nothing here can be timed on a CPU")
+    dev = torch.cuda.get_device_name(0)
+    N, tiling = args.N, args.tiling
+    for L in args.L:
+        field = make_field(L)
+        cp = torch.from_numpy(np.ascontiguousarray(field.control_points, dtype=np.float32)).cuda()
+        n = min(args.row_points, (N + 2) ** 3)
+        start = ((N + 2) ** 3 - n) // 2
+        k = ms_grid_rows(field, tiling, N, start, start + n)
+        t = torch_rows(cp, tiling, N, start, start + n)
+        diff = float((k - t).abs().max())
+        assert diff < 1e-5, diff                                  # the same rows up to fp32 rounding of the composed ops
+        del k, t
+        km = timed(lambda: ms_grid_rows(field, tiling, N, start, start + n), 20, 3)
+        tm = timed(lambda: torch_rows(cp, tiling, N, start, start + n), 20, 3)
+        gb = n * (L + 3) * 4 / 1e9
+        print(json.dumps(dict(what="rows", L=L, points=n, kernel_ms=[round(x, 4) for x in km], torch_ops_ms=[round(x, 4) for x in tm],
+                              kernel_write_gbs=round(gb / km[0] * 1e3, 1), share_of_hbm_copy_rate=round(gb / km[0] / HBM_COPY_TBS, 3),
+                              torch_over_kernel=round(tm[0] / km[0], 2), max_abs_diff=diff, device=dev)), flush=True)
+        for name in args.nets:
+            spec = bench.NETWORKS[name]["net"]
+            if any(spec["dims"][l - 1] <= L + 3 for l in spec["latent_in"]):
+                # the layer in front of a latent_in layer has dims - (L + 3) outputs: no such net exists
+                print(json.dumps(dict(what="mesh", net=name, L=L, skipped=f"no {name} net with latent_in {spec['latent_in']} "
+                                      f"exists for L = {L}: the layer before it would have {spec['dims'][0]} - {L + 3} outputs")), flush=True)
+                continue
+            dec = make_decoder(name, L, field, tiling)
+            staged(dec, field, tiling, N, args.max_batch)
+            st = [staged(dec, field, tiling, N, args.max_batch) for _ in range(args.reps)]
+            wh = [whole(dec, field, tiling, N, args.max_batch) for _ in range(args.reps)]
+            rows, decode, caps = (statistics.median(s[i] for s in st) for i in range(3))
+            tot = [w[0] for w in wh]
+            print(json.dumps(dict(what="mesh", net=name, L=L, N=N, tiling=tiling, max_batch=args.max_batch, rows_ms=round(rows, 3),
+                                  decode_ms=round(decode, 3), caps_ms=round(caps, 3),
+                                  mc_ms=round(statistics.median(w[1] for w in wh), 3), total_ms=round(statistics.median(tot), 3),
+                                  total_min_max_ms=[round(min(tot), 3), round(max(tot), 3)],
+                                  rows_share_of_chunk=round(rows / (rows + decode + caps), 4), V=wh[-1][2], F=wh[-1][3],
+                                  device=dev)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
