@@ -6,7 +6,7 @@ import os
 from .build import LIB
 
 MAX_LAYERS = 16
-ABI_VERSION = 18
+ABI_VERSION = 19
 MAX_BUCKETS = 8
 
 
@@ -68,6 +68,15 @@ class DsdfMsCap(C.Structure):
 MS_MAX_CAPS = 6
 
 
+class DsdfWsRegion(C.Structure):      # debug only: one row of dsdf_debug_ws_regions
+    _fields_ = [("name", C.c_char * 24), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+WS_MAX_REGIONS = 192
+WS_MAX_REDZONE = 4096
+WS_PLAN_TRAIN, WS_PLAN_DECODE, WS_PLAN_DECODE_LATENT = 0, 1, 2
+
+
 class DsdfError(RuntimeError):
     pass
 
@@ -115,6 +124,9 @@ PROTOTYPES = {
     "dsdf_msdf_prepare": [_P, _I64, _P, _I64, _P, _SZ, _P],
     "dsdf_ms_rows": [C.POINTER(DsdfMsSpline), C.POINTER(DsdfMsGrid), _I64, _I64, _P, _I32, _I32, _P, _P],
     "dsdf_ms_caps": [C.POINTER(DsdfMsGrid), _I64, _I64, C.POINTER(DsdfMsCap), _I32, _P, _P],
+    "dsdf_debug_ws_redzone": [_I32],
+    "dsdf_debug_ws_regions": [C.POINTER(DsdfWsRegion), _I32, C.POINTER(_I32), C.POINTER(_SZ)],
+    "dsdf_debug_ws_plan": [_NET, _I64, _I64, _I32, _I32, _I32, _I32],
     "dsdf_msdf_query": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P],
 }
 
@@ -144,6 +156,15 @@ def lib():
         raise DsdfError(f"libdsdf_hip.so ABI {v} != binding ABI {ABI_VERSION}: rebuild")
     _lib = h
     return h
+
+
+def ws_regions():
+    """Debug only: (rows, total) of the last workspace plan laid out on this thread (dsdf_debug_ws_regions);
+    rows = [(name, offset, bytes)] in layout order."""
+    n, total = C.c_int32(), C.c_size_t()
+    table = (DsdfWsRegion * WS_MAX_REGIONS)()
+    check(lib().dsdf_debug_ws_regions(table, WS_MAX_REGIONS, C.byref(n), C.byref(total)))
+    return [(table[i].name.decode(), int(table[i].offset), int(table[i].bytes)) for i in range(n.value)], int(total.value)
 
 
 def check(rc):

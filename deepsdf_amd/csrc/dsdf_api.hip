@@ -290,6 +290,26 @@ void dw_bucket_cuts(const DsdfNet* n, int K, int* cut) {
 }
 
 // ---- workspace plan -----------------------------------------------------------------------------
+// Debug-only view of the planners (dsdf_debug_ws_redzone / dsdf_debug_ws_regions, include/dsdf.h).  Every take() of a planner
+// is followed by g_redzone unused bytes (0 by default: the layout is then exactly the one without this mechanism), and a planner
+// that is handed a WsTable writes one {name, offset, exact bytes} row per take().  Every entry point that launches on a
+// workspace hands its planner the thread's t_last_plan, so a test can read the layout a launch actually used and compare
+// every byte outside the regions with what it put there.  Recording is a few stores per take(): no string is formatted
+// before the table is read.
+std::atomic<size_t> g_redzone{0};
+struct WsRow { const char* name; int idx; size_t off, bytes; };
+struct WsTable {
+  int n, dropped;
+  size_t total;
+  WsRow row[DSDF_WS_MAX_REGIONS];
+  void reset() { n = 0; dropped = 0; total = 0; }
+  void add(const char* name, int idx, size_t off, size_t bytes) {
+    if (n < DSDF_WS_MAX_REGIONS) row[n++] = WsRow{name, idx, off, bytes};
+    else ++dropped;
+  }
+};
+thread_local WsTable t_last_plan;
+
 struct Plan {
   int nl, W0, N, R;
   int ld_in[DSDF_MAX_LAYERS];
@@ -313,44 +333,54 @@ struct Plan {
 
 // nb: the bucket count the workspace is laid out for (DsdfLossCfg.dw_buckets; every call of one step passes the same one).
 // 2 also serves the un-phased step, so dsdf_workspace_bytes' answer covers K <= 2.
-Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segmode = false, int nb = 2, int frows = FROWS) {
+// rec: the table that receives one row per take() (launching entry points: &t_last_plan; size queries: none).
+Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segmode = false, int nb = 2, int frows = FROWS,
+               WsTable* rec = nullptr) {
   Plan P;
   memset(&P, 0, sizeof(P));
   P.frows = frows;
   P.nl = n->n_layers; P.W0 = n->latent_size + n->geom_dim; P.N = (int)N; P.R = (int)R;
   size_t o = 0;
-  auto take = [&](size_t bytes) { size_t r = o; o += (size_t)rup((int64_t)bytes, 256); return r; };
+  const size_t guard = g_redzone.load(std::memory_order_relaxed);
+  if (rec) rec->reset();
+  auto take = [&](const char* name, int idx, size_t bytes) {
+    size_t r = o;
+    o += (size_t)rup((int64_t)bytes, 256) + guard;
+    if (rec) rec->add(name, idx, r, bytes);
+    return r;
+  };
   int maxw = 4;
   for (int l = 0; l < P.nl; ++l) {
     P.ld_in[l] = (int)rup(n->in_dim[l], 4);
     if (P.ld_in[l] > maxw) maxw = P.ld_in[l];
   }
   if (inference) {
-    size_t pp[2] = {take((size_t)N * maxw * 4), take((size_t)N * maxw * 4)};
+    size_t pp[2] = {take("pp", 0, (size_t)N * maxw * 4), take("pp", 1, (size_t)N * maxw * 4)};
     for (int l = 0; l < P.nl; ++l) {
       // (xyz_in_all: every layer input carries xyz columns the gather pre-fills, so none of them can share a ping-pong buffer)
-      if (l == 0 || ((n->skip_mask >> l) & 1) || n->xyz_in_all) P.in_off[l] = take((size_t)N * P.ld_in[l] * 4);
+      if (l == 0 || ((n->skip_mask >> l) & 1) || n->xyz_in_all) P.in_off[l] = take("in", l, (size_t)N * P.ld_in[l] * 4);
       else P.in_off[l] = pp[l & 1];
     }
     if (n->ln_param_mask) {   // one scratch row block for the Linear's output before LayerNorm (nothing is kept in inference)
-      const size_t t = take((size_t)N * maxw * 4);
+      const size_t t = take("lnx", -1, (size_t)N * maxw * 4);
       for (int l = 0; l < P.nl; ++l) P.lnx_off[l] = t;
     }
     P.total = o;
+    if (rec) rec->total = o;
     return P;
   }
-  for (int l = 0; l < P.nl; ++l) P.in_off[l] = take((size_t)N * P.ld_in[l] * 4 + 4096);   // + slack: edge tiles of dw_stream over-read
-  P.u_off = take((size_t)N * 4);
-  P.y_off = take((size_t)N * 4);
+  for (int l = 0; l < P.nl; ++l) P.in_off[l] = take("in", l, (size_t)N * P.ld_in[l] * 4 + 4096);   // + slack: edge tiles of dw_stream over-read
+  P.u_off = take("u", -1, (size_t)N * 4);
+  P.y_off = take("y", -1, (size_t)N * 4);
   P.ld_dp = maxw;
-  P.dp_off[0] = take((size_t)N * maxw * 4);
-  P.dp_off[1] = take((size_t)N * maxw * 4);
+  P.dp_off[0] = take("dp", 0, (size_t)N * maxw * 4);
+  P.dp_off[1] = take("dp", 1, (size_t)N * maxw * 4);
   P.ldz = (int)rup(P.W0, 4);
-  P.dzA_off = take((size_t)N * P.ldz * 4);
-  P.dzB_off = take((size_t)N * P.ldz * 4);
-  for (int t = 0; t < 2; ++t) P.dxz_off[t] = n->xyz_in_all ? take((size_t)N * 4 * 4) : 0;   // [N][4]: one layer's d/d(xyz), running sum
+  P.dzA_off = take("dzA", -1, (size_t)N * P.ldz * 4);
+  P.dzB_off = take("dzB", -1, (size_t)N * P.ldz * 4);
+  for (int t = 0; t < 2; ++t) P.dxz_off[t] = n->xyz_in_all ? take("dxz", t, (size_t)N * 4 * 4) : 0;   // [N][4]: one layer's d/d(xyz), running sum
   for (int l = 0; l + 1 < P.nl; ++l)
-    if ((n->ln_param_mask >> l) & 1) { P.lnx_off[l] = take((size_t)N * P.ld_in[l + 1] * 4); P.lnr_off[l] = take((size_t)N * 4); }
+    if ((n->ln_param_mask >> l) & 1) { P.lnx_off[l] = take("lnx", l, (size_t)N * P.ld_in[l + 1] * 4); P.lnr_off[l] = take("lnr", l, (size_t)N * 4); }
   // split-K of the dW GEMMs: chunks of >= 256 points, at most NSPLIT_MAX slabs
   int ns = (int)((N + 255) / 256);
   if (ns > NSPLIT_MAX) ns = NSPLIT_MAX;
@@ -367,11 +397,11 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
     if (n->out_dim[l] > maxout) maxout = n->out_dim[l];
   }
   P.slab = rup(maxslab, 64);
-  P.slab_off = take((size_t)P.nsplit * P.slab * 4);
+  P.slab_off = take("slab", -1, (size_t)P.nsplit * P.slab * 4);
   P.mt = (int)((N + BM - 1) / BM);
   P.ldcs = (int)rup(maxout, 4);
-  P.colsum_off = take((size_t)P.mt * P.ldcs * 4);
-  if (n->ln_param_mask) { P.lnpg_off = take((size_t)LN_BLOCKS * P.ldcs * 4); P.lnpb_off = take((size_t)LN_BLOCKS * P.ldcs * 4); }
+  P.colsum_off = take("colsum", -1, (size_t)P.mt * P.ldcs * 4);
+  if (n->ln_param_mask) { P.lnpg_off = take("lnpg", -1, (size_t)LN_BLOCKS * P.ldcs * 4); P.lnpb_off = take("lnpb", -1, (size_t)LN_BLOCKS * P.ldcs * 4); }
   P.last_blocks = (int)((N + 15) / 16);
   if (P.last_blocks > LAST_BLOCKS_MAX) P.last_blocks = LAST_BLOCKS_MAX;
   if (P.last_blocks < 1) P.last_blocks = 1;
@@ -380,18 +410,18 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
   // unbounded): sized for the larger.  (Rounds 1-3 sized them by last_blocks alone: batches of more than 65536 points -- the shipped
   // 10 x 16000 -- let the fused head write its partials past these buffers, into part2 / partdb / partloss and the dP_0 buffer.)
   const size_t part_rows = (size_t)std::max<int64_t>(P.last_blocks, (N + frows - 1) / frows);
-  P.part_off = take(part_rows * P.ld_part * 4);
-  P.part2_off = take((size_t)LAST_GROUPS * P.ld_part * 4);
-  P.partdb_off = take(part_rows * 4);
-  P.partloss_off = take(part_rows * 4);
-  P.segpart_off = take((size_t)LAT_SLICES_MAX * (R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // (up to 8 partial copies)
-  P.segnorm_off = take((size_t)(R > 0 ? R : 1) * 4);
-  P.gnorm_off = take(1024 * 4);
+  P.part_off = take("part", -1, part_rows * P.ld_part * 4);
+  P.part2_off = take("part2", -1, (size_t)LAST_GROUPS * P.ld_part * 4);
+  P.partdb_off = take("partdb", -1, part_rows * 4);
+  P.partloss_off = take("partloss", -1, part_rows * 4);
+  P.segpart_off = take("segpart", -1, (size_t)LAT_SLICES_MAX * (R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // (up to 8 partial copies)
+  P.segnorm_off = take("segnorm", -1, (size_t)(R > 0 ? R : 1) * 4);
+  P.gnorm_off = take("gnorm", -1, 1024 * 4);
   P.nwg = (int)((N + frows - 1) / frows);
   for (int l = 0; l < P.nl - 1; ++l) {
-    P.dpl_off[l] = take((size_t)N * maxw * 4 + 4096);
-    P.mask_off[l] = take((size_t)P.nwg * 256 * 16);
-    P.cs_off[l] = take((size_t)P.nwg * P.ldcs * 4);
+    P.dpl_off[l] = take("dpl", l, (size_t)N * maxw * 4 + 4096);
+    P.mask_off[l] = take("mask", l, (size_t)P.nwg * 256 * 16);
+    P.cs_off[l] = take("cs", l, (size_t)P.nwg * P.ldcs * 4);
   }
   P.dw = dw_schedule(n, N, P.ld_in, segmode);
   P.dw_nb = nb < 2 ? 2 : (nb > DSDF_MAX_BUCKETS ? DSDF_MAX_BUCKETS : nb);
@@ -405,19 +435,20 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
     int ns = P.dw.nsplit[l];
     for (int t = 0; t < P.dw_nb; ++t)
       if (P.dwph[t].nsplit[l] > ns) ns = P.dwph[t].nsplit[l];
-    P.dwslab_off[l] = take((size_t)ns * P.dw.slab[l] * 4);
+    P.dwslab_off[l] = take("dwslab", l, (size_t)ns * P.dw.slab[l] * 4);
   }
   P.segmode = segmode ? 1 : 0;
   if (segmode) {
     P.ldu = P.ldcs;
-    P.hoistU_off = take((size_t)(R > 0 ? R : 1) * 2 * P.ldu * 4);
-    for (int t = 0; t < 2; ++t) P.xsum_off[t] = take((size_t)P.nwg * 4 * P.ldcs * 4);
+    P.hoistU_off = take("hoistU", -1, (size_t)(R > 0 ? R : 1) * 2 * P.ldu * 4);
+    for (int t = 0; t < 2; ++t) P.xsum_off[t] = take("xsum", t, (size_t)P.nwg * 4 * P.ldcs * 4);
     P.ldh = (int)rup(n->latent_size + n->geom_dim, 4);
     P.hstride = (long long)P.ldcs * P.ldh;
-    P.hs_off = take((size_t)2 * P.hstride * 4);
-    P.zr_off = take((size_t)(R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // renormed latent row of every segment
+    P.hs_off = take("hs", -1, (size_t)2 * P.hstride * 4);
+    P.zr_off = take("zr", -1, (size_t)(R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // renormed latent row of every segment
   }
   P.total = o;
+  if (rec) rec->total = o;
   return P;
 }
 
@@ -606,6 +637,10 @@ int pick_frows(const DsdfNet* net, int64_t n, bool merged = false) {
 struct HoistRenorm { float max_norm; float* dlat; long long nzero; };
 int run_hoist(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* table, const DsdfBatch* b,
               FusedSeg* seg, hipStream_t st, const HoistRenorm* renorm = nullptr) {
+  // (seg_hoist_kernel clamps its loads to column latent_size - 1: there must be one.  Both callers exclude the case before they
+  // get here -- the segment-mode condition and decode_latent_ok -- so this is the guard of a third one)
+  if (net->latent_size < 1 || net->latent_size > HOIST_MAXL)
+    return fail(DSDF_E_INVALID, "segment mode needs 1 <= latent_size <= %d (got %d)", HOIST_MAXL, net->latent_size);
   const Packed pk = packed_layout(net);
   const int ks = skip_layer(net);
   HoistArgs h;
@@ -1290,7 +1325,7 @@ int dsdf_decode(const DsdfNet* net, const float* packed, const float* params, co
   TRY(check_common(net, packed, params, ws));
   if (n == 0) return 0;
   if (!input || !sdf_out || n < 0 || ld_in < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in");
-  const Plan P = make_plan(net, n, 0, true, false, 2, pick_frows(net, n));
+  const Plan P = make_plan(net, n, 0, true, false, 2, pick_frows(net, n), &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   TRY(run_gather(net, P, ws, nullptr, nullptr, input, ld_in, n, st));
@@ -1311,6 +1346,26 @@ int dsdf_decode(const DsdfNet* net, const float* packed, const float* params, co
   return launch_last<LAST_FWD>(a, blocks, st);
 }
 
+// dsdf_decode_latent's own layout: the one-row "scene table" index and U [1][2][FMAXW] behind it.  The caller's buffer is still
+// sized like dsdf_decode's (at least 16384 bytes); none of that plan's regions is touched.
+static Plan decode_latent_plan(const DsdfNet* net, int64_t n, size_t* scene_off, size_t* need, WsTable* rec) {
+  Plan P = make_plan(net, n, 0, true, false, 2, pick_frows(net, n));
+  const size_t guard = g_redzone.load(std::memory_order_relaxed);
+  size_t o = 0;
+  if (rec) rec->reset();
+  auto take = [&](const char* name, size_t bytes) {
+    const size_t r = o;
+    o += (size_t)rup((int64_t)bytes, 256) + guard;
+    if (rec) rec->add(name, -1, r, bytes);
+    return r;
+  };
+  *scene_off = take("dl_scene", 8);                                             // seg_scene[0] = 0: the "table" is the single latent row
+  P.hoistU_off = take("dl_hoistU", (size_t)2 * FMAXW * 4); P.ldu = FMAXW;      // U [1][2][512] behind it
+  *need = std::max(std::max<size_t>(P.total, 16384), o);
+  if (rec) rec->total = *need;
+  return P;
+}
+
 static bool decode_latent_ok(const DsdfNet* net) {
   return fused_enabled() && fused_eligible(net) && net->geom_dim <= FGEO && net->latent_size <= HOIST_MAXL &&
          net->latent_size >= 1 && net->n_layers >= 3 && !last_layer_skip(net);
@@ -1328,20 +1383,62 @@ int dsdf_decode_latent(const DsdfNet* net, const float* packed, const float* par
   if (!latent || !xyz || !sdf_out || n < 0) return fail(DSDF_E_INVALID, "bad latent/xyz/sdf_out");
   if (!decode_latent_ok(net))
     return fail(DSDF_E_INVALID, "dsdf_decode_latent needs the fused forward (widths <= 512, geom_dim <= 4): use dsdf_decode");
-  Plan P = make_plan(net, n, 0, true, false, 2, pick_frows(net, n));
-  const size_t need = P.total > 16384 ? P.total : 16384;
+  size_t scene_off = 0, need = 0;
+  const Plan P = decode_latent_plan(net, n, &scene_off, &need, &t_last_plan);
   if (ws_bytes < need) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   // ONE segment covering every point: the segment-mode forward with the latent's products hoisted (fused.hpp FusedSeg)
-  HIP_OK(hipMemsetAsync(ws, 0, 8, st));                 // seg_scene[0] = 0: the "table" is the single latent row
-  P.hoistU_off = 256; P.ldu = FMAXW;                    // U [1][2][512] behind it
+  HIP_OK(hipMemsetAsync(at<char>(ws, scene_off), 0, 8, st));
   DsdfBatch b;
   memset(&b, 0, sizeof(b));
-  b.seg_scene = at<int64_t>(ws, 0); b.n_segments = 1; b.xyz = xyz; b.n_points = n; b.seg_len = n;
+  b.seg_scene = at<int64_t>(ws, scene_off); b.n_segments = 1; b.xyz = xyz; b.n_points = n; b.seg_len = n;
   FusedSeg seg;
   TRY(run_hoist(net, P, ws, packed, latent, &b, &seg, st));
   seg.wg_per_seg = (int)((n + P.frows - 1) / P.frows);  // every workgroup belongs to segment 0
   return run_fused_forward(net, P, ws, packed, params, n, 0, nullptr, 0, false, sdf_out, nullptr, st, &seg);
+}
+
+// ---- debug only: red zones and the region table of the workspace planners (include/dsdf.h) ----------------
+int dsdf_debug_ws_redzone(int32_t bytes) {
+  if (bytes < 0 || bytes > DSDF_WS_MAX_REDZONE || (bytes & 255))
+    return fail(DSDF_E_INVALID, "red zone of %d bytes: must be 0 or a multiple of 256, at most %d", bytes, DSDF_WS_MAX_REDZONE);
+  g_redzone.store((size_t)bytes, std::memory_order_relaxed);
+  return 0;
+}
+
+int dsdf_debug_ws_regions(DsdfWsRegion* table, int32_t capacity, int32_t* n_regions, size_t* total) {
+  const WsTable& T = t_last_plan;
+  if (!n_regions) return fail(DSDF_E_INVALID, "n_regions is NULL");
+  *n_regions = T.n;
+  if (total) *total = T.total;
+  if (T.dropped) return fail(DSDF_E_INVALID, "the last plan has %d regions more than DSDF_WS_MAX_REGIONS", T.dropped);
+  if (!table) return 0;                      // count / total only
+  if (capacity < T.n) return fail(DSDF_E_INVALID, "table of %d rows, the last plan has %d regions", capacity, T.n);
+  for (int i = 0; i < T.n; ++i) {
+    memset(&table[i], 0, sizeof(table[i]));
+    if (T.row[i].idx >= 0) snprintf(table[i].name, sizeof(table[i].name), "%s%d", T.row[i].name, T.row[i].idx);
+    else snprintf(table[i].name, sizeof(table[i].name), "%s", T.row[i].name);
+    table[i].offset = T.row[i].off; table[i].bytes = T.row[i].bytes;
+  }
+  return 0;
+}
+
+int dsdf_debug_ws_plan(const DsdfNet* net, int64_t n_points, int64_t n_segments, int32_t kind, int32_t segmode, int32_t n_buckets,
+                       int32_t frows) {
+  TRY(validate(net));
+  if (n_points < 0 || n_points > (1ll << 30) || n_segments < 0) return fail(DSDF_E_INVALID, "bad arguments");
+  if (frows != 32 && frows != FROWS) return fail(DSDF_E_INVALID, "frows %d: the fused kernels take 32 or %d rows", frows, FROWS);
+  if (n_buckets < 0 || n_buckets > DSDF_MAX_BUCKETS) return fail(DSDF_E_INVALID, "n_buckets %d out of range [0, %d]", n_buckets, DSDF_MAX_BUCKETS);
+  switch (kind) {
+    case DSDF_WS_PLAN_TRAIN: make_plan(net, n_points, n_segments, false, segmode != 0, n_buckets, frows, &t_last_plan); return 0;
+    case DSDF_WS_PLAN_DECODE: make_plan(net, n_points, 0, true, false, 2, frows, &t_last_plan); return 0;
+    case DSDF_WS_PLAN_DECODE_LATENT: {
+      size_t scene_off = 0, need = 0;
+      decode_latent_plan(net, n_points, &scene_off, &need, &t_last_plan);
+      return 0;
+    }
+    default: return fail(DSDF_E_INVALID, "plan kind %d", kind);
+  }
 }
 
 int dsdf_module_forward(const DsdfNet* net, const float* packed, const float* params, const float* input,
@@ -1351,7 +1448,7 @@ int dsdf_module_forward(const DsdfNet* net, const float* packed, const float* pa
   if (n == 0) return 0;
   if (!input || !sdf_out || n < 0 || ld_in < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in");
   if (training && net->dropout_p > 0.f && net->dropout_mask && !dropout_key) return fail(DSDF_E_INVALID, "dropout_key is NULL");
-  const Plan P = make_plan(net, n, 0, false);
+  const Plan P = make_plan(net, n, 0, false, false, 2, FROWS, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   TRY(run_gather(net, P, ws, nullptr, nullptr, input, ld_in, n, st, training, dropout_key, 0));
@@ -1379,7 +1476,7 @@ int dsdf_module_backward(const DsdfNet* net, const float* packed, const float* p
   if (d_input && ld_din < net->in_dim[0]) return fail(DSDF_E_INVALID, "ld_din too small");
   if (training && net->latent_dropout && d_input && !dropout_key)
     return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key for d/d(input))");
-  const Plan P = make_plan(net, n, 0, false);
+  const Plan P = make_plan(net, n, 0, false, false, 2, FROWS, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   DsdfParamLayout L;
@@ -1452,7 +1549,7 @@ int dsdf_module_jvp(const DsdfNet* net, const float* packed, const float* params
   if (!tangent || !jvp_out || n < 0 || ld_t < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad tangent/jvp_out/ld_t");
   const bool lat_drop = net->latent_dropout && training && net->latent_size > 0;
   if (lat_drop && !dropout_key) return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key)");
-  const Plan P = make_plan(net, n, 0, false);
+  const Plan P = make_plan(net, n, 0, false, false, 2, FROWS, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   DsdfParamLayout L;
@@ -1558,13 +1655,13 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
   const bool segsum = fusedb && b->seg_len > 0 && b->seg_len % frows == 0 && b->seg_len * R == n && net->n_layers > 2 &&
                       skip_l != net->n_layers - 2 &&   // the deepest hidden layer's dP column sums live in the head's partials
                       !last_layer_skip(net) &&
-                      net->geom_dim <= FGEO && net->latent_size <= HOIST_MAXL;   // (config 5 too: bf16 rounding is element-wise
+                      net->geom_dim <= FGEO && net->latent_size >= 1 && net->latent_size <= HOIST_MAXL;   // (config 5 too: bf16 rounding is element-wise
                                                                                   // on the operands, so the latent products still hoist)
   const int phase = cfg->dw_phase, nbk = cfg->dw_buckets;
   if (nbk < 0 || nbk > DSDF_MAX_BUCKETS) return fail(DSDF_E_INVALID, "dw_buckets %d out of range [0, %d]", nbk, DSDF_MAX_BUCKETS);
   if (phase < 0 || (nbk <= 1 ? phase != 0 : phase < 1 || phase > nbk))
     return fail(DSDF_E_INVALID, "dw_phase %d out of range for dw_buckets %d (0 without buckets, 1..K with K >= 2)", phase, nbk);
-  const Plan P = make_plan(net, n, R, false, segsum, nbk, frows);
+  const Plan P = make_plan(net, n, R, false, segsum, nbk, frows, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   const int Lc = net->latent_size;
@@ -1691,7 +1788,10 @@ int dsdf_grad_norm(const float* grads, int64_t n, float max_norm, float* norm_ou
   if (!grads || !norm_out || !coef_out || !ws || n <= 0) return fail(DSDF_E_INVALID, "bad arguments");
   int blocks = (int)((n + 4095) / 4096);
   if (blocks > 1024) blocks = 1024;
-  if (ws_bytes < (size_t)blocks * 4) return fail(DSDF_E_WORKSPACE, "workspace too small");
+  t_last_plan.reset();
+  t_last_plan.add("gn_partials", -1, 0, (size_t)blocks * 4);
+  t_last_plan.total = (size_t)blocks * 4 + g_redzone.load(std::memory_order_relaxed);
+  if (ws_bytes < t_last_plan.total) return fail(DSDF_E_WORKSPACE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(blocks), dim3(256), 0, st, grads, (long long)n, (float*)ws);
   LAUNCH_OK("sumsq_partial_kernel");
@@ -1887,8 +1987,13 @@ int dsdf_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float
   memset(&f, 0, sizeof(f));
   if (N > 2048 || ldc != N) return fail(DSDF_E_INVALID, "gemm_tn test entry needs ldc == N <= 2048");
   f.slabs = t.C; f.nsplit = nsplit; f.slab = slab; f.ldc = (int)ldc; f.colsum = nullptr; f.npart = 0; f.ldcs = 0;
-  f.dv = C; f.db = (float*)ws + (size_t)nsplit * slab;  // scratch row of M floats behind the slabs
-  if (ws_bytes < ((size_t)nsplit * slab + M) * 4) return fail(DSDF_E_WORKSPACE, "gemm_tn workspace too small");
+  const size_t guard = g_redzone.load(std::memory_order_relaxed), db_off = (size_t)nsplit * slab * 4 + guard;
+  t_last_plan.reset();
+  t_last_plan.add("tn_slabs", -1, 0, (size_t)nsplit * slab * 4);
+  t_last_plan.add("tn_db", -1, db_off, (size_t)M * 4);
+  t_last_plan.total = db_off + (size_t)M * 4 + guard;
+  f.dv = C; f.db = at<float>(ws, db_off);               // scratch row of M floats behind the slabs
+  if (ws_bytes < t_last_plan.total) return fail(DSDF_E_WORKSPACE, "gemm_tn workspace too small");
   f.out = (int)M; f.in = (int)N;
   hipLaunchKernelGGL(finalize_layer_kernel, dim3((unsigned)M), dim3(256), 0, st, f);
   LAUNCH_OK("finalize_layer_kernel(test)");
@@ -1913,27 +2018,35 @@ struct McPlan {
   size_t mask, cas, vbase, bv, bf, ov, of, total;
 };
 
-int mc_plan(int32_t nx, int32_t ny, int32_t nz, McPlan* P) {
+int mc_plan(int32_t nx, int32_t ny, int32_t nz, McPlan* P, WsTable* rec = nullptr) {
   if (nx < 2 || ny < 2 || nz < 2 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
     return fail(DSDF_E_INVALID, "marching cubes: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
   P->npts = (int64_t)nx * ny * nz;
   P->nblocks = (P->npts + MC_BLOCK - 1) / MC_BLOCK;
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (size_t)rup((int64_t)(o + bytes), 256); return at; };
-  P->mask = take((size_t)P->npts);
-  P->cas = take((size_t)P->npts);
-  P->vbase = take((size_t)P->npts * 4);
-  P->bv = take((size_t)P->nblocks * 4);
-  P->bf = take((size_t)P->nblocks * 4);
-  P->ov = take((size_t)(P->nblocks + 1) * 8);
-  P->of = take((size_t)(P->nblocks + 1) * 8);
+  const size_t guard = g_redzone.load(std::memory_order_relaxed);
+  if (rec) rec->reset();
+  auto take = [&](const char* name, size_t bytes) {
+    const size_t at = o;
+    o = (size_t)rup((int64_t)(o + bytes), 256) + guard;
+    if (rec) rec->add(name, -1, at, bytes);
+    return at;
+  };
+  P->mask = take("mc_mask", (size_t)P->npts);
+  P->cas = take("mc_cas", (size_t)P->npts);
+  P->vbase = take("mc_vbase", (size_t)P->npts * 4);
+  P->bv = take("mc_bv", (size_t)P->nblocks * 4);
+  P->bf = take("mc_bf", (size_t)P->nblocks * 4);
+  P->ov = take("mc_ov", (size_t)(P->nblocks + 1) * 8);
+  P->of = take("mc_of", (size_t)(P->nblocks + 1) * 8);
   P->total = o;
+  if (rec) rec->total = o;
   return 0;
 }
 
 int mc_setup(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, void* ws, size_t ws_bytes, McGrid* g,
              McWs* w, McPlan* P) {
-  TRY(mc_plan(nx, ny, nz, P));
+  TRY(mc_plan(nx, ny, nz, P, &t_last_plan));
   if (!sdf || !ws) return fail(DSDF_E_INVALID, "marching cubes: NULL sdf or workspace");
   if (ws_bytes < P->total) return fail(DSDF_E_WORKSPACE, "marching cubes: workspace %zu < %zu bytes", ws_bytes, P->total);
   g->sdf = sdf; g->nx = nx; g->ny = ny; g->nz = nz; g->level = level; g->npts = P->npts;
@@ -1947,7 +2060,7 @@ int mc_setup(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, 
 
 int dsdf_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes) {
   McPlan P;
-  TRY(mc_plan(nx, ny, nz, &P));
+  TRY(mc_plan(nx, ny, nz, &P, &t_last_plan));
   if (!bytes) return fail(DSDF_E_INVALID, "NULL bytes");
   *bytes = P.total;
   return 0;
@@ -2005,7 +2118,7 @@ struct MsdfPlan {
   size_t tri, ws;
 };
 
-int msdf_plan(int64_t nf, int64_t nq, MsdfPlan* P) {
+int msdf_plan(int64_t nf, int64_t nq, MsdfPlan* P, WsTable* rec = nullptr) {
   if (nf <= 0) return fail(DSDF_E_INVALID, "mesh sdf: %lld faces (need at least one)", (long long)nf);
   if (nq < 0) return fail(DSDF_E_INVALID, "mesh sdf: %lld queries", (long long)nq);
   if (nf > INT32_MAX || nq > INT32_MAX)
@@ -2021,14 +2134,16 @@ int msdf_plan(int64_t nf, int64_t nq, MsdfPlan* P) {
   P->n_splits = (int32_t)ns;
   P->chunk = (int32_t)((nf + ns - 1) / ns);
   P->tri = (size_t)nf * sizeof(MsdfTri);
-  P->ws = (size_t)ns * (size_t)nq * 12;          // d2, face, winding per (split, query)
+  const size_t part = (size_t)ns * (size_t)nq * 12;          // d2, face, winding per (split, query): one block
+  P->ws = part + g_redzone.load(std::memory_order_relaxed);
+  if (rec) { rec->reset(); rec->add("msdf_partials", -1, 0, part); rec->total = P->ws; }
   return 0;
 }
 }  // namespace
 
 int dsdf_msdf_plan(int64_t n_faces, int64_t n_queries, size_t* tri_bytes, size_t* ws_bytes, int32_t* n_splits) {
   MsdfPlan P;
-  TRY(msdf_plan(n_faces, n_queries, &P));
+  TRY(msdf_plan(n_faces, n_queries, &P, &t_last_plan));
   if (!tri_bytes && !ws_bytes && !n_splits) return fail(DSDF_E_INVALID, "mesh sdf plan: every output is NULL");
   if (tri_bytes) *tri_bytes = P.tri;
   if (ws_bytes) *ws_bytes = P.ws;
@@ -2055,7 +2170,7 @@ int dsdf_msdf_prepare(const float* verts, int64_t n_verts, const int32_t* faces,
 int dsdf_msdf_query(const void* tri, int64_t n_faces, const float* queries, int64_t n_queries, float* sdf, float* sqr_dist,
                     int32_t* face, float* closest, float* winding, int32_t flip_sign, void* ws, size_t ws_bytes, void* stream) {
   MsdfPlan P;
-  TRY(msdf_plan(n_faces, n_queries, &P));
+  TRY(msdf_plan(n_faces, n_queries, &P, &t_last_plan));
   if (!sdf && !sqr_dist && !face && !closest && !winding) return fail(DSDF_E_INVALID, "mesh sdf query: every output is NULL");
   if (n_queries == 0) return 0;
   if (!tri || !queries) return fail(DSDF_E_INVALID, "mesh sdf query: NULL record buffer or queries");

@@ -39,6 +39,15 @@ def reconstruct(engine: Engine, samples_xyz, samples_sdf, *, num_iterations=800,
     import math
     import os
     B, S, G = samples_xyz.shape
+    if resample is not None:
+        # argument errors first, before anything touches the device: the sampler writes 2 * (S // 2) rows per shape (half positive,
+        # half negative), so with an odd S its rows would shift against seg_len = S and the last B rows would never be written
+        if not isinstance(resample, (tuple, list)) or len(resample) < 2:
+            raise ValueError("reconstruct: `resample` must be (DeviceSampleCache, scene_ids[, generator])")
+        if S % 2 != 0:
+            raise ValueError(f"reconstruct: `resample` draws S / 2 positive and S / 2 negative samples per shape: S must be even, got {S}")
+        if callback is not None:
+            raise ValueError("reconstruct: `resample` and `callback` are two ways of feeding an iteration; give one")
     L = engine.spec.latent_size
     dev = engine.device
     z = (torch.randn(B, L, generator=generator) * init_std).to(dev) if z0 is None else z0.to(dev, torch.float32).clone()
@@ -59,8 +68,6 @@ def reconstruct(engine: Engine, samples_xyz, samples_sdf, *, num_iterations=800,
 
     draw = None
     if resample is not None:
-        if callback is not None:
-            raise ValueError("reconstruct: `resample` and `callback` are two ways of feeding an iteration; give one")
         cache, ids = resample[0], resample[1]
         draw = cache.sample_sequence(ids, S, num_iterations, counter, xyz, sdf, generator=resample[2] if len(resample) > 2 else None)
 

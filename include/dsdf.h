@@ -27,7 +27,7 @@ extern "C" {
 #endif
 
 #define DSDF_MAX_LAYERS 16
-#define DSDF_ABI_VERSION 18
+#define DSDF_ABI_VERSION 19
 #define DSDF_MAX_BUCKETS 8
 
 enum {
@@ -135,6 +135,42 @@ int dsdf_decode_workspace_bytes(const DsdfNet* net, int64_t n_points, size_t* by
  * bucket's weight-gradient launch are finer than the whole launch's.  dsdf_workspace_bytes covers n_buckets <= 2. */
 int dsdf_workspace_bytes_buckets(const DsdfNet* net, int64_t n_points, int64_t n_segments, int32_t n_buckets, size_t* bytes);
 
+/* ---- debug only: red zones and the region table of the workspace planners -------------------------------
+ * Every entry point that takes `void* ws` cuts that one allocation into adjacent regions (layer inputs, dP buffers, masks,
+ * column sums, split-K slabs, head partials, ...), each rounded up to 256 bytes.  These two entries let a TEST see a write that
+ * leaves its region: it asks for red zones, fills the whole workspace with one byte value, runs a call, reads the layout the
+ * call used and compares every byte outside the regions (red zones, rounding padding, the tail) with the fill value.  No
+ * kernel takes part; production callers never call either entry.
+ *
+ * dsdf_debug_ws_redzone  [host] process-wide: every region of every planner (training / module, decode, decode_latent,
+ *   marching cubes, mesh SDF, gemm_tn, grad_norm) is followed by `bytes` unused bytes.  0 (the default) or a multiple of
+ *   256, at most DSDF_WS_MAX_REDZONE; anything else is DSDF_E_INVALID and changes nothing.  Every *_workspace_bytes /
+ *   dsdf_msdf_plan answer and every entry point's size check include the red zones.  With 0 every offset and every total is
+ *   exactly what it is without this mechanism.  Set it while no call is in flight, and size the workspace AFTER setting it.
+ * dsdf_debug_ws_regions  [host] the layout of the LAST plan laid out on the calling thread: by a launching entry point (each
+ *   records the plan it launched with), by dsdf_mc_workspace_bytes / dsdf_msdf_plan, or by dsdf_debug_ws_plan.  One row per
+ *   region in layout order: `bytes` is the exact, unrounded size the planner asked for (deliberate over-read slack is part of
+ *   the region that owns it); buffers that alias on purpose (inference ping-pong, the shared LayerNorm scratch) appear once.
+ *   *n_regions and *total (the plan's size, red zones included; may be NULL) are always written.  table == NULL: only those
+ *   two.  capacity < *n_regions: DSDF_E_INVALID, nothing written to table.  DSDF_WS_MAX_REGIONS rows always suffice.
+ * dsdf_debug_ws_plan     [host] lays out the plan a launch WOULD use, without a launch or a device, and makes it the calling
+ *   thread's last plan: kind DSDF_WS_PLAN_TRAIN (training step and the module path: n_segments, segmode, n_buckets, frows as
+ *   the step chooses them -- dsdf_workspace_bytes answers the largest of these over segmode 0 / 1 and frows 32 / 64),
+ *   DSDF_WS_PLAN_DECODE (dsdf_decode) or DSDF_WS_PLAN_DECODE_LATENT (dsdf_decode_latent); the latter two ignore n_segments,
+ *   segmode and n_buckets.  frows is 32 or 64. */
+#define DSDF_WS_MAX_REGIONS 192
+#define DSDF_WS_MAX_REDZONE 4096
+enum { DSDF_WS_PLAN_TRAIN = 0, DSDF_WS_PLAN_DECODE = 1, DSDF_WS_PLAN_DECODE_LATENT = 2 };
+typedef struct DsdfWsRegion {
+  char name[24];                    /* NUL-terminated: "in3", "part", "dwslab5", "mc_vbase", ... */
+  uint64_t offset;                  /* bytes from the workspace pointer; a multiple of 256 */
+  uint64_t bytes;                   /* exact size asked for (not rounded, red zone not included) */
+} DsdfWsRegion;
+int dsdf_debug_ws_redzone(int32_t bytes);
+int dsdf_debug_ws_regions(DsdfWsRegion* table, int32_t capacity, int32_t* n_regions, size_t* total);
+int dsdf_debug_ws_plan(const DsdfNet* net, int64_t n_points, int64_t n_segments, int32_t kind, int32_t segmode, int32_t n_buckets,
+                       int32_t frows);
+
 /* [host] 1 if this net's training step can run its backward in phases (the fused kernels take it; in this process: the
  * DSDF_NO_FUSED switch counts), 0 if not (a caller then exchanges the gradient in ONE piece), < 0 for an invalid net. */
 int dsdf_dw_phase_supported(const DsdfNet* net);
@@ -202,7 +238,8 @@ int dsdf_train_forward_backward(const DsdfNet* net, const float* packed, const f
                                 float* sdf_out, int32_t accumulate, void* ws, size_t ws_bytes, void* stream);
 
 /* clip_grad_norm_ over the decoder arena (train_deep_sdf.py:541-543): writes total norm and the clip
- * coefficient min(1, max_norm/(norm+1e-6)) to two device floats. */
+ * coefficient min(1, max_norm/(norm+1e-6)) to two device floats.  ws: one float per block of 4096 gradients, at most 1024
+ * of them (4096 bytes always suffice; + one debug red zone when dsdf_debug_ws_redzone is set). */
 int dsdf_grad_norm(const float* grads, int64_t n, float max_norm, float* norm_out, float* coef_out,
                    void* ws, size_t ws_bytes, void* stream);
 
@@ -373,7 +410,9 @@ int dsdf_ms_caps(const DsdfMsGrid* grid, int64_t start, int64_t end, const DsdfM
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */
 int dsdf_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
                  int64_t N, int64_t K, const float* bias, void* stream);
-/* C[M,N] = A[K,M]^T * B[K,N]  (split-K inside; ws holds the partial slabs) */
+/* C[M,N] = A[K,M]^T * B[K,N]  (split-K inside; ws holds the partial slabs).  ldc == N <= 2048.  ws: nsplit slabs of
+ * rup(M * ldc, 64) floats, nsplit = ceil(K / kchunk), kchunk = rup(ceil(K / min(32, ceil(K / 256))), 32), and M floats behind
+ * them (+ one debug red zone behind each of the two when dsdf_debug_ws_redzone is set). */
 int dsdf_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
                  int64_t N, int64_t K, void* ws, size_t ws_bytes, void* stream);
 /* keep-mask of the dropout hash as 0/1 bytes [rows, cols] (spec: oracle/deepsdf_oracle.py dropout_keep) */

@@ -284,3 +284,207 @@ def test_bf16x8_kloop_never_reloads_the_sources_of_the_mfma_in_front():
         pytest.skip("ROCm LLVM tools or the built library are not available")
     worst, pairs = asmcheck.check_mfma_src_reuse(LIB, min_distance=2)
     assert worst is not None and worst >= 2 and pairs > 20
+
+
+# ---- workspace planners: red zones and the region table (dsdf_debug_ws_*; host code, no device) ------------------------------------
+def _net_from_golden(kw):
+    from deepsdf_amd.net import NetSpec
+    return NetSpec(**kw).c_struct()
+
+
+def _plan_table(lib, net, N, R, kind, seg, K, fr):
+    from deepsdf_amd import _lib
+    assert lib.dsdf_debug_ws_plan(C.byref(net), N, R, kind, seg, K, fr) == 0, lib.dsdf_last_error()
+    return _lib.ws_regions()
+
+
+@pytest.fixture()
+def redzone(lib):
+    """Sets a red zone for one test and ALWAYS puts 0 back (the setting is process-wide)."""
+    def set_(g):
+        assert lib.dsdf_debug_ws_redzone(g) == 0, lib.dsdf_last_error()
+    yield set_
+    assert lib.dsdf_debug_ws_redzone(0) == 0
+
+
+def test_default_layout_equals_the_recorded_totals(lib, golden_dir):
+    """Red zone 0: every size answer equals what the commit before the debug red zones answered (tests/golden/ws_totals.json,
+    recorded by tests/golden/make_golden_ws_totals.py): the default layout did not move by a byte."""
+    import json
+    gold = json.load(open(os.path.join(golden_dir, "ws_totals.json")))
+    assert lib.dsdf_debug_ws_redzone(0) == 0
+    assert len(gold["cases"]) >= 150 and len(gold["mc"]) >= 5 and len(gold["msdf"]) >= 9
+    nets = {name: _net_from_golden(kw) for name, kw in gold["nets"].items()}
+    b, tri, ns = C.c_size_t(), C.c_size_t(), C.c_int32()
+    for c in gold["cases"]:
+        net = nets[c["net"]]
+        assert lib.dsdf_workspace_bytes(C.byref(net), c["N"], c["R"], C.byref(b)) == 0 and b.value == c["train"], c
+        assert lib.dsdf_workspace_bytes_buckets(C.byref(net), c["N"], c["R"], c["K"], C.byref(b)) == 0 and b.value == c["buckets"], c
+        assert lib.dsdf_decode_workspace_bytes(C.byref(net), c["N"], C.byref(b)) == 0 and b.value == c["decode"], c
+    for m in gold["mc"]:
+        assert lib.dsdf_mc_workspace_bytes(*m["grid"], C.byref(b)) == 0 and b.value == m["bytes"], m
+    for m in gold["msdf"]:
+        assert lib.dsdf_msdf_plan(m["faces"], m["queries"], C.byref(tri), C.byref(b), C.byref(ns)) == 0
+        assert (tri.value, b.value, ns.value) == (m["tri"], m["ws"], m["splits"]), m
+
+
+def test_red_zones_add_one_guard_per_region_and_the_size_answers_cover_every_plan(lib, golden_dir, redzone):
+    """Per plan: total(G) = total(0) + G x regions, offsets move by G x (regions in front).  dsdf_workspace_bytes / _buckets answer
+    a maximum over the plans a launch can choose (segment mode on / off, 32- / 64-row workgroups): at least every one of them,
+    with and without red zones -- that inequality is the contract the entry points' size checks rely on."""
+    import json
+    from deepsdf_amd import _lib
+    gold = json.load(open(os.path.join(golden_dir, "ws_totals.json")))
+    nets = {name: _net_from_golden(kw) for name, kw in gold["nets"].items()}
+    b = C.c_size_t()
+    for c in gold["cases"]:
+        net, N, R, K = nets[c["net"]], c["N"], c["R"], c["K"]
+        plans = [(_lib.WS_PLAN_TRAIN, seg, k, fr) for seg in (0, 1) for fr in (32, 64) for k in (2, K)]
+        plans += [(_lib.WS_PLAN_DECODE, 0, 2, fr) for fr in (32, 64)] + [(_lib.WS_PLAN_DECODE_LATENT, 0, 2, 64)]
+        base = {}
+        for G in (0, 256, 1024):
+            redzone(G)
+            answers = {}
+            for k in (2, K):
+                assert lib.dsdf_workspace_bytes_buckets(C.byref(net), N, R, k, C.byref(b)) == 0
+                answers[k] = b.value
+            assert lib.dsdf_workspace_bytes(C.byref(net), N, R, C.byref(b)) == 0 and b.value == answers[2]
+            assert lib.dsdf_decode_workspace_bytes(C.byref(net), N, C.byref(b)) == 0
+            dec = b.value
+            for p in plans:
+                kind, seg, k, fr = p
+                rows, total = _plan_table(lib, net, N, R, kind, seg, k, fr)
+                if G == 0:
+                    base[p] = (rows, total)
+                    continue
+                rows0, total0 = base[p]
+                assert [(n, nb) for n, _, nb in rows] == [(n, nb) for n, _, nb in rows0], (c, p)
+                assert [o for _, o, _ in rows] == [o + G * i for i, (_, o, _) in enumerate(rows0)], (c, p, G)
+                if kind == _lib.WS_PLAN_DECODE_LATENT:      # (sized like dsdf_decode's buffer, with a floor of 16384 bytes)
+                    own = rows[-1][1] + rows[-1][2] + G
+                    assert len(rows) == 2 and total == max(_plan_table(lib, net, N, R, _lib.WS_PLAN_DECODE, 0, 2, fr)[1], 16384, own), (c, p, G)
+                else:
+                    assert total == total0 + G * len(rows), (c, p, G, total, total0, len(rows))
+            for p in plans:                                   # the inequality, at this G (0 included)
+                kind, seg, k, fr = p
+                _, total = _plan_table(lib, net, N, R, kind, seg, k, fr)
+                if kind == _lib.WS_PLAN_TRAIN:
+                    assert answers[k] >= total, (c, p, G)
+                elif kind == _lib.WS_PLAN_DECODE:
+                    assert dec >= total, (c, p, G)
+                else:
+                    assert lib.dsdf_decode_workspace_bytes(C.byref(net), max(N, 64), C.byref(b)) == 0
+                    assert max(b.value, 16384) >= total, (c, p, G)
+            if G == 0:                                        # and the maximum is attained: the answer is not padded beyond its plans
+                assert answers[2] == max(t for (kind, _, k, _), (_, t) in base.items() if kind == _lib.WS_PLAN_TRAIN and k == 2)
+    for m in gold["mc"]:
+        tot = {}
+        for G in (0, 256):
+            redzone(G)
+            assert lib.dsdf_mc_workspace_bytes(*m["grid"], C.byref(b)) == 0
+            rows, tot[G] = _lib.ws_regions()
+            assert tot[G] == b.value and len(rows) == 7
+        assert tot[256] == tot[0] + 256 * 7
+    for m in gold["msdf"]:
+        tot = {}
+        for G in (0, 512):
+            redzone(G)
+            assert lib.dsdf_msdf_plan(m["faces"], m["queries"], None, C.byref(b), None) == 0
+            rows, tot[G] = _lib.ws_regions()
+            assert tot[G] == b.value and [r[0] for r in rows] == ["msdf_partials"] and rows[0][2] == m["ws"]
+        assert tot[512] == tot[0] + 512
+
+
+def test_region_tables_of_the_whole_gpu_sweep(lib, redzone):
+    """Every plan a case of tests/test_gpu_workspace.py can launch with, laid out on the host by the SAME make_plan: offsets
+    256-aligned and in layout order, regions disjoint with at least the red zone between them, last end + red zone <= total,
+    names unique, and the size answer the GPU test allocates covers the plan."""
+    from deepsdf_amd import _lib
+    from tests import test_gpu_workspace as T
+    from tests.ws_guard import table_problems
+    n_plans = 0
+    for G in (0, 256):
+        redzone(G)
+        sizes = {}
+        for c in T.CASES:
+            net = T.spec_of(c.net).c_struct()
+            key = (c.net, c.entry if c.entry in ("decode", "decode_latent") else c.entry in T.MODULE, c.N, c.R, c.K)
+            if key in sizes:
+                continue
+            sizes[key] = c.ws_query(lib, net)
+            for kind, N, R, seg, K, fr in c.plans():
+                rows, total = _plan_table(lib, net, N, R, kind, seg, K, fr)
+                assert not table_problems(rows, total, G), (c.id, kind, seg, K, fr, table_problems(rows, total, G))
+                assert total <= sizes[key], (c.id, kind, seg, K, fr)
+                n_plans += 1
+        for shape, _ in T.MC_GRIDS:
+            b = C.c_size_t()
+            assert lib.dsdf_mc_workspace_bytes(*shape, C.byref(b)) == 0
+            rows, total = _lib.ws_regions()
+            assert not table_problems(rows, total, G) and total == b.value
+        for nf, nq in T.MSDF_CASES:
+            b = C.c_size_t()
+            assert lib.dsdf_msdf_plan(nf, nq, None, C.byref(b), None) == 0
+            rows, total = _lib.ws_regions()
+            assert not table_problems(rows, total, G) and total == b.value
+    assert n_plans > 2000
+
+
+def test_debug_entries_check_their_arguments(lib, redzone):
+    from deepsdf_amd import _lib
+    from deepsdf_amd.net import NetSpec
+    for bad in (-256, 1, 100, 255, 257, _lib.WS_MAX_REDZONE + 256):
+        assert lib.dsdf_debug_ws_redzone(bad) == -1 and b"multiple of 256" in lib.dsdf_last_error(), bad
+    net = NetSpec(8, [32] * 4, 3, latent_in=[2]).c_struct()
+    b0, b1 = C.c_size_t(), C.c_size_t()
+    assert lib.dsdf_workspace_bytes(C.byref(net), 1000, 4, C.byref(b0)) == 0          # a refused setting changed nothing
+    redzone(_lib.WS_MAX_REDZONE)
+    assert lib.dsdf_workspace_bytes(C.byref(net), 1000, 4, C.byref(b1)) == 0 and b1.value > b0.value
+    redzone(0)
+    assert lib.dsdf_workspace_bytes(C.byref(net), 1000, 4, C.byref(b1)) == 0 and b1.value == b0.value
+    for args in ((-1, 4, 0, 0, 2, 64), (1000, -1, 0, 0, 2, 64), (1000, 4, 3, 0, 2, 64), (1000, 4, 0, 0, 9, 64), (1000, 4, 0, 0, 2, 48),
+                 (1000, 4, 0, 0, -1, 64)):
+        assert lib.dsdf_debug_ws_plan(C.byref(net), *args) == -1, args
+    assert lib.dsdf_debug_ws_plan(None, 1000, 4, 0, 0, 2, 64) == -1
+    assert lib.dsdf_debug_ws_plan(C.byref(net), 1000, 4, _lib.WS_PLAN_TRAIN, 1, 2, 32) == 0
+    n, total = C.c_int32(), C.c_size_t()
+    assert lib.dsdf_debug_ws_regions(None, 0, None, None) == -1 and b"n_regions" in lib.dsdf_last_error()
+    assert lib.dsdf_debug_ws_regions(None, 0, C.byref(n), C.byref(total)) == 0 and n.value > 20 and total.value > 0    # NULL table: the count
+    assert lib.dsdf_debug_ws_regions(None, 0, C.byref(n), None) == 0
+    small = (_lib.DsdfWsRegion * (n.value - 1))()
+    for r in small:
+        r.offset = 77
+    n2 = C.c_int32()
+    assert lib.dsdf_debug_ws_regions(small, n.value - 1, C.byref(n2), None) == -1 and n2.value == n.value     # too small: refused,
+    assert all(r.offset == 77 for r in small) and b"regions" in lib.dsdf_last_error()                        # nothing written
+    exact = (_lib.DsdfWsRegion * n.value)()
+    assert lib.dsdf_debug_ws_regions(exact, n.value, C.byref(n2), C.byref(total)) == 0
+    names = [r.name.decode() for r in exact]
+    assert names[0] == "in0" and "part" in names and "hoistU" in names and "dwslab3" in names and exact[-1].offset + exact[-1].bytes <= total.value
+    rows, tot = _lib.ws_regions()
+    assert [r[0] for r in rows] == names and tot == total.value
+
+
+def test_latent_size_zero_never_reaches_segment_mode(lib):
+    """validate() accepts latent_size == 0 (the general inference path takes such a net).  The hoist kernel of segment mode clamps
+    its loads to column latent_size - 1: every way into it must refuse L = 0 on the host, before anything is launched."""
+    from deepsdf_amd import _lib
+    from deepsdf_amd.net import NetSpec
+    net = NetSpec(0, [32, 32, 32], 3).c_struct()
+    b = C.c_size_t()
+    assert lib.dsdf_workspace_bytes(C.byref(net), 256, 4, C.byref(b)) == 0 and b.value > 0        # sizes: fine
+    assert lib.dsdf_decode_workspace_bytes(C.byref(net), 256, C.byref(b)) == 0
+    assert lib.dsdf_decode_latent_supported(C.byref(net)) == 0
+    dummy = C.c_void_p(4096)                                    # never dereferenced: the argument checks come first
+    batch = _lib.DsdfBatch(4096, 4096, 4, 4096, 4096, 256, 256, 0, 64)                           # 4 equal segments of 64: segment-mode shaped
+    cfg = _lib.DsdfLossCfg()
+    cfg.clamp_dist, cfg.training = 0.1, 1
+    rc = lib.dsdf_train_forward_backward(C.byref(net), dummy, dummy, dummy, 4, C.byref(batch), C.byref(cfg), dummy, dummy, dummy, None, 0,
+                                         dummy, 1 << 30, None)
+    assert rc == -1 and b"latent_size > 0" in lib.dsdf_last_error()
+    adam = _lib.DsdfAdamCfg(1, 5e-4, 1e-3, 0.9, 0.999, 1e-8, None)
+    rc = lib.dsdf_train_step(C.byref(net), dummy, dummy, dummy, dummy, dummy, dummy, 4, dummy, dummy, dummy, C.byref(batch), C.byref(cfg),
+                             C.byref(adam), dummy, None, dummy, 1 << 30, None)
+    assert rc == -1 and b"latent_size > 0" in lib.dsdf_last_error()
+    rc = lib.dsdf_decode_latent(C.byref(net), dummy, dummy, dummy, dummy, 256, dummy, dummy, 1 << 30, None)
+    assert rc == -1 and b"dsdf_decode_latent needs" in lib.dsdf_last_error()

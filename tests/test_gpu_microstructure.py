@@ -56,7 +56,7 @@ def test_public_names_import():
     from deep_sdf.mesh import CapBorderDict, create_mesh_microstructure      # noqa: F401
     from deepsdf_amd.spline import BSplineField                              # noqa: F401
     from deepsdf_amd import _lib
-    assert _lib.lib().dsdf_abi_version() == 18
+    assert _lib.lib().dsdf_abi_version() == 19
 
 
 @pytest.mark.parametrize("N,tiling", CASES)

@@ -294,3 +294,20 @@ def test_torchscript_export_matches_reference_outputs(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     m = torch.jit.load(os.path.join(exp, "cpp_model.pt"))
     assert rel_err(m(g10.get("eval/x")).reshape(-1), g10.get("eval/y")) <= 1e-6
+
+
+def test_reconstruct_refuses_resample_shapes_the_sampler_cannot_fill():
+    """reconstruct(resample=...): the device sampler writes 2 * (S // 2) rows per shape.  An odd S would shift every shape's rows
+    against seg_len = S and leave the last B rows of the batch unwritten -- refused as an argument error, like a `resample` tuple
+    without scene ids; both before anything touches the engine or a device (none is needed to see it)."""
+    from deepsdf_amd.reconstruct import reconstruct
+    xyz, sdf = torch.zeros(2, 63, 3), torch.zeros(2, 63)
+    with pytest.raises(ValueError, match="S must be even, got 63"):
+        reconstruct(None, xyz, sdf, num_iterations=4, resample=(object(), [0, 1]))
+    with pytest.raises(ValueError, match="S must be even, got 1"):
+        reconstruct(None, xyz[:, :1], sdf[:, :1], num_iterations=4, resample=(object(), [0, 1], None))
+    for short in ((), (object(),), object()):
+        with pytest.raises(ValueError, match="scene_ids"):
+            reconstruct(None, torch.zeros(2, 64, 3), torch.zeros(2, 64), num_iterations=4, resample=short)
+    with pytest.raises(ValueError, match="two ways"):
+        reconstruct(None, torch.zeros(2, 64, 3), torch.zeros(2, 64), num_iterations=4, resample=(object(), [0, 1]), callback=lambda it: None)

@@ -262,7 +262,7 @@ def _grid_struct(dims=(10, 10, 10), tiling=(2, 2, 2)):
 
 def test_ms_arguments_are_refused_before_any_launch(lib):
     from deepsdf_amd import _lib
-    assert lib.dsdf_abi_version() == 18
+    assert lib.dsdf_abi_version() == 19
     fake = C.c_void_p(1 << 20)          # never dereferenced: every call below is refused before a launch
     g = _grid_struct()
     s, keep = _spline_struct()
