@@ -430,6 +430,106 @@ def test_region_tables_of_the_whole_gpu_sweep(lib, redzone):
     assert n_plans > 2000
 
 
+def test_break_point_value_sweep_lists_what_it_must():
+    """The conditions of tests/test_gpu_breakpoints.py's case list (not measurements): both product nets at v - 1, v, v + 1 of every
+    threshold and at every BIG_N, every R of R_VALUES, many short segments, every entry point, every family of the workspace sweep
+    (or a stated reason), every segment shape of the sweep; every group reaches the one test that runs it; the pinned table of restated bf16 bounds is well-formed."""
+    import inspect
+    from collections import Counter
+    from tests import test_gpu_breakpoints as B
+    from tests import test_gpu_workspace as T
+    per = Counter(g.tier for g in B.GROUPS)
+    n_launch = sum(len(g.launches) for g in B.GROUPS)
+    print(f"\nbreak-point value sweep: {len(B.GROUPS)} oracle runs {dict(per)}, {n_launch} (net, entry) pairs")
+    for net in B.PRODUCT_NETS:
+        mine = [g for g in B.GROUPS if g.tier == 1 and g.onet == net]
+        ns = {g.N for g in mine}
+        for name, v in T.thresholds().items():
+            assert {v - 1, v, v + 1} <= ns | {0}, (net, name)
+        assert set(T.BIG_N) <= ns and set(T.n_values()) <= ns, net
+        assert {g.R for g in mine} >= set(T.R_VALUES), net
+        assert any(g.R >= 2000 and g.R > g.N / 32 for g in mine), net
+        for g in mine:                                   # the full product: these entries at EVERY N
+            assert {"fb", "step", "decode", "decode_latent"} <= {e for n, e in g.launches if n == net}, g.id
+        for v in T.thresholds().values():                # ... and the rest exactly one above every threshold
+            g = next(g for g in mine if g.N == v + 1)
+            want = set(B.ENTRIES) - (set() if T._fused(net) else {"phase2", "phase4"})
+            assert want <= {e for n, e in g.launches if n == net}, g.id
+    nets = {n for g in B.GROUPS for n, _ in g.launches}
+    assert set(B.EXCLUDED) == {"L0"} and all(B.EXCLUDED.values())
+    assert nets | set(B.EXCLUDED) == set(T.NETS) and not nets & set(B.EXCLUDED)
+    assert {e for g in B.GROUPS for _, e in g.launches} == set(B.ENTRIES)
+    for net in B.SEGMENT_NETS:                           # section 3 of the sweep, shape by shape
+        mine = {g.lens for g in B.GROUPS if g.onet == net and ("fb" in {e for n, e in g.launches if n == net})}
+        for lens in [(sl,) * R for R, sl in T.SEG_RS] + [tuple(l) for l in T.SEG_GENERAL]:
+            assert lens in mine or (net == "fused_8x512" and sum(lens) > T.thresholds()["last_blocks"]), (net, lens[:4])
+    for g in B.GROUPS:
+        assert sum(g.lens) == g.N and len(g.lens) == g.R and g.launches and g.onet not in B.EXCLUDED
+    # every group belongs to exactly one parametrisation of the one test, whose body runs all of its groups and all of their launches
+    assert sorted(B.TESTS) == sorted({(g.tier, g.onet) for g in B.GROUPS}) and len(set(B.TESTS)) == len(B.TESTS)
+    # the restated bf16 bounds name groups and quantities that exist, on bf16 nets only, and no spread can widen one at run time
+    gids = {g.id for g in B.GROUPS if B.NETS[g.onet][1].get("forward_bf16")}
+    for (gid, q), d in B.BF16_RESTATED.items():
+        assert gid in gids and q in B.QUANTITIES and 0 < d < 0.02, (gid, q, d)
+    src = inspect.getsource(B)
+    for word in ("skip", "xfail", "importorskip"):       # nothing in the module can skip or xfail a case
+        assert "pytest." + word not in src and "mark." + word not in src
+
+
+def test_safe_batch_takes_explicit_segment_lengths_and_draws_what_it_drew_before():
+    """tests/safe_batch.py: (a) three calls of the builder's earlier form (equal segments; 2-D geometry; rows of a larger table) give
+    the tensors they gave before it took `lens` (SHA-256 of idx | xyz | gt, pinned on the earlier code); (b) lens = [S] * B is that same
+    batch; (c) ragged lengths sum to N, every segment reads the row `scenes` names, and the result is margin-safe by the oracle."""
+    import hashlib
+    import math
+    import torch
+    from oracle import deepsdf_oracle as orc
+    from tests.safe_batch import big_batch, safe_batch
+    from tests.test_gpu_parity import SEG_SHAPES
+
+    def digest(*ts):
+        m = hashlib.sha256()
+        for t in ts:
+            m.update(t.contiguous().numpy().tobytes())
+        return m.hexdigest()
+
+    def state(name):
+        c = SEG_SHAPES[name]
+        net = orc.make_net(c["L"], **c["net"])
+        params = orc.init_params(net, 31)
+        lat0 = torch.randn(c["B"], c["L"], generator=torch.Generator().manual_seed(32)) / math.sqrt(c["L"])
+        lat0[-1] *= 1.7 / lat0[-1].norm()
+        return net, orc.TrainState.create({k: v.double() for k, v in params.items()}, lat0.double()), c["B"], c["S"], c["net"]["geom_dimension"]
+
+    net, st, B, S, G = state("skip2_w64")
+    a = safe_batch(net, st, B, S, 500, 0.1, 1.0, 77, G=G)
+    assert digest(*a) == "1ae796386144c98516ddc663ee36447eceaba3af0e6b083adce377eb0db47570"
+    b = safe_batch(net, st, None, None, 500, 0.1, 1.0, 77, G=G, lens=[S] * B)
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    net, st, B, S, G = state("geom2_plain")
+    assert digest(*safe_batch(net, st, B, S, 500, 0.1, 1.0, 77, G=G)) == "774d94455d792cc98f5e4b338a57be027b254aa0c6e6b4bccdf0a32106edff51"
+    net, st, B, S, G = state("noskip_w40_L6_drop")
+    st.latents = torch.cat([st.latents, st.latents * 0.5, st.latents * 0.25])
+    scenes = torch.tensor([4, 1])
+    assert digest(*safe_batch(net, st, B, S, 950, 0.1, 1.0, 7, scenes=scenes)) == "4f63a4083fd6bfb0163ddb459c2f80afe44fa8be2234d4934f0ac8e880fc2d20"
+    # ragged lengths through a permuted scenes vector into the 6-row table, one row in use above code_bound
+    lens, scenes = [1, 63, 64, 65, 7], torch.tensor([5, 0, 3, 2, 4])
+    st.latents[3] *= 1.7 / st.latents[3].norm()
+    idx, xyz, gt = safe_batch(net, st, None, None, 11, 0.1, 1.0, 77, G=G, scenes=scenes, lens=lens)
+    assert idx.numel() == xyz.shape[0] == gt.shape[0] == sum(lens) and xyz.shape[1] == G
+    assert torch.equal(torch.unique_consecutive(idx, return_counts=True)[1], torch.tensor(lens))
+    assert torch.equal(torch.unique_consecutive(idx), scenes)
+    lat = st.latents.clone()
+    orc.renorm_rows_(lat, idx, 1.0)
+    y, sv = orc.decoder_forward(net, st.params, torch.cat([lat[idx], xyz.double()], 1), training=True, masks=orc.dropout_masks(net, 77, 0, sum(lens)),
+                                track_margin=True)
+    d = torch.clamp(y, -0.1, 0.1) - torch.clamp(gt.double(), -0.1, 0.1)
+    assert float(sv.min_abs_pre.min()) >= 1e-6 and not bool((((y.abs() - 0.1).abs() < 2e-5) | ((d != 0) & (d.abs() < 2e-5))).any())
+    assert big_batch(None, None, 3, lens=[2, 5])[0].tolist() == [0, 0, 1, 1, 1, 1, 1]
+    with pytest.raises(RuntimeError, match="margin-safe"):     # a margin nothing can meet: it raises, it never returns an unsafe batch
+        safe_batch(net, st, None, None, 11, 0.1, 1.0, 77, G=G, scenes=scenes, lens=lens, relu_margin=1e3)
+
+
 def test_debug_entries_check_their_arguments(lib, redzone):
     from deepsdf_amd import _lib
     from deepsdf_amd.net import NetSpec

@@ -112,6 +112,12 @@ ALL_ENTRIES = TRAIN + PHASED + MODULE + INFER
 R_VALUES = [1, 2, 3, 64, 512, 2000]
 
 
+# section 3 of build_cases(): (R, seg_len) pairs in segment mode, and explicit lengths sent down the general path (seg_len 0)
+SEG_RS = ((3, 32), (3, 64), (3, 96), (2, 40), (3, 100), (64, 64), (512, 32), (2000, 3), (2000, 32), (1, 16 * K_["FROWS"] * 2 * K_["LAT_SLICES_MAX"]))
+SEG_GENERAL = ([1, 63, 64, 65, 300, 507],      # ragged by construction
+               [96] * 3)                       # equal, but sent down the general path
+
+
 def spec_of(net):
     L, kw, _ = NETS[net]
     return NetSpec(L, **kw)
@@ -224,11 +230,11 @@ def build_cases():
     cases.append(Case("family_fused_8x512", "fused_8x512", "step", 160000, 10))
     # 3. segment shapes: seg_len at multiples and non-multiples of 32 and 64, many short segments (R > N / 32), ragged
     for net in ("w32_4x32", "w32x2_4x64", "n128_6x128", "fused_8x512", "bf16_8x512", "split_8x512", "L257"):
-        for R, sl in ((3, 32), (3, 64), (3, 96), (2, 40), (3, 100), (64, 64), (512, 32), (2000, 3), (2000, 32), (1, 16 * K_["FROWS"] * 2 * K_["LAT_SLICES_MAX"])):
+        for R, sl in SEG_RS:
             for entry in ("fb", "step", "phase2"):
                 cases.append(Case("segments_" + net, net, entry, R * sl, R))
-        cases.append(Case("segments_" + net, net, "fb", 1000, lens=[1, 63, 64, 65, 300, 507], seg_len=0))      # ragged by construction
-        cases.append(Case("segments_" + net, net, "fb", 96 * 3, lens=[96] * 3, seg_len=0))                      # equal, but sent down the general path
+        for lens in SEG_GENERAL:
+            cases.append(Case("segments_" + net, net, "fb", sum(lens), lens=list(lens), seg_len=0))
     # 4. latent_size 0: the general inference path takes it; every training entry refuses it BEFORE it plans anything
     for N in (1, 65, 3000):
         cases.append(Case("L0", "L0", "decode", N))
