@@ -7,10 +7,13 @@ domain is tiled with mirrored unit cells, the borders are capped and the zero le
 deep_sdf.mesh.create_mesh_microstructure: rows, decode, caps and marching cubes on the GPU.
 
     python create_microstructure.py -e <experiment_dir> -c latest --tiling 4 4 2 --codes 0 3 1 2 5 5 7 8 \\
-        [--degrees 1 1 1] [--resolution 256] [--cap x1=1:0.1 z0=-1:0] [-b 32] -o out.ply
+        [--degrees 1 1 1] [--resolution 256] [--cap x1=1:0.1 z0=-1:0] [-b 32] [--jacobian out.npz] -o out.ply
 
 With degrees p the number of codes must be a product nx * ny * nz of control points per axis, each > p; the split is taken
 from --control-points, or for 8 codes 2 x 2 x 2.  Knot vectors are uniform and clamped.
+
+--jacobian FILE.npz also writes the mesh with its derivative with respect to the control points: verts [V, 3], faces [F, 3],
+jac [V, ncp, L] = d verts[v, axis[v]] / d control points, axis [V] (the other two coordinates of a vertex do not depend on them).
 """
 import argparse
 
@@ -45,7 +48,7 @@ def parse_caps(items):
 
 
 def main(experiment_directory, checkpoint, tiling, codes, out, degrees=(1, 1, 1), control_points=None, resolution=256,
-         caps=None, max_batch=32):
+         caps=None, max_batch=32, jacobian=None):
     if not torch.cuda.is_available():
         raise RuntimeError("create_microstructure.py (deepsdf_amd) needs an AMD GPU: the HIP path has no CPU fallback")
     decoder = ws.load_trained_model(experiment_directory, checkpoint)
@@ -66,6 +69,11 @@ def main(experiment_directory, checkpoint, tiling, codes, out, degrees=(1, 1, 1)
     deep_sdf.mesh.create_mesh_microstructure(list(tiling), decoder, field, name, N=resolution, max_batch=int(max_batch ** 3),
                                              cap_border_dict=caps, save_ply_file=True)
     print(f"wrote {name}.ply")
+    if jacobian:
+        d = deep_sdf.mesh.microstructure_mesh_diff(list(tiling), decoder, field, resolution, int(max_batch ** 3), caps)
+        jac, axis = d.jacobian()
+        np.savez(jacobian, verts=d.verts.cpu().numpy(), faces=d.faces.cpu().numpy(), jac=jac.cpu().numpy(), axis=axis.cpu().numpy())
+        print(f"wrote {jacobian}")
 
 
 if __name__ == "__main__":
@@ -79,7 +87,9 @@ if __name__ == "__main__":
     parser.add_argument("--resolution", type=int, default=256, help="grid points per axis (N of create_mesh_microstructure)")
     parser.add_argument("--cap", type=str, nargs="*", default=None, help="<face>=<cap>:<measure>, e.g. x1=1:0.1; in order")
     parser.add_argument("--max_batch", "-b", type=int, default=32, help="decode chunk = max_batch^3 grid points")
+    parser.add_argument("--jacobian", type=str, default=None, metavar="FILE.npz",
+                        help="also write verts, faces, jac [V, ncp, L] (d vertex / d control points along axis) and axis")
     parser.add_argument("--output", "-o", type=str, required=True)
     args = parser.parse_args()
     main(args.experiment_directory, args.checkpoint, args.tiling, args.codes, args.output, args.degrees, args.control_points,
-         args.resolution, parse_caps(args.cap), args.max_batch)
+         args.resolution, parse_caps(args.cap), args.max_batch, args.jacobian)

@@ -66,6 +66,18 @@ class DsdfMsCap(C.Structure):
 
 
 MS_MAX_CAPS = 6
+MS_WEIGHTS = 64                        # weight slots per point of dsdf_ms_rows_at: (k * 4 + j) * 4 + i
+
+
+class DsdfMsdMesh(C.Structure):
+    _fields_ = [("grid", C.c_void_p), ("edge_point", C.c_void_p), ("edge_axis", C.c_void_p), ("band_of", C.c_void_p),
+                ("n_verts", C.c_int64), ("dims", C.c_int32 * 3), ("scale", C.c_float * 3), ("level", C.c_float)]
+
+
+class DsdfMsdBand(C.Structure):
+    _fields_ = [("G", C.c_void_p), ("weights", C.c_void_p), ("base", C.c_void_p), ("mask", C.c_void_p),
+                ("n_band", C.c_int64), ("ld_g", C.c_int64), ("degree", C.c_int32 * 3), ("n_cp", C.c_int32 * 3),
+                ("L", C.c_int32)]
 
 
 class DsdfWsRegion(C.Structure):      # debug only: one row of dsdf_debug_ws_regions
@@ -128,6 +140,13 @@ PROTOTYPES = {
     "dsdf_debug_ws_regions": [C.POINTER(DsdfWsRegion), _I32, C.POINTER(_I32), C.POINTER(_SZ)],
     "dsdf_debug_ws_plan": [_NET, _I64, _I64, _I32, _I32, _I32, _I32],
     "dsdf_msdf_query": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P],
+    "dsdf_module_input_grad": [_NET, _P, _P, _P, _I64, _P, _I64, _P, _SZ, _P],
+    "dsdf_mc_edges": [_I32, _I32, _I32, _I64, _P, _P, _P, _SZ, _P],
+    "dsdf_ms_rows_at": [C.POINTER(DsdfMsSpline), C.POINTER(DsdfMsGrid), _P, _I64, _P, _P, _P, _P],
+    "dsdf_msd_vjp_workspace_bytes": [_I64, _I64, _I32, C.POINTER(_SZ), C.POINTER(_I32)],
+    "dsdf_msd_jacobian": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _I32, _P, _P, _P],
+    "dsdf_msd_jvp": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P],
+    "dsdf_msd_vjp": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P, _SZ, _P],
 }
 
 _lib = None

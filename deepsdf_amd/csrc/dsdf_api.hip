@@ -22,6 +22,7 @@
 #include "mcubes.hpp"
 #include "meshsdf.hpp"
 #include "msgrid.hpp"
+#include "msdiff.hpp"
 
 using namespace dsdf;
 
@@ -1467,12 +1468,13 @@ int dsdf_module_forward(const DsdfNet* net, const float* packed, const float* pa
   return launch_last<LAST_FWD>(a, P.last_blocks, st);
 }
 
-int dsdf_module_backward(const DsdfNet* net, const float* packed, const float* params, const float* d_sdf, int64_t n,
-                         int32_t training, const uint32_t* dropout_key, float* grads, int32_t accumulate, float* d_input,
-                         int64_t ld_din, void* ws, size_t ws_bytes, void* stream) {
+// want_dw == false (dsdf_module_input_grad): the same launches without the weight-gradient ones; grads is not touched
+static int module_backward_impl(const DsdfNet* net, const float* packed, const float* params, const float* d_sdf, int64_t n,
+                                int32_t training, const uint32_t* dropout_key, float* grads, int32_t accumulate, float* d_input,
+                                int64_t ld_din, void* ws, size_t ws_bytes, void* stream, bool want_dw) {
   TRY(check_common(net, packed, params, ws));
   if (n == 0) return 0;
-  if (!d_sdf || !grads || n < 0) return fail(DSDF_E_INVALID, "bad d_sdf/grads");
+  if (!d_sdf || (want_dw && !grads) || n < 0) return fail(DSDF_E_INVALID, "bad d_sdf/grads");
   if (d_input && ld_din < net->in_dim[0]) return fail(DSDF_E_INVALID, "ld_din too small");
   if (training && net->latent_dropout && d_input && !dropout_key)
     return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key for d/d(input))");
@@ -1500,7 +1502,7 @@ int dsdf_module_backward(const DsdfNet* net, const float* packed, const float* p
   if (fusedb) {
     FusedBwdHead h = make_head(net, P, ws, packed, params, HEAD_EXT, training);
     h.d_sdf = d_sdf; h.u_in = at<float>(ws, P.u_off);
-    TRY(run_backward_fused(net, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, true, h));
+    TRY(run_backward_fused(net, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, want_dw, h));
   } else {
     TRY(launch_last<LAST_BWD_EXT>(a, P.last_blocks, st));
     bool xyz_acc = false;
@@ -1512,7 +1514,7 @@ int dsdf_module_backward(const DsdfNet* net, const float* packed, const float* p
       LAUNCH_OK("last_xyz_grad_kernel");
       xyz_acc = true;
     }
-    TRY(run_backward(net, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, true, dropout_key, 0,
+    TRY(run_backward(net, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, want_dw, dropout_key, 0,
                      (d_input && net->xyz_in_all) ? &xyz_acc : nullptr));
     if (last_layer_skip(net) && d_input) used_dzB = true;      // (last_layer_kernel wrote it)
     if (d_input) {
@@ -1536,6 +1538,20 @@ int dsdf_module_backward(const DsdfNet* net, const float* packed, const float* p
     LAUNCH_OK("add2_kernel");
   }
   return 0;
+}
+
+int dsdf_module_backward(const DsdfNet* net, const float* packed, const float* params, const float* d_sdf, int64_t n,
+                         int32_t training, const uint32_t* dropout_key, float* grads, int32_t accumulate, float* d_input,
+                         int64_t ld_din, void* ws, size_t ws_bytes, void* stream) {
+  return module_backward_impl(net, packed, params, d_sdf, n, training, dropout_key, grads, accumulate, d_input, ld_din, ws, ws_bytes,
+                              stream, true);
+}
+
+int dsdf_module_input_grad(const DsdfNet* net, const float* packed, const float* params, const float* d_sdf, int64_t n,
+                           float* d_input, int64_t ld_din, void* ws, size_t ws_bytes, void* stream) {
+  if (n < 0) return fail(DSDF_E_INVALID, "input gradient: %lld rows", (long long)n);
+  if (n > 0 && (!d_sdf || !d_input)) return fail(DSDF_E_INVALID, "input gradient: NULL d_sdf or d_input");
+  return module_backward_impl(net, packed, params, d_sdf, n, 0, nullptr, nullptr, 0, d_input, ld_din, ws, ws_bytes, stream, false);
 }
 
 // Forward-mode tangent of the decoder at the point of the last dsdf_module_forward on this workspace:
@@ -2102,6 +2118,27 @@ int dsdf_mc_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float lev
   return 0;
 }
 
+int dsdf_mc_edges(int32_t nx, int32_t ny, int32_t nz, int64_t n_verts, int64_t* edge_point, int32_t* edge_axis, void* ws,
+                  size_t ws_bytes, void* stream) {
+  McPlan P;
+  TRY(mc_plan(nx, ny, nz, &P, &t_last_plan));
+  if (n_verts < 0 || n_verts > INT32_MAX)
+    return fail(DSDF_E_INVALID, "marching cubes edges: %lld vertices (0 .. %d)", (long long)n_verts, INT32_MAX);
+  if (!ws) return fail(DSDF_E_INVALID, "marching cubes edges: NULL workspace");
+  if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "marching cubes edges: workspace %zu < %zu bytes", ws_bytes, P.total);
+  if (n_verts > 0 && (!edge_point || !edge_axis)) return fail(DSDF_E_INVALID, "marching cubes edges: NULL edge_point or edge_axis");
+  if (n_verts == 0) return 0;
+  McWs w;
+  char* b = (char*)ws;
+  w.mask = (uint8_t*)(b + P.mask); w.cas = (uint8_t*)(b + P.cas); w.vbase = (int32_t*)(b + P.vbase);
+  w.bv = (int32_t*)(b + P.bv); w.bf = (int32_t*)(b + P.bf); w.ov = (int64_t*)(b + P.ov); w.of = (int64_t*)(b + P.of);
+  w.nblocks = P.nblocks;
+  hipLaunchKernelGGL(mc_edge_kernel, dim3((unsigned)P.nblocks), dim3(MC_BLOCK), 0, (hipStream_t)stream, P.npts, w, n_verts, edge_point,
+                     edge_axis);
+  LAUNCH_OK("mc_edge_kernel");
+  return 0;
+}
+
 int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width) {
   if (width) *width = MC_TABLE_W;
   if (!table) return width ? 0 : fail(DSDF_E_INVALID, "NULL table and width");
@@ -2276,6 +2313,140 @@ int dsdf_ms_rows(const DsdfMsSpline* spline, const DsdfMsGrid* grid, int64_t sta
     hipLaunchKernelGGL((ms_rows_kernel<false>), dim3((unsigned)blocks), dim3(MS_BLOCK), 0, (hipStream_t)stream, g, s, first, n, points,
                        test, xyz, rows);
   LAUNCH_OK("ms_rows_kernel");
+  return 0;
+}
+
+int dsdf_ms_rows_at(const DsdfMsSpline* spline, const DsdfMsGrid* grid, const int64_t* indices, int64_t n, float* rows,
+                    float* weights, int32_t* base, void* stream) {
+  MsGrid g; MsSpline s;
+  int64_t npts;
+  TRY(ms_grid(grid, &g, &npts));
+  TRY(ms_spline(spline, &s));
+  if (n < 0 || n > INT32_MAX) return fail(DSDF_E_INVALID, "microstructure rows at indices: %lld points in one call (0 .. %d)", (long long)n, INT32_MAX);
+  if (!indices || !rows) return fail(DSDF_E_INVALID, "microstructure rows at indices: NULL indices or rows");
+  if (n == 0) return 0;
+  const int64_t blocks = (n + MS_TILE - 1) / MS_TILE;
+  if (s.deg[0] == 1 && s.deg[1] == 1 && s.deg[2] == 1)
+    hipLaunchKernelGGL((ms_rows_kernel<true, true>), dim3((unsigned)blocks), dim3(MS_BLOCK), 0, (hipStream_t)stream, g, s, (int64_t)0, n,
+                       (const float*)nullptr, 1, 1, rows, indices, npts, weights, base);
+  else
+    hipLaunchKernelGGL((ms_rows_kernel<false, true>), dim3((unsigned)blocks), dim3(MS_BLOCK), 0, (hipStream_t)stream, g, s, (int64_t)0, n,
+                       (const float*)nullptr, 1, 1, rows, indices, npts, weights, base);
+  LAUNCH_OK("ms_rows_kernel(at)");
+  return 0;
+}
+
+// ---- microstructure mesh derivatives (msdiff.hpp) ----------------------------------------------------------
+namespace {
+struct MsdPlan { int64_t per; int32_t n_parts, n_tiles; size_t part, ws; };
+
+int msd_plan(int64_t n_verts, int64_t ncp, int32_t L, MsdPlan* P, WsTable* rec = nullptr) {
+  if (n_verts < 0 || n_verts > INT32_MAX) return fail(DSDF_E_INVALID, "mesh derivative: %lld vertices (0 .. %d)", (long long)n_verts, INT32_MAX);
+  if (L < 1) return fail(DSDF_E_INVALID, "mesh derivative: %d latent columns", L);
+  if (ncp < 1 || ncp * (int64_t)L > INT32_MAX)
+    return fail(DSDF_E_INVALID, "mesh derivative: control net of %lld x %d floats (1 .. %d)", (long long)ncp, L, INT32_MAX);
+  P->per = ncp * L;
+  P->n_parts = (int32_t)((n_verts + MSD_VJP_VERTS - 1) / MSD_VJP_VERTS);
+  P->n_tiles = (int32_t)((P->per + MSD_VJP_TILE - 1) / MSD_VJP_TILE);
+  if (P->n_tiles > 65535) return fail(DSDF_E_INVALID, "mesh derivative: control net of %lld floats (the adjoint takes at most %lld)", (long long)P->per, 65535ll * MSD_VJP_TILE);
+  P->part = (size_t)P->n_parts * (size_t)P->per * 4;
+  P->ws = (size_t)rup((int64_t)P->part, 256) + g_redzone.load(std::memory_order_relaxed);
+  if (rec) { rec->reset(); rec->add("msd_vjp_part", -1, 0, P->part); rec->total = P->ws; }
+  return 0;
+}
+
+int msd_setup(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, MsdMesh* M, MsdBand* B) {
+  if (!mesh || !band) return fail(DSDF_E_INVALID, "mesh derivative: NULL mesh or band");
+  if (mesh->n_verts < 0 || mesh->n_verts > INT32_MAX)
+    return fail(DSDF_E_INVALID, "mesh derivative: %lld vertices (0 .. %d)", (long long)mesh->n_verts, INT32_MAX);
+  M->npts = 1;
+  for (int a = 0; a < 3; ++a) {
+    const int n = mesh->dims[a];
+    if (n < 2 || n > MC_MAX_DIM) return fail(DSDF_E_INVALID, "mesh derivative: grid size %d outside 2 .. %d", n, MC_MAX_DIM);
+    if (!std::isfinite(mesh->scale[a])) return fail(DSDF_E_INVALID, "mesh derivative: scale %d is not finite", a);
+    M->npts *= n;
+    M->scale[a] = mesh->scale[a];
+  }
+  M->stride[0] = (int64_t)mesh->dims[1] * mesh->dims[2]; M->stride[1] = mesh->dims[2]; M->stride[2] = 1;
+  if (band->L < 1) return fail(DSDF_E_INVALID, "mesh derivative: %d latent columns", band->L);
+  if (band->n_band < 0 || band->n_band > INT32_MAX) return fail(DSDF_E_INVALID, "mesh derivative: %lld band rows", (long long)band->n_band);
+  if (band->ld_g < band->L) return fail(DSDF_E_INVALID, "mesh derivative: ld_g %lld < L %d", (long long)band->ld_g, band->L);
+  int64_t ncp = 1;
+  for (int a = 0; a < 3; ++a) {
+    const int p = band->degree[a], n = band->n_cp[a];
+    if (p < 1 || p > MS_MAX_DEG) return fail(DSDF_E_INVALID, "mesh derivative: degree %d of axis %d outside 1 .. %d", p, a, MS_MAX_DEG);
+    if (n <= p || n > (1 << 20)) return fail(DSDF_E_INVALID, "mesh derivative: %d control points on axis %d (degree %d)", n, a, p);
+    B->deg[a] = p; B->ncp[a] = n;
+    ncp *= n;
+  }
+  if (ncp * (int64_t)band->L > INT32_MAX) return fail(DSDF_E_INVALID, "mesh derivative: control net of %lld floats (at most %d)", (long long)(ncp * band->L), INT32_MAX);
+  if (mesh->n_verts > 0) {
+    if (!mesh->grid || !mesh->edge_point || !mesh->edge_axis || !mesh->band_of)
+      return fail(DSDF_E_INVALID, "mesh derivative: NULL grid, edge_point, edge_axis or band_of");
+    if (band->n_band > 0 && (!band->G || !band->weights || !band->base || !band->mask))
+      return fail(DSDF_E_INVALID, "mesh derivative: NULL G, weights, base or mask");
+  }
+  M->grid = mesh->grid; M->edge_point = mesh->edge_point; M->edge_axis = mesh->edge_axis; M->band_of = mesh->band_of;
+  M->V = mesh->n_verts; M->level = mesh->level;
+  B->G = band->G; B->w = band->weights; B->base = band->base; B->m = band->mask;
+  B->nb = band->n_band; B->ldg = band->ld_g; B->L = band->L; B->ncp_total = (int)ncp;
+  return 0;
+}
+}  // namespace
+
+int dsdf_msd_vjp_workspace_bytes(int64_t n_verts, int64_t n_control_points, int32_t L, size_t* bytes, int32_t* n_parts) {
+  MsdPlan P;
+  TRY(msd_plan(n_verts, n_control_points, L, &P, &t_last_plan));
+  if (!bytes && !n_parts) return fail(DSDF_E_INVALID, "mesh derivative: every output is NULL");
+  if (bytes) *bytes = P.ws;
+  if (n_parts) *n_parts = P.n_parts;
+  return 0;
+}
+
+int dsdf_msd_jacobian(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, int32_t full, float* jac, int32_t* axis, void* stream) {
+  MsdMesh M; MsdBand B;
+  TRY(msd_setup(mesh, band, &M, &B));
+  if (M.V == 0) return 0;
+  if (!jac) return fail(DSDF_E_INVALID, "mesh derivative: NULL jacobian");
+  const bool vec = B.L % 4 == 0 && (reinterpret_cast<uintptr_t>(jac) & 15) == 0;
+  const int64_t stores = (int64_t)B.ncp_total * (B.L / (vec ? 4 : 1)) * (full ? 3 : 1);   // per vertex
+  const int vpw = stores >= MSD_DENSE_STORES ? 1 : (int)std::min<int64_t>(MSD_DENSE_VERTS, MSD_DENSE_STORES / stores);
+  const dim3 grid((unsigned)((M.V + vpw - 1) / vpw));
+  if (vec) hipLaunchKernelGGL((msd_dense_kernel<4>), grid, dim3(MSD_BLOCK), 0, (hipStream_t)stream, M, B, jac, axis, (int)(full != 0), vpw);
+  else hipLaunchKernelGGL((msd_dense_kernel<1>), grid, dim3(MSD_BLOCK), 0, (hipStream_t)stream, M, B, jac, axis, (int)(full != 0), vpw);
+  LAUNCH_OK("msd_dense_kernel");
+  return 0;
+}
+
+int dsdf_msd_jvp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* d_cp, float* d_verts, void* stream) {
+  MsdMesh M; MsdBand B;
+  TRY(msd_setup(mesh, band, &M, &B));
+  if (M.V == 0) return 0;
+  if (!d_cp || !d_verts) return fail(DSDF_E_INVALID, "mesh derivative: NULL d_cp or d_verts");
+  const int per = MSD_BLOCK / 64;
+  hipLaunchKernelGGL(msd_jvp_kernel, dim3((unsigned)((M.V + per - 1) / per)), dim3(MSD_BLOCK), 0, (hipStream_t)stream, M, B, d_cp, d_verts);
+  LAUNCH_OK("msd_jvp_kernel");
+  return 0;
+}
+
+int dsdf_msd_vjp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* grad_verts, float* grad_cp, void* ws, size_t ws_bytes,
+                 void* stream) {
+  MsdMesh M; MsdBand B;
+  TRY(msd_setup(mesh, band, &M, &B));
+  MsdPlan P;
+  TRY(msd_plan(M.V, B.ncp_total, B.L, &P, &t_last_plan));
+  if (!grad_cp) return fail(DSDF_E_INVALID, "mesh derivative: NULL grad_cp");
+  if (M.V > 0 && (!grad_verts || !ws)) return fail(DSDF_E_INVALID, "mesh derivative: NULL grad_verts or workspace");
+  if (M.V > 0 && ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "mesh derivative: workspace %zu < %zu bytes", ws_bytes, P.ws);
+  hipStream_t st = (hipStream_t)stream;
+  if (P.n_parts > 0) {
+    hipLaunchKernelGGL(msd_vjp_part_kernel, dim3((unsigned)P.n_parts, (unsigned)P.n_tiles), dim3(MSD_BLOCK), 0, st, M, B, grad_verts,
+                       (float*)ws);
+    LAUNCH_OK("msd_vjp_part_kernel");
+  }
+  hipLaunchKernelGGL(msd_vjp_sum_kernel, dim3((unsigned)((P.per + MSD_BLOCK - 1) / MSD_BLOCK)), dim3(MSD_BLOCK), 0, st, (const float*)ws,
+                     P.n_parts, P.per, grad_cp);
+  LAUNCH_OK("msd_vjp_sum_kernel");
   return 0;
 }
 

@@ -11,6 +11,8 @@
 //   3. vertices:  workgroup scan of popcount(mask) + offset -> vbase[p] (id of p's first vertex) and the interpolated positions
 //   4. faces:     workgroup scan of the triangle counts + offset; edge (corner c of cell p, axis a) has vertex id
 //                 vbase[q] + popcount(mask[q] & ((1 << a) - 1)), q = p + offset(c): no edge-id map
+//   edges (on request, dsdf_mc_edges): pass 3's scan again, writing (p, a) of every vertex id instead of its position; it reads
+//                 only what passes 1 and 2 left (mask, offsets)
 // The case table is generated (deepsdf_amd/mc_table.py -> mc_table.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -185,6 +187,27 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_vertex_kernel(McGrid g, McWs w, M
         const float x = b == a ? __fadd_rn((float)idx[b], t) : (float)idx[b];
         out[b] = __fadd_rn(o.origin[b], __fmul_rn(x, o.spacing[b]));
       }
+    }
+    ++id;
+  }
+}
+
+// The grid edge of every vertex id, in the vertex kernel's order: the same scan of popcount(mask) + offset, so it needs only what
+// the count pass left (mask, ov) and neither the grid nor vbase.  Nothing is written at or past nv.
+__global__ __launch_bounds__(MC_BLOCK) void mc_edge_kernel(int64_t npts, McWs w, int64_t nv, int64_t* __restrict__ edge_point,
+                                                           int32_t* __restrict__ edge_axis) {
+  __shared__ int s[MC_BLOCK];
+  const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
+  const uint32_t m = p < npts ? w.mask[p] : 0u;
+  const int n = __popc(m);
+  const int inc = mc_block_scan(n, s);
+  if (!m) return;
+  int64_t id = w.ov[blockIdx.x] + inc - n;
+  for (int a = 0; a < 3; ++a) {
+    if (!((m >> a) & 1u)) continue;
+    if (id < nv) {
+      edge_point[id] = p;
+      edge_axis[id] = a;
     }
     ++id;
   }

@@ -106,10 +106,15 @@ __device__ __forceinline__ int ms_basis(const float* __restrict__ U, int p, int 
   return span;
 }
 
-template <bool LIN>
+// AT (dsdf_ms_rows_at): the tile's points are the padded-grid indices at[t0 ..], in any order -- the coordinate arithmetic is that of
+// grid mode -- and phase 1's weights (w_out [n][MS_WEIGHTS], slot (k * 4 + j) * 4 + i, unused slots zero) and first control-point
+// index (base_out [n], -1: outside) are written too.  An index outside [0, npts) gives a zero row, zero weights and base -1.
+template <bool LIN, bool AT = false>
 __global__ __launch_bounds__(MS_BLOCK) void ms_rows_kernel(MsGrid g, MsSpline s, int64_t start, int64_t n,
                                                            const float* __restrict__ pts, int inside_test, int with_xyz,
-                                                           float* __restrict__ rows) {
+                                                           float* __restrict__ rows, const int64_t* __restrict__ at = nullptr,
+                                                           int64_t npts = 0, float* __restrict__ w_out = nullptr,
+                                                           int32_t* __restrict__ base_out = nullptr) {
   __shared__ float w_s[MS_TILE * MS_WSTRIDE];
   __shared__ float xyz_s[MS_TILE][3];
   __shared__ int base_s[MS_TILE];                            // first control point of the row, -1: outside (zeros)
@@ -118,16 +123,24 @@ __global__ __launch_bounds__(MS_BLOCK) void ms_rows_kernel(MsGrid g, MsSpline s,
   const int npt = (int)((n - t0) < (int64_t)MS_TILE ? (n - t0) : (int64_t)MS_TILE);
   if (tid < npt) {
     float xo[3];
-    if (pts) {
+    bool valid = true;
+    if (AT) {
+      int64_t gi = at[t0 + tid];
+      valid = gi >= 0 && gi < npts;
+      if (!valid) gi = 0;
+      int ijk[3];
+      ms_index(gi, g, ijk[0], ijk[1], ijk[2]);
+      for (int a = 0; a < 3; ++a) xo[a] = ms_xo(ijk[a], g.vs[a], g.org[a]);
+    } else if (pts) {
       for (int a = 0; a < 3; ++a) xo[a] = pts[(t0 + tid) * 3 + a];
     } else {
       int ijk[3];
       ms_index(start + t0 + tid, g, ijk[0], ijk[1], ijk[2]);
       for (int a = 0; a < 3; ++a) xo[a] = ms_xo(ijk[a], g.vs[a], g.org[a]);
     }
-    bool inside = true;
+    bool inside = valid;
     for (int a = 0; a < 3; ++a) {
-      xyz_s[tid][a] = ms_fold(xo[a], g.sub[a], g.mod[a], g.p[a], g.scale[a]);
+      xyz_s[tid][a] = valid ? ms_fold(xo[a], g.sub[a], g.mod[a], g.p[a], g.scale[a]) : 0.f;
       inside = inside && xo[a] >= -1.f && xo[a] <= 1.f;
     }
     int base = -1;
@@ -148,6 +161,16 @@ __global__ __launch_bounds__(MS_BLOCK) void ms_rows_kernel(MsGrid g, MsSpline s,
     base_s[tid] = base;
   }
   __syncthreads();
+  if (AT) {
+    if (base_out && tid < npt) base_out[t0 + tid] = base_s[tid];
+    if (w_out) {
+      for (int e = tid; e < npt * MS_WEIGHTS; e += MS_BLOCK) {   // coalesced: the tile's weights are one contiguous run
+        const int pt = e / MS_WEIGHTS, sl = e % MS_WEIGHTS;
+        const bool used = base_s[pt] >= 0 && (sl & 3) <= s.deg[0] && ((sl >> 2) & 3) <= s.deg[1] && (sl >> 4) <= s.deg[2];
+        w_out[t0 * MS_WEIGHTS + e] = used ? w_s[pt * MS_WSTRIDE + sl] : 0.f;
+      }
+    }
+  }
   const int L = s.L, W = L + (with_xyz ? 3 : 0);
   const int total = npt * W;
   float* __restrict__ out = rows + t0 * W;

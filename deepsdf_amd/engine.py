@@ -195,6 +195,18 @@ class Engine:
                                                  self.spec.in_dim[0], _ptr(ws), ws.numel(), _stream()))
         return d_in
 
+    def module_input_grad(self, d_sdf, n):
+        """d_input [n, L+G] of module_backward for the last eval-mode module_forward, without the weight-gradient launches: the
+        gradient arena is not touched (dsdf_module_input_grad)."""
+        d = d_sdf.to(self.device, torch.float32).reshape(-1).contiguous()
+        if d.numel() != n:
+            raise ValueError(f"expected d_sdf with {n} values, got {d.numel()}")
+        ws = self.train_workspace(n, 0)
+        d_in = torch.empty(n, self.spec.in_dim[0], dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.dsdf_module_input_grad(C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(d), n, _ptr(d_in),
+                                                   self.spec.in_dim[0], _ptr(ws), ws.numel(), _stream()))
+        return d_in
+
     def module_jvp(self, tangent, n, training):
         """J . tangent at the point of the last module_forward: tangent [n, L+G] -> [n, 1] (dsdf_module_jvp)."""
         t = tangent.to(self.device, torch.float32)

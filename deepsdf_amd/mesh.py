@@ -9,6 +9,8 @@ convert_sdf_samples_to_ply :86-155) with every step on the GPU.
     file   write_ply        one header + two buffer writes, byte for byte what plyfile writes for the reference's dtypes
     tiled  microstructure_sdf_grid / create_mesh_microstructure / sdf_struct: a B-spline latent field over mirrored unit cells
                             (create_mesh_microstructure :157-342): rows and caps by csrc/msgrid.hpp around the same decode
+    diff   microstructure_mesh_diff / create_mesh_microstructure_diff (:346-454): d vertices / d control points assembled in closed
+                            form (csrc/msdiff.hpp) from one input-gradient pass over the band of grid points that carry a vertex
 
 There is no CPU path: the grid and the marching cubes need a HIP device (a grid handed in on the host is moved there).
 """
@@ -43,11 +45,12 @@ def _triple(x, what):
 
 
 # ---- marching cubes ---------------------------------------------------------------------------------------------------
-def marching_cubes(sdf_grid, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+def marching_cubes(sdf_grid, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), return_edges=False):
     """Surface {sdf == level} of a dense device grid sdf_grid [nx, ny, nz] (z fastest; 2 <= n <= 1024 per axis).
 
     Returns (verts [V, 3] fp32, faces [F, 3] int32) on the grid's device; an empty surface gives empty tensors.  Inside is
-    v < level (strictly); vertex of edge (p, a): origin + (p + t e_a) * spacing; order and orientation: include/dsdf.h."""
+    v < level (strictly); vertex of edge (p, a): origin + (p + t e_a) * spacing; order and orientation: include/dsdf.h.
+    return_edges: also (edge_point [V] int64, edge_axis [V] int32), the grid point p (linear index) and axis a of every vertex."""
     g = sdf_grid
     if not torch.is_tensor(g) or g.dim() != 3:
         raise ValueError("marching_cubes expects a 3-D tensor [nx, ny, nz]")
@@ -71,6 +74,11 @@ def marching_cubes(sdf_grid, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.
         faces = torch.empty(nf, 3, dtype=torch.int32, device=g.device)
         _lib.check(lib.dsdf_mc_emit(_ptr(g), nx, ny, nz, float(level), sp, org, nv, nf, _ptr(verts), _ptr(faces), _ptr(ws),
                                     ws.numel(), _stream()))
+        if return_edges:
+            edge_point = torch.empty(nv, dtype=torch.int64, device=g.device)
+            edge_axis = torch.empty(nv, dtype=torch.int32, device=g.device)
+            _lib.check(lib.dsdf_mc_edges(nx, ny, nz, nv, _ptr(edge_point), _ptr(edge_axis), _ptr(ws), ws.numel(), _stream()))
+            return verts, faces, edge_point, edge_axis
     return verts, faces
 
 
@@ -290,6 +298,28 @@ def ms_point_rows(field, tiling, points, inside_test=False, with_xyz=True):
     return rows
 
 
+def ms_rows_at(field, tiling, N, indices):
+    """Grid-mode rows at a list of padded-grid linear indices (device int64 tensor [n], any order): (rows [n, L + 3], bit for bit
+    ms_grid_rows at those indices; weights [n, 64], slot (k * 4 + j) * 4 + i; base [n] int32, first control point, -1 outside)."""
+    from .spline import as_field
+    field = as_field(field)
+    g, _ = _ms_grid(tiling, N)
+    idx = indices
+    if not torch.is_tensor(idx) or idx.dim() != 1 or idx.dtype != torch.int64 or idx.device.type != "cuda":
+        raise ValueError("ms_rows_at expects a device int64 tensor [n]")
+    idx = idx.contiguous()
+    n = idx.numel()
+    with torch.cuda.device(idx.device):
+        s, _keep = field.c_spline(idx.device)
+        rows = torch.empty(n, s.L + 3, dtype=torch.float32, device=idx.device)
+        weights = torch.empty(n, _lib.MS_WEIGHTS, dtype=torch.float32, device=idx.device)
+        base = torch.empty(n, dtype=torch.int32, device=idx.device)
+        if n > 0:
+            _lib.check(_lib.lib().dsdf_ms_rows_at(C.byref(s), C.byref(g), _ptr(idx), n, _ptr(rows), _ptr(weights), _ptr(base),
+                                                  _stream()))
+    return rows, weights, base
+
+
 def ms_apply_caps(sdf, N, start, end, cap_border_dict=None):
     """Caps in place on sdf [end - start] (contiguous fp32 device tensor), the values of points [start, end) of the padded grid."""
     g, _ = _ms_grid(1, N)
@@ -386,3 +416,166 @@ def sdf_struct(decoder, queries, tiling, latent_vec_interpolation, device=None):
         rows = ms_point_rows(latent_vec_interpolation, tiling, q, inside_test=False)
         y = dec.engine().decode(rows) if hip else dec(rows)
     return y.reshape(-1).detach().cpu().numpy()
+
+
+# ---- d vertices / d control points ------------------------------------------------------------------------------------------------
+# deep_sdf/mesh.py create_mesh_microstructure_diff :346-454.  A marching-cubes vertex is a closed-form function of the two grid values
+# of its edge, and a grid value depends on the control points through the row's latent columns only, so the Jacobian is assembled
+# from d sdf / d latent at the band of grid points that carry a vertex (one forward + one input-gradient pass over the band) and
+# the spline weights the row kernel holds (csrc/msdiff.hpp).  The reference's FlexiCubes variant is not implemented.
+def _free_device_memory(device):
+    return torch.cuda.mem_get_info(device)[0]
+
+
+class MicrostructureMeshDiff:
+    """A microstructure mesh with its derivative with respect to the spline's control points (microstructure_mesh_diff).
+
+    verts [V, 3] float64 and faces [F, 3] int32 (device) are create_mesh_microstructure's; edge_point [V] int64 / edge_axis [V] int32
+    name the padded-grid edge of every vertex.  Only coordinate edge_axis[v] of vertex v depends on the control points."""
+
+    def __init__(self, verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale):
+        self.verts, self.faces, self.edge_point, self.edge_axis = verts, faces, edge_point, edge_axis
+        self.grid, self.band, self.band_of = grid, band, band_of
+        self.G, self.weights, self.base, self.mask = G, weights, base, mask
+        self.n_control_points, self.latent_size = int(field.control_points.shape[0]), int(field.latent_size)
+        self._degrees = [int(d) for d in field.degrees]
+        self._n_cp = [int(n) for n in field.control_mesh_resolutions]
+        self._scale = scale
+
+    @property
+    def device(self):
+        return self.grid.device
+
+    def _structs(self):
+        m, b = _lib.DsdfMsdMesh(), _lib.DsdfMsdBand()
+        m.grid, m.edge_point, m.edge_axis, m.band_of = (t.data_ptr() for t in (self.grid, self.edge_point, self.edge_axis, self.band_of))
+        m.n_verts, m.level = self.verts.shape[0], 0.0
+        b.G, b.weights, b.base, b.mask = (t.data_ptr() for t in (self.G, self.weights, self.base, self.mask))
+        b.n_band, b.ld_g, b.L = self.G.shape[0], self.G.stride(0) if self.G.shape[0] > 0 else self.latent_size, self.latent_size
+        for a in range(3):
+            m.dims[a], m.scale[a] = self.grid.shape[a], self._scale[a]
+            b.degree[a], b.n_cp[a] = self._degrees[a], self._n_cp[a]
+        return m, b
+
+    def jacobian(self, dense=False):
+        """dense=False: (jac [V, ncp, L] fp32, axis [V] int32), jac[v] = d verts[v, axis[v]] / d control points.  dense=True: the
+        reference's [V, 3, ncp, L] with the two other coordinates' planes zero.  Raises MemoryError, stating the size, when the
+        array would not fit the free device memory."""
+        V, ncp, L = self.verts.shape[0], self.n_control_points, self.latent_size
+        shape = (V, 3, ncp, L) if dense else (V, ncp, L)
+        need = 4 * int(np.prod(shape, dtype=np.int64))
+        free = _free_device_memory(self.device)
+        if need > free:
+            raise MemoryError(f"the Jacobian {list(shape)} fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB), the device has {free} "
+                              f"bytes free: use vjp / jvp, or dense=False" + ("" if dense else " with a coarser grid"))
+        with torch.cuda.device(self.device):
+            jac = torch.empty(shape, dtype=torch.float32, device=self.device)
+            axis = torch.empty(V, dtype=torch.int32, device=self.device)
+            m, b = self._structs()
+            _lib.check(_lib.lib().dsdf_msd_jacobian(C.byref(m), C.byref(b), int(bool(dense)), _ptr(jac), _ptr(axis), _stream()))
+        return jac if dense else (jac, axis)
+
+    def vjp_plan(self):
+        """(scratch bytes, partial sums of the first stage) of vjp (dsdf_msd_vjp_workspace_bytes)."""
+        nbytes, parts = C.c_size_t(), C.c_int32()
+        _lib.check(_lib.lib().dsdf_msd_vjp_workspace_bytes(self.verts.shape[0], self.n_control_points, self.latent_size,
+                                                           C.byref(nbytes), C.byref(parts)))
+        return nbytes.value, parts.value
+
+    def vjp(self, grad_verts):
+        """grad_verts [V, 3] -> grad_cp [ncp, L] fp32 = sum_v grad_verts[v, a(v)] * J[v]: a fixed-order two-stage sum."""
+        gv = torch.as_tensor(grad_verts).to(self.device, torch.float32).contiguous()
+        V = self.verts.shape[0]
+        if gv.shape != (V, 3):
+            raise ValueError(f"grad_verts must be [{V}, 3], got {tuple(gv.shape)}")
+        with torch.cuda.device(self.device):
+            lib = _lib.lib()
+            ws = torch.empty(max(self.vjp_plan()[0], 256), dtype=torch.uint8, device=self.device)
+            out = torch.empty(self.n_control_points, self.latent_size, dtype=torch.float32, device=self.device)
+            m, b = self._structs()
+            _lib.check(lib.dsdf_msd_vjp(C.byref(m), C.byref(b), _ptr(gv), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+        return out
+
+    def jvp(self, d_cp):
+        """d_cp [ncp, L] -> d_verts [V, 3] fp32 (zero off each vertex's edge axis)."""
+        d = torch.as_tensor(d_cp).to(self.device, torch.float32).contiguous()
+        if d.shape != (self.n_control_points, self.latent_size):
+            raise ValueError(f"d_cp must be [{self.n_control_points}, {self.latent_size}], got {tuple(d.shape)}")
+        with torch.cuda.device(self.device):
+            out = torch.empty(self.verts.shape[0], 3, dtype=torch.float32, device=self.device)
+            m, b = self._structs()
+            _lib.check(_lib.lib().dsdf_msd_jvp(C.byref(m), C.byref(b), _ptr(d), _ptr(out), _stream()))
+        return out
+
+
+def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None):
+    """The mesh create_mesh_microstructure returns, on the device, with what its derivative needs (MicrostructureMeshDiff).
+
+    Forward: the raw grid, its capped copy and marching cubes, as create_mesh_microstructure.  Band: the sorted unique grid points
+    {p, p + e_a} of the vertices' edges.  Per chunk of max_batch band points: rows at the band indices (dsdf_ms_rows_at), the
+    decoder's forward and its input gradient with d_sdf = 1 (Engine.module_input_grad; torch.autograd.grad for any other
+    nn.Module).  mask = inside and capped value == raw value."""
+    from .spline import as_field
+    field = as_field(field)
+    tiling, n = _int_triple(tiling, "Tiling"), _int_triple(N, "Number of grid points")
+    dec = _unwrap(decoder)
+    hip = _is_hip_decoder(dec)
+    decoder.eval()
+    _, voxel_size = _ms_grid(tiling, n)
+    max_batch = int(max_batch)
+    raw = microstructure_sdf_grid(tiling, decoder, field, n, max_batch, cap_border_dict, device, apply_caps=False)
+    device = raw.device
+    dims = list(raw.shape)
+    npts = raw.numel()
+    L = int(field.latent_size)
+    with torch.cuda.device(device):
+        grid = raw.clone()
+        ms_apply_caps(grid.view(-1), n, 0, npts, cap_border_dict)
+        verts, faces, edge_point, edge_axis = marching_cubes(grid, 0.0, voxel_size, return_edges=True)
+        vs = torch.tensor(voxel_size, dtype=torch.float64, device=device)
+        verts = (verts.double() - vs) / 2
+        stride = torch.tensor([dims[1] * dims[2], dims[2], 1], dtype=torch.int64, device=device)
+        band = torch.unique(torch.cat([edge_point, edge_point + stride[edge_axis.long()]]))      # sorted
+        nb = band.numel()
+        band_of = torch.full((npts,), -1, dtype=torch.int32, device=device)
+        band_of[band] = torch.arange(nb, dtype=torch.int32, device=device)
+        G = torch.empty(nb, L, dtype=torch.float32, device=device)
+        weights = torch.empty(nb, _lib.MS_WEIGHTS, dtype=torch.float32, device=device)
+        base = torch.empty(nb, dtype=torch.int32, device=device)
+        if hip:
+            eng = dec.engine()
+            eng.materialize()
+        ones = torch.ones(min(nb, max_batch), dtype=torch.float32, device=device)
+        for b in range(0, nb, max_batch):
+            e = min(nb, b + max_batch)
+            rows, weights[b:e], base[b:e] = ms_rows_at(field, tiling, n, band[b:e])
+            if hip:
+                with torch.no_grad():
+                    eng.module_forward(rows, False)
+                    G[b:e] = eng.module_input_grad(ones[:e - b], e - b)[:, :L]
+            else:
+                x = rows.detach().requires_grad_(True)
+                with torch.enable_grad():
+                    y = dec(x)
+                    G[b:e] = torch.autograd.grad(y.sum(), x)[0][:, :L]
+        flat_raw, flat = raw.view(-1), grid.view(-1)
+        mask = ((base >= 0) & (flat[band] == flat_raw[band])).to(torch.uint8)
+    scale = [float(np.float32(v / 2)) for v in voxel_size]
+    return MicrostructureMeshDiff(verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale)
+
+
+def create_mesh_microstructure_diff(tiling, decoder, latent_vec_interpolation, N=256, max_batch=32 ** 3, offset=None, scale=None,
+                                    cap_border_dict=None, device=None, output_tetmesh=False, compute_derivatives=False):
+    """deep_sdf/mesh.py create_mesh_microstructure_diff: (verts [V, 3] float64, faces [F, 3] int32, jac) as numpy arrays, verts and
+    faces exactly create_mesh_microstructure's.  compute_derivatives: jac [V, 3, n_control_points, latent_dim] fp32 =
+    d verts / d control points of the marching-cubes mesh; otherwise jac = [] (as the reference).  offset and scale are accepted
+    and unused, as in the reference's return path."""
+    if output_tetmesh:
+        raise NotImplementedError("output_tetmesh needs kaolin's FlexiCubes, which this package does not carry: only the "
+                                  "marching-cubes surface and its derivative are implemented")
+    if not compute_derivatives:
+        verts, faces = create_mesh_microstructure(tiling, decoder, latent_vec_interpolation, "unused", N=N, max_batch=max_batch,
+                                                  cap_border_dict=cap_border_dict, device=device)
+        return verts, faces, []
+    d = microstructure_mesh_diff(tiling, decoder, latent_vec_interpolation, N, max_batch, cap_border_dict, device)
+    return d.verts.cpu().numpy(), d.faces.cpu().numpy(), d.jacobian(dense=True).cpu().numpy()

@@ -226,6 +226,12 @@ int dsdf_module_backward(const DsdfNet* net, const float* packed, const float* p
 int dsdf_module_jvp(const DsdfNet* net, const float* packed, const float* params, const float* tangent, int64_t ld_t,
                     int64_t n, int32_t training, const uint32_t* dropout_key /*[host] as dsdf_module_backward*/,
                     float* jvp_out, void* ws, size_t ws_bytes, void* stream);
+/* d_input [n, ld_din] of dsdf_module_backward for an eval-mode dsdf_module_forward (training == 0), with every weight-gradient
+ * launch skipped: no gradient arena is read or written.  The dX launches are those of dsdf_module_backward, so d_input is bit for
+ * bit what it returns.  One pass of this with d_sdf = 1 gives d sdf / d latent for every row, which replaces the
+ * latent_dim x n_control_points double-backward passes of deep_sdf/mesh.py:405-422 (inside :346-454). */
+int dsdf_module_input_grad(const DsdfNet* net, const float* packed, const float* params, const float* d_sdf, int64_t n,
+                           float* d_input, int64_t ld_din, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- training step ---------------------------------------------------------------------------------
  * dsdf_train_forward_backward = train_deep_sdf.py:509-533 for one chunk: max-norm renorm of the looked-up
@@ -326,6 +332,13 @@ int dsdf_mc_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float le
 /* verts [n_verts][3] fp32, faces [n_faces][3] int32 (vertex ids); spacing, origin [host] 3 floats each */
 int dsdf_mc_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing, const float* origin,
                  int64_t n_verts, int64_t n_faces, float* verts, int32_t* faces, void* ws, size_t ws_bytes, void* stream);
+/* The grid edge of every vertex (what deep_sdf/mesh.py:346-454 needs to differentiate the mesh): edge_point [n_verts] int64, the
+ * linear index of grid point p, edge_axis [n_verts] int32, the axis a of edge (p, p + e_a), in the vertex order of dsdf_mc_emit.
+ * Reads what dsdf_mc_count left in the workspace (the crossing masks and the per-workgroup offsets), so it is valid from
+ * dsdf_mc_count to the end of the workspace's life, before or after dsdf_mc_emit; n_verts is the counted total (fewer: the
+ * first n_verts).  n_verts == 0 launches nothing. */
+int dsdf_mc_edges(int32_t nx, int32_t ny, int32_t nz, int64_t n_verts, int64_t* edge_point, int32_t* edge_axis, void* ws,
+                  size_t ws_bytes, void* stream);
 /* [host] the compiled-in case table (generated by deepsdf_amd/mc_table.py): *width = entries per case (edge ids of its
  * triangles, -1 terminated); table (may be NULL) receives 256 * width int8. */
 int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width);
@@ -405,6 +418,59 @@ int dsdf_ms_rows(const DsdfMsSpline* spline, const DsdfMsGrid* grid, int64_t sta
                  int32_t inside_test, int32_t with_xyz, float* rows, void* stream);
 int dsdf_ms_caps(const DsdfMsGrid* grid, int64_t start, int64_t end, const DsdfMsCap* caps /*[host]*/, int32_t n_caps, float* sdf,
                  void* stream);
+
+/* Grid mode for a list of padded-grid linear indices (device int64 [n], any order, repeats allowed): rows [n][L + 3] are bit
+ * for bit those of dsdf_ms_rows' grid mode at these indices (the unfolded coordinate comes from the index with the single-rounded
+ * arithmetic above, never from a point list).  Also written, when not NULL: weights [n][64] fp32, the tensor-product basis weight
+ * of control point (first + (i, j, k)) in slot (k * 4 + j) * 4 + i, zero in unused slots, and base [n] int32, the linear index of
+ * the first control point (first parametric axis fastest), -1 for outside points (weights all zero).  An index outside the grid
+ * cannot be refused on the host: its row and weights are zero and its base is -1.  n == 0 launches nothing.
+ * Replaces the spline evaluation of deep_sdf/mesh.py:346-454 (create_mesh_microstructure_diff) on the band of grid points. */
+int dsdf_ms_rows_at(const DsdfMsSpline* spline, const DsdfMsGrid* grid, const int64_t* indices, int64_t n, float* rows,
+                    float* weights, int32_t* base, void* stream);
+
+/* ---- derivative of a microstructure mesh with respect to the spline's control points (csrc/msdiff.hpp) ---------------------
+ * deep_sdf/mesh.py:346-454 (create_mesh_microstructure_diff: latent_dim x n_control_points double-backward passes over the grid,
+ * :405-422), assembled in closed form.  Vertex v lies on edge (p, a) = (edge_point[v], edge_axis[v]) of the capped grid, between
+ * s0 = grid[p] and s1 = grid[p + e_a]; only coordinate a moves:
+ *   J[v, c, l] = scale[a] * sum_{k in {0, 1}} dt/ds_k * mask_k * G_k[l] * weight_k(c)
+ *   dt/ds0 = (level - s1) / (s1 - s0)^2,  dt/ds1 = -(level - s0) / (s1 - s0)^2  (fp32, from the two values marching cubes read)
+ * where k names the band row band_of[p] / band_of[p + e_a].  Band row r carries G [r][0 .. L) = d sdf / d latent at the row the
+ * forward decoded, the weights and base of dsdf_ms_rows_at, and mask (1: inside and the caps left the decoder's value).
+ * A vertex whose edge, band row or base is out of range gets zeros; nothing is read out of bounds for in-range arrays.
+ *   dsdf_msd_jacobian  jac [n_verts][ncp][L] and axis [n_verts] (may be NULL); full != 0: jac [n_verts][3][ncp][L], the two other
+ *                      coordinates' planes written as zeros (the reference's layout)
+ *   dsdf_msd_jvp       d_cp [ncp][L] -> d_verts [n_verts][3] (zeros off the edge axis)
+ *   dsdf_msd_vjp       grad_verts [n_verts][3] -> grad_cp [ncp][L]; two stages: ceil(n_verts / 512) partial sums in vertex order, then
+ *                      their sum in part order; ws from dsdf_msd_vjp_workspace_bytes (256-byte aligned, planner conventions:
+ *                      dsdf_debug_ws_redzone / dsdf_debug_ws_regions)
+ * No atomics; two identical calls give identical bytes.  Every argument error returns DSDF_E_INVALID before anything is launched. */
+typedef struct DsdfMsdMesh {
+  const float* grid;               /* device, capped sdf [dims[0]][dims[1]][dims[2]] */
+  const int64_t* edge_point;       /* device [n_verts] */
+  const int32_t* edge_axis;        /* device [n_verts] */
+  const int32_t* band_of;          /* device [grid points]: band row of a grid index, < 0: none */
+  int64_t n_verts;
+  int32_t dims[3];                 /* 2 .. 1024 */
+  float scale[3];                  /* voxel_size / 2 of the returned vertices */
+  float level;
+} DsdfMsdMesh;
+
+typedef struct DsdfMsdBand {
+  const float* G;                  /* device [n_band][ld_g] */
+  const float* weights;            /* device [n_band][64] */
+  const int32_t* base;             /* device [n_band] */
+  const uint8_t* mask;             /* device [n_band] */
+  int64_t n_band, ld_g;
+  int32_t degree[3], n_cp[3];
+  int32_t L;
+} DsdfMsdBand;
+
+int dsdf_msd_vjp_workspace_bytes(int64_t n_verts, int64_t n_control_points, int32_t L, size_t* bytes, int32_t* n_parts); /* [host] */
+int dsdf_msd_jacobian(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, int32_t full, float* jac, int32_t* axis, void* stream);
+int dsdf_msd_jvp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* d_cp, float* d_verts, void* stream);
+int dsdf_msd_vjp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* grad_verts, float* grad_cp, void* ws,
+                 size_t ws_bytes, void* stream);
 
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */

@@ -2,6 +2,7 @@
 against the same rows composed from torch ops.  One JSON line per (net, L) and one per L for the row kernel.
 
     python tools/ms_bench.py [--nets 8x512 4x64] [--L 16 256] [--N 256] [--tiling 4 4 4] [--max-batch 32768] [--reps 5]
+    python tools/ms_bench.py --diff [--nets 8x512 4x64] [--L 16] [--diff-N 64 256]
 
 mesh lines   rows_ms / decode_ms / caps_ms: HIP events around each step of every chunk, summed over the grid (the loop of
              microstructure_sdf_grid restated with events between the steps); mc_ms: events around marching_cubes; total_ms: host
@@ -11,6 +12,13 @@ row lines    dsdf_ms_rows on one range of --row-points grid points, 20 launches 
              must write ((L + 3) * 4 per point) over the median as GB/s, beside the measured HBM copy rate of MI355X (6.29 TB/s
              for reading and writing, MI355X_MICROARCH.md); and the same rows from torch ops on the device (index arithmetic, the
              fold, a degree-1 basis and a matmul for the spline, a concatenation), checked against the kernel's before timing.
+
+--diff       the derivative with respect to the control points (deepsdf_amd/mesh.py microstructure_mesh_diff) instead: one line per
+             (net, L, N) with the band size and the time of its steps -- rows at the band indices, forward + input gradient,
+             the dense assembly (with its store rate: V * ncp * L * 4 bytes over the median), the adjoint -- and, for comparison,
+             the reference's recipe on the same build: ncp * L calls of Decoder.jvp over the same band, chunk by chunk
+             (deep_sdf/mesh.py:405-422 runs that many double-backward passes, over the whole grid).  HIP events, median of --reps
+             after one warm-up, with min and max.  --diff-N gives the grid sizes.
 
 Nets: seeded (nn.Linear init) decoders of bench.py's NetworkSpecs with CodeLength L; the output bias is shifted so that the zero
 level set crosses the structure.  A (net, L) pair for which no net exists (4x64 with L = 256) is reported as skipped.  The field: degree 1, 2 x 2 x 2 seeded codes.
@@ -29,7 +37,8 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from deepsdf_amd.decoder import Decoder  # noqa: E402
-from deepsdf_amd.mesh import marching_cubes, microstructure_sdf_grid, ms_apply_caps, ms_grid_rows  # noqa: E402
+from deepsdf_amd.mesh import (marching_cubes, microstructure_mesh_diff, microstructure_sdf_grid, ms_apply_caps, ms_grid_rows,  # noqa: E402
+                              ms_rows_at)
 from deepsdf_amd.spline import BSplineField  # noqa: E402
 
 HBM_COPY_TBS = 6.29
@@ -122,6 +131,77 @@ def timed(fn, reps, warm):
     return statistics.median(ts), min(ts), max(ts)
 
 
+ROWS_KERNEL_TBS = 3.0            # what the row kernel reaches at L = 256 (profiles/ms_bench.log)
+
+
+def diff_bench(args, dev):
+    """--diff: the steps of microstructure_mesh_diff and the reference's recipe, per (net, L, N)."""
+    tiling = args.tiling
+    for L in args.L:
+        field = make_field(L)
+        ncp = field.control_points.shape[0]
+        for name in args.nets:
+            spec = bench.NETWORKS[name]["net"]
+            if any(spec["dims"][l - 1] <= L + 3 for l in spec["latent_in"]):
+                print(json.dumps(dict(what="diff", net=name, L=L, skipped=f"no {name} net exists for L = {L}")), flush=True)
+                continue
+            dec = make_decoder(name, L, field, tiling)
+            eng = dec.engine()
+            for N in args.diff_N:
+                d = microstructure_mesh_diff(tiling, dec, field, N, args.max_batch)
+                nb, V = d.band.numel(), d.verts.shape[0]
+                ones = torch.ones(min(nb, args.max_batch), device="cuda")
+
+                def band_steps():
+                    marks = []
+                    with torch.no_grad():
+                        for b in range(0, nb, args.max_batch):
+                            e = min(nb, b + args.max_batch)
+                            m = [ev() for _ in range(3)]
+                            m[0].record()
+                            rows, _, _ = ms_rows_at(field, tiling, N, d.band[b:e])
+                            m[1].record()
+                            eng.module_forward(rows, False)
+                            eng.module_input_grad(ones[:e - b], e - b)
+                            m[2].record()
+                            marks.append(m)
+                    torch.cuda.synchronize()
+                    return tuple(sum(m[i].elapsed_time(m[i + 1]) for m in marks) for i in range(2))
+
+                def reference_recipe():
+                    with torch.no_grad():
+                        for b in range(0, nb, args.max_batch):
+                            e = min(nb, b + args.max_batch)
+                            rows, w, base = ms_rows_at(field, tiling, N, d.band[b:e])
+                            tangent = torch.zeros_like(rows)
+                            for c in range(ncp):           # degree 1, 2 x 2 x 2: slot (k * 4 + j) * 4 + i of control point c
+                                wc = w[:, ((c >> 2) * 4 + ((c >> 1) & 1)) * 4 + (c & 1)]
+                                for l in range(L):
+                                    tangent.zero_()
+                                    tangent[:, l] = wc
+                                    dec.jvp(rows, tangent)
+
+                band_steps()
+                st = [band_steps() for _ in range(args.reps)]
+                gw = torch.randn(V, 3, device="cuda")
+                dense = timed(lambda: d.jacobian(), args.reps, 1)
+                vjp = timed(lambda: d.vjp(gw), args.reps, 1)
+                jvp = timed(lambda: d.jvp(d.G.new_ones(ncp, L)), args.reps, 1)
+                ref = timed(reference_recipe, args.reps, 1)
+                rows_ms, grad_ms = (statistics.median(s[i] for s in st) for i in range(2))
+                gb = V * ncp * L * 4 / 1e9
+                ours = rows_ms + grad_ms + dense[0]
+                print(json.dumps(dict(what="diff", net=name, L=L, N=N, tiling=tiling, max_batch=args.max_batch, V=V, band=nb,
+                                      grid_points=(N + 2) ** 3, n_control_points=ncp, rows_ms=round(rows_ms, 3),
+                                      forward_input_grad_ms=round(grad_ms, 3), dense_ms=[round(x, 3) for x in dense],
+                                      dense_store_gbs=round(gb / dense[0] * 1e3, 1),
+                                      dense_share_of_row_kernel_rate=round(gb / dense[0] / ROWS_KERNEL_TBS, 3),
+                                      vjp_ms=[round(x, 3) for x in vjp], jvp_ms=[round(x, 3) for x in jvp],
+                                      reference_recipe_ms=[round(x, 1) for x in ref], reference_jvp_calls=ncp * L,
+                                      reference_over_ours=round(ref[0] / ours, 1), device=dev)), flush=True)
+                del d
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nets", nargs="+", default=["8x512", "4x64"], choices=sorted(bench.NETWORKS))
@@ -131,10 +211,14 @@ def main():
     ap.add_argument("--max-batch", type=int, default=32 ** 3, help="chunk (create_mesh_microstructure's max_batch)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--row-points", type=int, default=1 << 21, help="points of the row-kernel measurement")
+    ap.add_argument("--diff", action="store_true", help="time the derivative with respect to the control points instead")
+    ap.add_argument("--diff-N", nargs="+", type=int, default=[64, 256], help="grid sizes of --diff")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ms_bench.py needs an AMD GPU: nothing here can be timed on a CPU")
     dev = torch.cuda.get_device_name(0)
+    if args.diff:
+        return diff_bench(args, dev)
     N, tiling = args.N, args.tiling
     for L in args.L:
         field = make_field(L)
