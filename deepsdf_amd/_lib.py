@@ -87,6 +87,7 @@ class DsdfWsRegion(C.Structure):      # debug only: one row of dsdf_debug_ws_reg
 WS_MAX_REGIONS = 192
 WS_MAX_REDZONE = 4096
 WS_PLAN_TRAIN, WS_PLAN_DECODE, WS_PLAN_DECODE_LATENT = 0, 1, 2
+MEAN_WS_BYTES = 8192
 
 
 class DsdfError(RuntimeError):
@@ -147,6 +148,12 @@ PROTOTYPES = {
     "dsdf_msd_jacobian": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _I32, _P, _P, _P],
     "dsdf_msd_jvp": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P],
     "dsdf_msd_vjp": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P, _SZ, _P],
+    "dsdf_nn_plan": [_I64, _I64, C.POINTER(_SZ), C.POINTER(_I32)],
+    "dsdf_nn_query": [_P, _I64, _P, _I64, _P, _P, _P, _SZ, _P],
+    "dsdf_mean_f64": [_P, _I64, _P, _P, _SZ, _P],
+    "dsdf_surf_plan": [_I64, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_I32)],
+    "dsdf_surf_prepare": [_P, _I64, _P, _I64, _P, _SZ, C.POINTER(C.c_double), _P],
+    "dsdf_surf_sample": [_P, _I64, _P, _I64, _P, _SZ, _I64, C.c_uint64, C.c_uint64, _F, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -23,6 +23,7 @@
 #include "meshsdf.hpp"
 #include "msgrid.hpp"
 #include "msdiff.hpp"
+#include "pointset.hpp"
 
 using namespace dsdf;
 
@@ -2236,6 +2237,182 @@ int dsdf_msdf_query(const void* tri, int64_t n_faces, const float* queries, int6
   hipLaunchKernelGGL(msdf_combine_kernel, dim3((unsigned)P.qblocks), dim3(MSDF_BLOCK), 0, st, t, queries, nq, P.n_splits,
                      (int)dist, (int)wind, part, o);
   LAUNCH_OK("msdf_combine_kernel");
+  return 0;
+}
+
+// ---- point sets (pointset.hpp) -------------------------------------------------------------------------
+namespace {
+struct NnPlan {
+  int32_t n_splits, chunk;
+  int64_t tiles;
+  size_t ws;
+};
+
+int nn_plan(int64_t nq, int64_t nr, NnPlan* P, WsTable* rec = nullptr) {
+  if (nr <= 0) return fail(DSDF_E_INVALID, "nearest neighbour: %lld reference points (need at least one)", (long long)nr);
+  if (nq < 0) return fail(DSDF_E_INVALID, "nearest neighbour: %lld queries", (long long)nq);
+  if (nr > INT32_MAX || nq > INT32_MAX)
+    return fail(DSDF_E_INVALID, "nearest neighbour: %lld queries / %lld reference points (the kernels index in int32: at most %d)",
+                (long long)nq, (long long)nr, INT32_MAX);
+  P->tiles = (nq + NN_TILE - 1) / NN_TILE;
+  int64_t ns = 1;
+  if (P->tiles > 0 && P->tiles < NN_TARGET_WG) {
+    ns = (NN_TARGET_WG + P->tiles - 1) / P->tiles;
+    ns = std::min<int64_t>(ns, std::min<int64_t>(nr / NN_MIN_SPLIT_REFS, NN_MAX_SPLITS));
+    ns = std::max<int64_t>(ns, 1);
+  }
+  P->n_splits = (int32_t)ns;
+  P->chunk = (int32_t)((nr + ns - 1) / ns);
+  const size_t part = ns > 1 ? (size_t)ns * (size_t)nq * 8 : 0;          // d2 and index per (split, query); one split writes the outputs
+  P->ws = part ? part + g_redzone.load(std::memory_order_relaxed) : 0;
+  if (rec) {
+    rec->reset();
+    if (part) rec->add("nn_partials", -1, 0, part);
+    rec->total = P->ws;
+  }
+  return 0;
+}
+
+struct SurfPlan {
+  int64_t tiles;
+  size_t tile_off, area_off, bytes;
+};
+
+int surf_plan(int64_t nf, SurfPlan* P) {
+  if (nf <= 0) return fail(DSDF_E_INVALID, "surface sampling: %lld faces (need at least one)", (long long)nf);
+  if (nf > INT32_MAX) return fail(DSDF_E_INVALID, "surface sampling: %lld faces (at most %d)", (long long)nf, INT32_MAX);
+  P->tiles = (nf + SURF_TILE - 1) / SURF_TILE;
+  P->tile_off = (size_t)rup(nf * 8, 256);
+  P->area_off = P->tile_off + (size_t)rup(P->tiles * 8, 256);
+  P->bytes = P->area_off + (size_t)rup(nf * 4, 256);
+  return 0;
+}
+
+SurfBuf surf_buf(void* surf, const SurfPlan& P) {
+  SurfBuf b;
+  b.cdf = (double*)surf;
+  b.tile = (double*)((char*)surf + P.tile_off);
+  b.area = (float*)((char*)surf + P.area_off);
+  return b;
+}
+}  // namespace
+
+int dsdf_nn_plan(int64_t n_queries, int64_t n_refs, size_t* ws_bytes, int32_t* n_splits) {
+  NnPlan P;
+  TRY(nn_plan(n_queries, n_refs, &P, &t_last_plan));
+  if (!ws_bytes && !n_splits) return fail(DSDF_E_INVALID, "nearest neighbour plan: every output is NULL");
+  if (ws_bytes) *ws_bytes = P.ws;
+  if (n_splits) *n_splits = P.n_splits;
+  return 0;
+}
+
+int dsdf_nn_query(const float* queries, int64_t n_queries, const float* refs, int64_t n_refs, float* sqr_dist, int32_t* index,
+                  void* ws, size_t ws_bytes, void* stream) {
+  NnPlan P;
+  TRY(nn_plan(n_queries, n_refs, &P, &t_last_plan));
+  if (!sqr_dist && !index) return fail(DSDF_E_INVALID, "nearest neighbour: every output is NULL");
+  if (n_queries == 0) return 0;
+  if (!queries || !refs) return fail(DSDF_E_INVALID, "nearest neighbour: NULL queries or reference points");
+  if (P.ws && !ws) return fail(DSDF_E_INVALID, "nearest neighbour: NULL workspace");
+  if (ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "nearest neighbour: workspace %zu < %zu bytes", ws_bytes, P.ws);
+  if (P.ws && ((uintptr_t)ws & 3) != 0) return fail(DSDF_E_INVALID, "nearest neighbour: workspace not 4-byte aligned");
+  const int nq = (int)n_queries, nr = (int)n_refs;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)P.tiles, (unsigned)P.n_splits);
+  if (P.n_splits == 1) {
+    hipLaunchKernelGGL((nn_query_kernel<NN_QPL, NN_UNROLL>), grid, dim3(NN_BLOCK), 0, st, refs, nr, P.chunk, queries, nq, sqr_dist, index);
+    LAUNCH_OK("nn_query_kernel");
+    return 0;
+  }
+  float* pd2 = (float*)ws;
+  int32_t* pidx = (int32_t*)((char*)ws + (size_t)P.n_splits * (size_t)n_queries * 4);
+  hipLaunchKernelGGL((nn_query_kernel<NN_QPL, NN_UNROLL>), grid, dim3(NN_BLOCK), 0, st, refs, nr, P.chunk, queries, nq, pd2, pidx);
+  LAUNCH_OK("nn_query_kernel");
+  hipLaunchKernelGGL(nn_combine_kernel, dim3((unsigned)((n_queries + NN_BLOCK - 1) / NN_BLOCK)), dim3(NN_BLOCK), 0, st,
+                     (const float*)pd2, (const int32_t*)pidx, nq, P.n_splits, sqr_dist, index);
+  LAUNCH_OK("nn_combine_kernel");
+  return 0;
+}
+
+int dsdf_mean_f64(const float* x, int64_t n, double* mean, void* ws, size_t ws_bytes, void* stream) {
+  static_assert(DSDF_MEAN_WS_BYTES == MEAN_MAX_BLOCKS * 8, "the header's workspace size is the partial-sum table");
+  if (n <= 0) return fail(DSDF_E_INVALID, "mean: %lld values (need at least one)", (long long)n);
+  if (!x || !mean || !ws) return fail(DSDF_E_INVALID, "mean: NULL values, result or workspace");
+  if (ws_bytes < DSDF_MEAN_WS_BYTES) return fail(DSDF_E_WORKSPACE, "mean: workspace %zu < %d bytes", ws_bytes, DSDF_MEAN_WS_BYTES);
+  if (((uintptr_t)ws & 7) != 0 || ((uintptr_t)mean & 7) != 0) return fail(DSDF_E_INVALID, "mean: workspace or result not 8-byte aligned");
+  const int64_t blocks = std::min<int64_t>((n + MEAN_MIN_SLICE - 1) / MEAN_MIN_SLICE, MEAN_MAX_BLOCKS);
+  const int64_t slice = (n + blocks - 1) / blocks;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mean_partial_kernel, dim3((unsigned)blocks), dim3(MEAN_BLOCK), 0, st, x, n, slice, (double*)ws);
+  LAUNCH_OK("mean_partial_kernel");
+  hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(MEAN_BLOCK), 0, st, (const double*)ws, (int)blocks, n, mean);
+  LAUNCH_OK("mean_final_kernel");
+  return 0;
+}
+
+int dsdf_surf_plan(int64_t n_faces, size_t* surf_bytes, size_t* area_offset, int32_t* n_tiles) {
+  SurfPlan P;
+  TRY(surf_plan(n_faces, &P));
+  if (!surf_bytes && !area_offset && !n_tiles) return fail(DSDF_E_INVALID, "surface plan: every output is NULL");
+  if (surf_bytes) *surf_bytes = P.bytes;
+  if (area_offset) *area_offset = P.area_off;
+  if (n_tiles) *n_tiles = (int32_t)P.tiles;
+  return 0;
+}
+
+namespace {
+int surf_args(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const void* surf, size_t surf_bytes,
+              SurfPlan* P) {
+  TRY(surf_plan(n_faces, P));
+  if (n_verts <= 0 || n_verts > INT32_MAX)
+    return fail(DSDF_E_INVALID, "surface sampling: %lld vertices (need 1 .. %d)", (long long)n_verts, INT32_MAX);
+  if (!verts || !faces || !surf) return fail(DSDF_E_INVALID, "surface sampling: NULL verts, faces or surf buffer");
+  if (surf_bytes < P->bytes) return fail(DSDF_E_WORKSPACE, "surface sampling: surf buffer %zu < %zu bytes", surf_bytes, P->bytes);
+  if (((uintptr_t)surf & 7) != 0) return fail(DSDF_E_INVALID, "surface sampling: surf buffer not 8-byte aligned");
+  return 0;
+}
+}  // namespace
+
+int dsdf_surf_prepare(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* surf, size_t surf_bytes,
+                      double* total_area, void* stream) {
+  SurfPlan P;
+  TRY(surf_args(verts, n_verts, faces, n_faces, surf, surf_bytes, &P));
+  const SurfBuf b = surf_buf(surf, P);
+  const int nf = (int)n_faces;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(surf_area_kernel, dim3((unsigned)((n_faces + SURF_BLOCK - 1) / SURF_BLOCK)), dim3(SURF_BLOCK), 0, st, verts,
+                     (int)n_verts, faces, nf, b.area);
+  LAUNCH_OK("surf_area_kernel");
+  hipLaunchKernelGGL(surf_scan_tile_kernel<false>, dim3((unsigned)P.tiles), dim3(SURF_BLOCK), 0, st, b, nf);
+  LAUNCH_OK("surf_scan_tile_kernel<false>");
+  hipLaunchKernelGGL(surf_scan_tiles_kernel, dim3(1), dim3(SURF_BLOCK), 0, st, b.tile, (int)P.tiles);
+  LAUNCH_OK("surf_scan_tiles_kernel");
+  hipLaunchKernelGGL(surf_scan_tile_kernel<true>, dim3((unsigned)P.tiles), dim3(SURF_BLOCK), 0, st, b, nf);
+  LAUNCH_OK("surf_scan_tile_kernel<true>");
+  double total = 0.0;
+  HIP_OK(hipMemcpyAsync(&total, b.cdf + (n_faces - 1), sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (total_area) *total_area = total;
+  if (!(total > 0.0) || !std::isfinite(total))
+    return fail(DSDF_E_INVALID, "surface sampling: the mesh's total area is %g (need a finite positive area)", total);
+  return 0;
+}
+
+int dsdf_surf_sample(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const void* surf, size_t surf_bytes,
+                     int64_t n, uint64_t offset, uint64_t seed, float std_dev, float* points, int32_t* face, float* bary,
+                     void* stream) {
+  SurfPlan P;
+  TRY(surf_args(verts, n_verts, faces, n_faces, surf, surf_bytes, &P));
+  if (n < 0 || n > INT32_MAX) return fail(DSDF_E_INVALID, "surface sampling: %lld samples (0 .. %d per call)", (long long)n, INT32_MAX);
+  if (offset > UINT64_MAX - (uint64_t)n) return fail(DSDF_E_INVALID, "surface sampling: offset + n exceeds 2^64 - 1");
+  if (!(std_dev >= 0.f) || !std::isfinite(std_dev)) return fail(DSDF_E_INVALID, "surface sampling: std must be finite and >= 0");
+  if (n == 0) return 0;
+  if (!points) return fail(DSDF_E_INVALID, "surface sampling: NULL points");
+  SurfOut o;
+  o.points = points; o.face = face; o.bary = bary;
+  hipLaunchKernelGGL(surf_sample_kernel, dim3((unsigned)((n + SURF_BLOCK - 1) / SURF_BLOCK)), dim3(SURF_BLOCK), 0,
+                     (hipStream_t)stream, verts, (int)n_verts, faces, (int)n_faces, (const double*)surf, n, offset, seed, std_dev, o);
+  LAUNCH_OK("surf_sample_kernel");
   return 0;
 }
 

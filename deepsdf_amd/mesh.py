@@ -7,6 +7,7 @@ convert_sdf_samples_to_ply :86-155) with every step on the GPU.
     mesh   marching_cubes   HIP marching cubes (csrc/mcubes.hpp, dsdf_mc_count / dsdf_mc_emit): one host sync per mesh, to
                             read the two totals and allocate exact outputs
     file   write_ply        one header + two buffer writes, byte for byte what plyfile writes for the reference's dtypes
+           write_points_ply the vertex-only variant (SurfaceSamples)
     tiled  microstructure_sdf_grid / create_mesh_microstructure / sdf_struct: a B-spline latent field over mirrored unit cells
                             (create_mesh_microstructure :157-342): rows and caps by csrc/msgrid.hpp around the same decode
     diff   microstructure_mesh_diff / create_mesh_microstructure_diff (:346-454): d vertices / d control points assembled in closed
@@ -113,6 +114,16 @@ def write_ply(path, verts, faces):
         fh.write(ply_header(v.shape[0], f.shape[0]))
         fh.write(v.tobytes())
         fh.write(packed.tobytes())
+
+
+def write_points_ply(path, points):
+    """Vertex-only binary little-endian PLY (x, y, z f4): the SurfaceSamples files.  points [n, 3]: a tensor or an array."""
+    v = points.detach().cpu().numpy() if torch.is_tensor(points) else np.asarray(points)
+    v = np.ascontiguousarray(v.reshape(-1, 3), dtype="<f4")
+    with open(path, "wb") as fh:
+        fh.write(("ply\nformat binary_little_endian 1.0\n"
+                  f"element vertex {v.shape[0]}\nproperty float x\nproperty float y\nproperty float z\nend_header\n").encode("ascii"))
+        fh.write(v.tobytes())
 
 
 # ---- grid -------------------------------------------------------------------------------------------------------------

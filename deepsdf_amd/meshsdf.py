@@ -6,7 +6,9 @@ and its sign from an embree ray test (``contains_points``: inside is negative). 
 and the generalized winding number, whose parity (``floor(|w| + 0.5)`` odd) is the inside test.
 
     read_mesh                     PLY (ascii, binary either endianness) and OBJ -> (V float64 [n, 3], F int64 [m, 3])
-    TriangleMesh                  validates and uploads a mesh once, then answers .sdf / .squared_distance / .winding_number
+    read_points                   the vertices of a PLY / OBJ file, faces or none (SurfaceSamples files) -> float64 [n, 3]
+    TriangleMesh                  validates and uploads a mesh once, then answers .sdf / .squared_distance / .winding_number,
+                                  and draws area-weighted surface samples (.sample_surface, .area; csrc/pointset.hpp)
     point_mesh_squared_distance   igl's argument order and return shapes (sqrD [n], I [n], C [n, 3])
     winding_number                igl's argument order (V, F, O) -> w [n]
 
@@ -218,6 +220,11 @@ def read_mesh(path):
     return V, F
 
 
+def read_points(path):
+    """Vertices float64 [n, 3] of a .ply or .obj file; a face element is read and ignored, a vertex-only PLY is fine."""
+    return read_mesh(path)[0]
+
+
 # ---- device API -------------------------------------------------------------------------------------------------------------
 def _as_host_or_device(x, what, device, cols=3, dtype=torch.float32):
     """(tensor on `device`, returns_numpy, return device)."""
@@ -267,6 +274,7 @@ class TriangleMesh:
             self.tri = torch.empty(tb.value, dtype=torch.uint8, device=device)
             _lib.check(lib.dsdf_msdf_prepare(_ptr(self.V), self.V.shape[0], _ptr(self.F), self.n_faces, _ptr(self.tri),
                                              self.tri.numel(), _stream()))
+        self._surf = None              # (buffer, total area, area offset): dsdf_surf_prepare, on first use
 
     @property
     def vertices(self):
@@ -320,6 +328,51 @@ class TriangleMesh:
     def winding_number(self, queries):
         """Generalized winding number [n]: sum of solid angles / 4 pi."""
         return self._query(queries, wind=True)["w"]
+
+    # ---- surface samples (dsdf_surf_*) ----
+    def _surface(self):
+        if self._surf is None:
+            lib = _lib.lib()
+            sb, ao, total = C.c_size_t(), C.c_size_t(), C.c_double()
+            _lib.check(lib.dsdf_surf_plan(self.n_faces, C.byref(sb), C.byref(ao), None))
+            with torch.cuda.device(self.device):
+                buf = torch.empty(sb.value, dtype=torch.uint8, device=self.device)
+                rc = lib.dsdf_surf_prepare(_ptr(self.V), self.V.shape[0], _ptr(self.F), self.n_faces, _ptr(buf), buf.numel(),
+                                           C.byref(total), _stream())
+            if rc != 0 and total.value == 0.0:
+                raise ValueError("the mesh has no surface area: nothing to sample")
+            _lib.check(rc)
+            self._surf = (buf, total.value, ao.value)
+        return self._surf
+
+    def area(self):
+        """Total surface area: the fp64 sum of the fp32 face areas."""
+        return self._surface()[1]
+
+    def face_areas(self):
+        """(area fp32 [m], cdf fp64 [m]) as the sampler uses them: per-face areas and their inclusive prefix sums."""
+        buf, _, ao = self._surface()
+        return buf[ao:ao + 4 * self.n_faces].view(torch.float32), buf[:8 * self.n_faces].view(torch.float64)
+
+    def sample_surface(self, count, seed=0, std=0.0, return_bary=False, offset=0):
+        """count points drawn uniformly from the surface: (points fp32 [count, 3], face int32 [count]) and, with return_bary,
+        bary fp32 [count, 2] (p = a + u ab + v ac), as tensors on the mesh's device.  Sample i depends on (seed, offset + i)
+        only, so draws at consecutive offsets continue one another.  std > 0 adds N(0, std^2) noise per coordinate."""
+        count, seed, offset = int(count), int(seed), int(offset)
+        if count < 0 or count > INT32_MAX:
+            raise ValueError("count must lie in [0, 2^31 - 1]")
+        if not 0 <= seed < 2 ** 64 or not 0 <= offset <= 2 ** 64 - 1 - count:
+            raise ValueError("seed and offset must be unsigned 64-bit integers")
+        if not (std >= 0.0 and np.isfinite(std)):
+            raise ValueError("std must be finite and >= 0")
+        buf, _, _ = self._surface()
+        with torch.cuda.device(self.device):
+            pts = torch.empty(count, 3, dtype=torch.float32, device=self.device)
+            face = torch.empty(count, dtype=torch.int32, device=self.device)
+            bary = torch.empty(count, 2, dtype=torch.float32, device=self.device) if return_bary else None
+            _lib.check(_lib.lib().dsdf_surf_sample(_ptr(self.V), self.V.shape[0], _ptr(self.F), self.n_faces, _ptr(buf), buf.numel(),
+                                                   count, offset, seed, float(std), _ptr(pts), _ptr(face), _ptr(bary), _stream()))
+        return (pts, face, bary) if return_bary else (pts, face)
 
 
 def _mesh_device(*xs):

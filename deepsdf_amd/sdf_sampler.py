@@ -1,7 +1,7 @@
 """Training data from SDFs: the API of the reference's ``sdf_sampler/sdf_sampler.py`` with the mesh distance on the GPU.
 
 Same names, signatures and semantics as the reference module (analytic helpers :21-69, ``RandomSampleSDF`` :81-107,
-``SDFSampler.sample_sdfs`` / ``write_json`` :109-157, ``random_sample_sdf`` :187-199, ``SDFfromMesh`` :201-242).
+``SDFSampler.sample_sdfs`` / ``write_json`` :109-157, ``noisy_sample`` :164-167, ``random_sample_sdf`` :187-199, ``SDFfromMesh`` :201-242).
 ``random_sample_sdf`` makes the same ``np.random`` calls in the same order, so a seeded run draws the reference's points bit
 for bit, and ``sample_sdfs`` writes the same files (``<class>_<10000 + i>.npz`` with float64 ``pos`` / ``neg`` rows).
 
@@ -223,6 +223,15 @@ def _mesh_arrays(mesh):
     if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
         return mesh
     raise TypeError("SDFfromMesh needs an object with .vertices / .faces, a (V, F) pair or a .ply / .obj path")
+
+
+def noisy_sample(mesh, std, count, seed=0):
+    """count points of the mesh's surface plus N(0, std^2) noise per coordinate, float64 [count, 3] -- the reference's helper of
+    this name (:164-167: trimesh's ``mesh.sample`` plus ``np.random.normal``), drawn on the GPU from `seed` instead of numpy's
+    global state.  mesh: what SDFfromMesh takes, or a deepsdf_amd.meshsdf.TriangleMesh."""
+    from .meshsdf import TriangleMesh
+    tm = mesh if isinstance(mesh, TriangleMesh) else TriangleMesh(*_mesh_arrays(mesh))
+    return tm.sample_surface(int(count), seed=seed, std=float(std))[0].cpu().numpy().astype(np.float64)
 
 
 class SDFfromMesh(SDFBase):

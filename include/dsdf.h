@@ -368,6 +368,60 @@ int dsdf_msdf_prepare(const float* verts, int64_t n_verts, const int32_t* faces,
 int dsdf_msdf_query(const void* tri, int64_t n_faces, const float* queries, int64_t n_queries, float* sdf, float* sqr_dist,
                     int32_t* face, float* closest, float* winding, int32_t flip_sign, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- point sets: the kernels behind deep_sdf/metrics/chamfer.py (scipy KDTree query, trimesh.sample.sample_surface) and the
+ * surface half of sdf_sampler.py noisy_sample, on the device (csrc/pointset.hpp) ------------------------------------------------
+ * Nearest neighbour, brute force.  For every query q of queries [n_queries][3] against refs [n_refs][3], both fp32:
+ *   sqr_dist  min over j of fmaf(dz, dz, fmaf(dy, dy, dx * dx)), (dx, dy, dz) = q - refs[j] formed explicitly (three rounded
+ *             subtractions, one rounded product, two fused multiply-adds)
+ *   index     the LOWEST j attaining the minimum.  A pair whose value is NaN is never chosen (the test is value < best); a query
+ *             with no comparable pair (every value NaN or +inf) reports sqr_dist = +inf, index = 0.
+ * sqr_dist [n_queries] fp32, index [n_queries] int32; either may be NULL, not both.
+ * Split rule (n_splits): the query pass runs ceil(n_queries / 1024) workgroups of 256 lanes with 4 queries per lane; when they
+ * are fewer than 2048 the reference set is cut into n_splits = min(ceil(2048 / that), floor(n_refs / 1024), 64) contiguous pieces
+ * (at least 1), one workgroup per (query block, piece), combined in piece order with strict < and without atomics: neither
+ * output depends on the split.  Two identical calls give identical bytes.  One piece needs no workspace (ws_bytes = 0, ws may be
+ * NULL); more need n_splits * n_queries * 8 bytes.
+ * n_queries and n_refs must fit int32.  n_queries == 0 is valid and launches nothing; n_refs == 0 is DSDF_E_INVALID. */
+int dsdf_nn_plan(int64_t n_queries, int64_t n_refs, size_t* ws_bytes, int32_t* n_splits);               /* [host] */
+int dsdf_nn_query(const float* queries, int64_t n_queries, const float* refs, int64_t n_refs, float* sqr_dist, int32_t* index,
+                  void* ws, size_t ws_bytes, void* stream);
+
+/* Mean of n fp32 values as one fp64 on the device (*mean, 8-byte aligned): every value converted to fp64, summed in fp64 by
+ * min(ceil(n / 4096), 1024) workgroups over contiguous slices (lane sums in stride order, a fixed tree per workgroup), then the
+ * partial sums by one workgroup in the same way, divided by n.  No atomics: two calls give identical bits.  ws is a fixed
+ * scratch of DSDF_MEAN_WS_BYTES (8-byte aligned; there is no planner and the debug red zones do not apply).  n == 0 is
+ * DSDF_E_INVALID. */
+#define DSDF_MEAN_WS_BYTES 8192
+int dsdf_mean_f64(const float* x, int64_t n, double* mean, void* ws, size_t ws_bytes, void* stream);
+
+/* Area-weighted sampling of a triangle mesh's surface (verts [n_verts][3] fp32, faces [n_faces][3] int32 as for dsdf_msdf_prepare).
+ * dsdf_surf_prepare, once per mesh, fills the `surf` buffer (dsdf_surf_plan: *surf_bytes; 8-byte aligned):
+ *   area  [n_faces] fp32 at byte *area_offset: 0.5 * sqrt(n.n), n = ab x ac, ab = b - a, ac = c - a, every product, difference and
+ *         sum rounded to fp32 on its own (n.n = (nx nx + ny ny) + nz nz)
+ *   cdf   [n_faces] fp64 at byte 0: the inclusive prefix sums of area, formed in fp64 by a fixed three-pass scan over tiles of
+ *         1024 faces (*n_tiles = ceil(n_faces / 1024)) -- deterministic, and within n_faces * 2^-53 * total of the exact sums;
+ *         total = cdf[n_faces - 1]
+ * It waits for the stream, returns the total in *total_area ([host], may be NULL) and fails with DSDF_E_INVALID when the total
+ * is 0 or not finite; dsdf_surf_sample is defined only on a buffer it accepted.
+ * Sample i = offset + t, t in [0, n), with the 64-bit seed:
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (lo32(i), 0, hi32(i), 0), key = (lo32(seed), hi32(seed)))
+ *   r = fp64(w0 * 2^32 + w3) * 2^-64 (the integer rounded to nearest), x = r * total rounded to fp64
+ *   face = the first f with cdf[f] > x, so a face that adds no area is never chosen; when there is none (r rounded to 1): the
+ *          first f with cdf[f] = total, the last face that added area
+ *   u = (w1 >> 8) * 2^-24, v = (w2 >> 8) * 2^-24 in fp32; if the fp32 sum u + v > 1: u = 1 - u, v = 1 - v
+ *   p = fmaf(ac, v, fmaf(ab, u, a)) per coordinate, the nesting of the mesh SDF's closest point
+ * std > 0 adds std * N(0, 1) per coordinate (fmaf(std, g, p)): (g0, g1, g2, g3) = Philox4x32-10 with counter (lo32(i), 1, hi32(i),
+ * 0), Box-Muller in fp32: x = sqrt(-2 log(((g0 >> 8) + 1) 2^-24)) cos(2 pi (g1 >> 8) 2^-24), y = the same radius times the sine,
+ * z = sqrt(-2 log(((g2 >> 8) + 1) 2^-24)) cos(2 pi (g3 >> 8) 2^-24).  std == 0 draws nothing and changes no bit.
+ * Sample i depends on (seed, i, mesh) only: n samples at offset 0 and n at offset n equal 2 n samples at offset 0.
+ * points [n][3] fp32; face [n] int32 and bary [n][2] fp32 (u, v) may be NULL.  n must fit int32; n == 0 launches nothing. */
+int dsdf_surf_plan(int64_t n_faces, size_t* surf_bytes, size_t* area_offset, int32_t* n_tiles);          /* [host] */
+int dsdf_surf_prepare(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* surf, size_t surf_bytes,
+                      double* total_area, void* stream);
+int dsdf_surf_sample(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const void* surf, size_t surf_bytes,
+                     int64_t n, uint64_t offset, uint64_t seed, float std_dev, float* points, int32_t* face, float* bary,
+                     void* stream);
+
 /* ---- microstructure grids: deep_sdf/mesh.py create_mesh_microstructure / analysis/geometry.py sdf_struct, the parts in front of
  * and behind the decoder (csrc/msgrid.hpp) ----------------------------------------------------------------------------------
  * The padded grid has dims[a] = N[a] + 2 points per axis (linear index, z fastest).  Unfolded coordinate of index i on axis a:
