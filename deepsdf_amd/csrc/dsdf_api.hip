@@ -12,6 +12,9 @@
 
 #include <algorithm>
 #include <atomic>
+#ifdef DSDF_LAB
+#include <vector>
+#endif
 
 #include "dwstream.hpp"
 #include "sample.hpp"
@@ -312,6 +315,26 @@ struct WsTable {
 };
 thread_local WsTable t_last_plan;
 
+// What every planner carves its regions with.  align: 256, or 1 where regions were never padded (mesh SDF, nearest neighbour, and
+// the two test entries dsdf_gemm_tn / dsdf_grad_norm).
+struct WsCarver {
+  size_t o = 0, guard, align;
+  WsTable* rec;
+  explicit WsCarver(WsTable* r, size_t al = 256) : guard(g_redzone.load(std::memory_order_relaxed)), align(al), rec(r) {
+    if (rec) rec->reset();
+  }
+  size_t take(const char* name, int idx, size_t bytes) {
+    const size_t r = o;
+    o += (size_t)rup((int64_t)bytes, (int64_t)align) + guard;
+    if (rec) rec->add(name, idx, r, bytes);
+    return r;
+  }
+  size_t finish(size_t total) {   // total: o, or what the planner reports instead (decode_latent_plan)
+    if (rec) rec->total = total;
+    return total;
+  }
+};
+
 struct Plan {
   int nl, W0, N, R;
   int ld_in[DSDF_MAX_LAYERS];
@@ -323,7 +346,7 @@ struct Plan {
   size_t lnx_off[DSDF_MAX_LAYERS], lnr_off[DSDF_MAX_LAYERS];   // LayerNorm: xhat [N][ld_in[l+1]] (the Linear's output in place), rstd [N]
   // fused backward: per hidden layer l a global dP_l buffer, the forward's mask bits and per-workgroup column sums
   size_t dpl_off[DSDF_MAX_LAYERS], mask_off[DSDF_MAX_LAYERS], cs_off[DSDF_MAX_LAYERS], dwslab_off[DSDF_MAX_LAYERS];
-  int nwg, frows;    // workgroups of the fused kernels and their rows (64; 32 for batches that would leave CUs idle: pick_frows)
+  int nwg, frows;    // workgroups of the fused kernels and their rows (64; 32 for batches that would leave CUs idle: pick_path)
   DwSched dw;
   DwSched dwph[DSDF_MAX_BUCKETS];   // phased backward: the schedule of bucket b's layers [dw_cut[b + 1], dw_cut[b])
   int dw_nb, dw_cut[DSDF_MAX_BUCKETS + 1];   // dw_bucket_cuts
@@ -342,47 +365,38 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
   memset(&P, 0, sizeof(P));
   P.frows = frows;
   P.nl = n->n_layers; P.W0 = n->latent_size + n->geom_dim; P.N = (int)N; P.R = (int)R;
-  size_t o = 0;
-  const size_t guard = g_redzone.load(std::memory_order_relaxed);
-  if (rec) rec->reset();
-  auto take = [&](const char* name, int idx, size_t bytes) {
-    size_t r = o;
-    o += (size_t)rup((int64_t)bytes, 256) + guard;
-    if (rec) rec->add(name, idx, r, bytes);
-    return r;
-  };
+  WsCarver c(rec);
   int maxw = 4;
   for (int l = 0; l < P.nl; ++l) {
     P.ld_in[l] = (int)rup(n->in_dim[l], 4);
     if (P.ld_in[l] > maxw) maxw = P.ld_in[l];
   }
   if (inference) {
-    size_t pp[2] = {take("pp", 0, (size_t)N * maxw * 4), take("pp", 1, (size_t)N * maxw * 4)};
+    size_t pp[2] = {c.take("pp", 0, (size_t)N * maxw * 4), c.take("pp", 1, (size_t)N * maxw * 4)};
     for (int l = 0; l < P.nl; ++l) {
       // (xyz_in_all: every layer input carries xyz columns the gather pre-fills, so none of them can share a ping-pong buffer)
-      if (l == 0 || ((n->skip_mask >> l) & 1) || n->xyz_in_all) P.in_off[l] = take("in", l, (size_t)N * P.ld_in[l] * 4);
+      if (l == 0 || ((n->skip_mask >> l) & 1) || n->xyz_in_all) P.in_off[l] = c.take("in", l, (size_t)N * P.ld_in[l] * 4);
       else P.in_off[l] = pp[l & 1];
     }
     if (n->ln_param_mask) {   // one scratch row block for the Linear's output before LayerNorm (nothing is kept in inference)
-      const size_t t = take("lnx", -1, (size_t)N * maxw * 4);
+      const size_t t = c.take("lnx", -1, (size_t)N * maxw * 4);
       for (int l = 0; l < P.nl; ++l) P.lnx_off[l] = t;
     }
-    P.total = o;
-    if (rec) rec->total = o;
+    P.total = c.finish(c.o);
     return P;
   }
-  for (int l = 0; l < P.nl; ++l) P.in_off[l] = take("in", l, (size_t)N * P.ld_in[l] * 4 + 4096);   // + slack: edge tiles of dw_stream over-read
-  P.u_off = take("u", -1, (size_t)N * 4);
-  P.y_off = take("y", -1, (size_t)N * 4);
+  for (int l = 0; l < P.nl; ++l) P.in_off[l] = c.take("in", l, (size_t)N * P.ld_in[l] * 4 + 4096);   // + slack: edge tiles of dw_stream over-read
+  P.u_off = c.take("u", -1, (size_t)N * 4);
+  P.y_off = c.take("y", -1, (size_t)N * 4);
   P.ld_dp = maxw;
-  P.dp_off[0] = take("dp", 0, (size_t)N * maxw * 4);
-  P.dp_off[1] = take("dp", 1, (size_t)N * maxw * 4);
+  P.dp_off[0] = c.take("dp", 0, (size_t)N * maxw * 4);
+  P.dp_off[1] = c.take("dp", 1, (size_t)N * maxw * 4);
   P.ldz = (int)rup(P.W0, 4);
-  P.dzA_off = take("dzA", -1, (size_t)N * P.ldz * 4);
-  P.dzB_off = take("dzB", -1, (size_t)N * P.ldz * 4);
-  for (int t = 0; t < 2; ++t) P.dxz_off[t] = n->xyz_in_all ? take("dxz", t, (size_t)N * 4 * 4) : 0;   // [N][4]: one layer's d/d(xyz), running sum
+  P.dzA_off = c.take("dzA", -1, (size_t)N * P.ldz * 4);
+  P.dzB_off = c.take("dzB", -1, (size_t)N * P.ldz * 4);
+  for (int t = 0; t < 2; ++t) P.dxz_off[t] = n->xyz_in_all ? c.take("dxz", t, (size_t)N * 4 * 4) : 0;   // [N][4]: one layer's d/d(xyz), running sum
   for (int l = 0; l + 1 < P.nl; ++l)
-    if ((n->ln_param_mask >> l) & 1) { P.lnx_off[l] = take("lnx", l, (size_t)N * P.ld_in[l + 1] * 4); P.lnr_off[l] = take("lnr", l, (size_t)N * 4); }
+    if ((n->ln_param_mask >> l) & 1) { P.lnx_off[l] = c.take("lnx", l, (size_t)N * P.ld_in[l + 1] * 4); P.lnr_off[l] = c.take("lnr", l, (size_t)N * 4); }
   // split-K of the dW GEMMs: chunks of >= 256 points, at most NSPLIT_MAX slabs
   int ns = (int)((N + 255) / 256);
   if (ns > NSPLIT_MAX) ns = NSPLIT_MAX;
@@ -399,11 +413,11 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
     if (n->out_dim[l] > maxout) maxout = n->out_dim[l];
   }
   P.slab = rup(maxslab, 64);
-  P.slab_off = take("slab", -1, (size_t)P.nsplit * P.slab * 4);
+  P.slab_off = c.take("slab", -1, (size_t)P.nsplit * P.slab * 4);
   P.mt = (int)((N + BM - 1) / BM);
   P.ldcs = (int)rup(maxout, 4);
-  P.colsum_off = take("colsum", -1, (size_t)P.mt * P.ldcs * 4);
-  if (n->ln_param_mask) { P.lnpg_off = take("lnpg", -1, (size_t)LN_BLOCKS * P.ldcs * 4); P.lnpb_off = take("lnpb", -1, (size_t)LN_BLOCKS * P.ldcs * 4); }
+  P.colsum_off = c.take("colsum", -1, (size_t)P.mt * P.ldcs * 4);
+  if (n->ln_param_mask) { P.lnpg_off = c.take("lnpg", -1, (size_t)LN_BLOCKS * P.ldcs * 4); P.lnpb_off = c.take("lnpb", -1, (size_t)LN_BLOCKS * P.ldcs * 4); }
   P.last_blocks = (int)((N + 15) / 16);
   if (P.last_blocks > LAST_BLOCKS_MAX) P.last_blocks = LAST_BLOCKS_MAX;
   if (P.last_blocks < 1) P.last_blocks = 1;
@@ -412,18 +426,18 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
   // unbounded): sized for the larger.  (Rounds 1-3 sized them by last_blocks alone: batches of more than 65536 points -- the shipped
   // 10 x 16000 -- let the fused head write its partials past these buffers, into part2 / partdb / partloss and the dP_0 buffer.)
   const size_t part_rows = (size_t)std::max<int64_t>(P.last_blocks, (N + frows - 1) / frows);
-  P.part_off = take("part", -1, part_rows * P.ld_part * 4);
-  P.part2_off = take("part2", -1, (size_t)LAST_GROUPS * P.ld_part * 4);
-  P.partdb_off = take("partdb", -1, part_rows * 4);
-  P.partloss_off = take("partloss", -1, part_rows * 4);
-  P.segpart_off = take("segpart", -1, (size_t)LAT_SLICES_MAX * (R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // (up to 8 partial copies)
-  P.segnorm_off = take("segnorm", -1, (size_t)(R > 0 ? R : 1) * 4);
-  P.gnorm_off = take("gnorm", -1, 1024 * 4);
+  P.part_off = c.take("part", -1, part_rows * P.ld_part * 4);
+  P.part2_off = c.take("part2", -1, (size_t)LAST_GROUPS * P.ld_part * 4);
+  P.partdb_off = c.take("partdb", -1, part_rows * 4);
+  P.partloss_off = c.take("partloss", -1, part_rows * 4);
+  P.segpart_off = c.take("segpart", -1, (size_t)LAT_SLICES_MAX * (R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // (up to 8 partial copies)
+  P.segnorm_off = c.take("segnorm", -1, (size_t)(R > 0 ? R : 1) * 4);
+  P.gnorm_off = c.take("gnorm", -1, 1024 * 4);
   P.nwg = (int)((N + frows - 1) / frows);
   for (int l = 0; l < P.nl - 1; ++l) {
-    P.dpl_off[l] = take("dpl", l, (size_t)N * maxw * 4 + 4096);
-    P.mask_off[l] = take("mask", l, (size_t)P.nwg * 256 * 16);
-    P.cs_off[l] = take("cs", l, (size_t)P.nwg * P.ldcs * 4);
+    P.dpl_off[l] = c.take("dpl", l, (size_t)N * maxw * 4 + 4096);
+    P.mask_off[l] = c.take("mask", l, (size_t)P.nwg * 256 * 16);
+    P.cs_off[l] = c.take("cs", l, (size_t)P.nwg * P.ldcs * 4);
   }
   P.dw = dw_schedule(n, N, P.ld_in, segmode);
   P.dw_nb = nb < 2 ? 2 : (nb > DSDF_MAX_BUCKETS ? DSDF_MAX_BUCKETS : nb);
@@ -437,20 +451,19 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
     int ns = P.dw.nsplit[l];
     for (int t = 0; t < P.dw_nb; ++t)
       if (P.dwph[t].nsplit[l] > ns) ns = P.dwph[t].nsplit[l];
-    P.dwslab_off[l] = take("dwslab", l, (size_t)ns * P.dw.slab[l] * 4);
+    P.dwslab_off[l] = c.take("dwslab", l, (size_t)ns * P.dw.slab[l] * 4);
   }
   P.segmode = segmode ? 1 : 0;
   if (segmode) {
     P.ldu = P.ldcs;
-    P.hoistU_off = take("hoistU", -1, (size_t)(R > 0 ? R : 1) * 2 * P.ldu * 4);
-    for (int t = 0; t < 2; ++t) P.xsum_off[t] = take("xsum", t, (size_t)P.nwg * 4 * P.ldcs * 4);
+    P.hoistU_off = c.take("hoistU", -1, (size_t)(R > 0 ? R : 1) * 2 * P.ldu * 4);
+    for (int t = 0; t < 2; ++t) P.xsum_off[t] = c.take("xsum", t, (size_t)P.nwg * 4 * P.ldcs * 4);
     P.ldh = (int)rup(n->latent_size + n->geom_dim, 4);
     P.hstride = (long long)P.ldcs * P.ldh;
-    P.hs_off = take("hs", -1, (size_t)2 * P.hstride * 4);
-    P.zr_off = take("zr", -1, (size_t)(R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // renormed latent row of every segment
+    P.hs_off = c.take("hs", -1, (size_t)2 * P.hstride * 4);
+    P.zr_off = c.take("zr", -1, (size_t)(R > 0 ? R : 1) * (n->latent_size > 0 ? n->latent_size : 1) * 4);   // renormed latent row of every segment
   }
-  P.total = o;
-  if (rec) rec->total = o;
+  P.total = c.finish(c.o);
   return P;
 }
 
@@ -582,10 +595,67 @@ int run_gather(const DsdfNet* net, const Plan& P, void* ws, const float* table, 
   return 0;
 }
 
-bool fused_enabled() {
-  const char* e = getenv("DSDF_NO_FUSED");
-  return !(e && e[0] == '1');
-}
+// ---- the kernel path of one call --------------------------------------------------------------------
+// A/B and test switches.  Read ONCE per call, by the entry point (the tests flip them inside one process); nothing below an entry
+// point reads the environment (lab builds and the per-process DSDF_NO_RIDE of plan_roles excepted).
+struct Switches {
+  bool no_fused, no_narrow, frows64, no_w32, no_w32x2, no_merge;
+  static Switches read() {
+    auto is1 = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
+    const char* fr = getenv("DSDF_FROWS");
+    Switches s;
+    s.no_fused = is1("DSDF_NO_FUSED");             // the layer-by-layer launches instead of the fused kernels
+    s.no_narrow = is1("DSDF_NO_NARROW");           // narrow nets on the full-size kernels
+    s.frows64 = fr && !strcmp(fr, "64");           // no 32-row workgroups
+    s.no_w32 = getenv("DSDF_NO_W32") != nullptr;   // no wave-private kernels (w32x2: the 64-wide one only)
+    s.no_w32x2 = getenv("DSDF_NO_W32X2") != nullptr;
+    s.no_merge = getenv("DSDF_NO_MERGE") != nullptr;   // training: forward and backward as two launches
+#ifdef DSDF_LAB
+    if (getenv("DSDF_LAB_DBG")) s.no_merge = true;     // per-layer stamps are dumped after a forward launch of its own
+#endif
+    return s;
+  }
+};
+
+enum Family { FAM_LAYERED, FAM_FP32, FAM_SPLIT, FAM_BF16, FAM_BF16_SPLIT, FAM_H32, FAM_N128, FAM_W32, FAM_W32X2, FAM_COUNT };
+enum Entry { ENTRY_TRAIN, ENTRY_MODULE_FWD, ENTRY_MODULE_BWD, ENTRY_INFER };
+struct Path {
+  Family family;
+  int frows;     // rows per workgroup of the fused kernels: what make_plan lays the per-workgroup regions out for
+  bool fused;    // family != FAM_LAYERED
+  bool merged;   // training: forward + backward of the same points go out as one launch
+};
+
+// One row per family: the kernel of every role (nullptr: the family has none) and the block sizes.
+using FwdKernel = void (*)(FusedFwdArgs);
+using BwdKernel = void (*)(FusedBwdArgs);
+using FwdBwdKernel = void (*)(FusedFwdArgs, FusedBwdArgs);
+using DwKernel = void (*)(DwArgs, PostBwdArgs, int, int);
+struct FamilyKernels {
+  FwdKernel fwd; int fwd_block;   // forward without activation copies (inference)
+  FwdKernel fwd_act;              // forward with activation copies (module path, un-merged training)
+  BwdKernel bwd;                  // separate backward: 64-row workgroups only
+  FwdBwdKernel fwd_bwd;           // merged forward + backward
+  DwKernel dw;
+  int block;                      // every role but fwd
+};
+const FamilyKernels KERNELS[FAM_COUNT] = {
+    /* FAM_LAYERED    */ {nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0},
+    /* FAM_FP32       */ {fused_forward_kernel, 256, fused_forward_kernel, fused_backward_kernel, fused_fwd_bwd_kernel, dw_stream_kernel, 256},
+    /* FAM_SPLIT      */ {fused_forward_split_kernel, 256, fused_forward_split_kernel, fused_backward_split_kernel, fused_fwd_bwd_split_kernel,
+                          dw_stream_split_kernel, 256},
+    // config 5: the inference form has 8 staggered waves and transposed accumulators (fused_bf16x8.hpp); the backward is fp32
+    /* FAM_BF16       */ {fused_forward_bf16x8_kernel, F8_THREADS, fused_forward_bf16_kernel, fused_backward_kernel, fused_fwd_bf16_bwd_kernel,
+                          dw_stream_kernel, 256},
+    /* FAM_BF16_SPLIT */ {fused_forward_bf16x8_kernel, F8_THREADS, fused_forward_bf16_kernel, fused_backward_split_kernel,
+                          fused_fwd_bf16_bwd_split_kernel, dw_stream_split_kernel, 256},
+    /* FAM_H32        */ {fused_forward_h32_kernel, 256, fused_forward_h32_kernel, nullptr, fused_fwd_bwd_h32_kernel, dw_stream_kernel, 256},
+    /* FAM_N128       */ {fused_forward_n128_kernel, 256, fused_forward_n128_kernel, fused_backward_kernel, fused_fwd_bwd_n128_kernel,
+                          dw_stream_kernel, 256},
+    // wave-private: one wave per workgroup, merged training launch only
+    /* FAM_W32        */ {nullptr, 0, nullptr, nullptr, fused_fwd_bwd_w32_kernel, dw_stream_kernel, 64},
+    /* FAM_W32X2      */ {nullptr, 0, nullptr, nullptr, fused_fwd_bwd_w32x2_kernel, dw_stream_kernel, 64},
+};
 
 bool fused_eligible(const DsdfNet* net) {
   if (net_variant(net)) return false;   // latent_dropout / xyz_in_all live on the layer-by-layer kernels only
@@ -595,40 +665,77 @@ bool fused_eligible(const DsdfNet* net) {
   return net->in_dim[net->n_layers - 1] <= FMAXW;
 }
 
-// Narrow nets (every layer input and hidden width <= 128): the fused kernels' n128 variants, two workgroups per CU (fused.hpp).
-// fp32 MFMA only; DSDF_NO_NARROW=1 switches it off (A/B).
-bool net_narrow(const DsdfNet* net) {
-  const char* e = getenv("DSDF_NO_NARROW");
-  if ((e && e[0] == '1') || !fused_enabled() || !fused_eligible(net) || net->gemm_split || net->fwd_bf16) return false;
-  for (int l = 0; l < net->n_layers; ++l)
-    if (net->in_dim[l] > 128 || (l < net->n_layers - 1 && net->out_dim[l] > 128)) return false;
-  return true;
-}
-
-// Rows per workgroup of the fused kernels: 64, or 32 (fused_*_h32_kernel: fp32 MFMA, merged forward + backward or forward alone) when
-// 32-row workgroups still fit one per CU -- i.e. when 64-row workgroups would leave at least half of the chip idle (BASELINE config 4:
-// one shape x 8000 points).  DSDF_FROWS=64 switches it off (A/B).
-// merged: the training step's one-launch forward + backward.  Nets of at most 32-wide layers take it WAVE-PRIVATE at every batch size
-// (32 points per one-wave workgroup, fused_fwd_bwd_w32_kernel; DSDF_NO_W32=1: the 64-row narrow kernels instead).
-int w32_width(const DsdfNet* net) {      // 0: no; 32 / 64: the wave-private kernel for nets of at most that width
-  if (!net_narrow(net) || getenv("DSDF_NO_W32")) return 0;
+// THE decision which kernels run a call of `entry` on n points (n <= 0: the family whatever the batch).  Precedence, first match:
+//   not fused (DSDF_NO_FUSED, or a net the fused kernels do not cover)        -> layered
+//   bf16 / gemm_split nets                                                    -> their own family, 64 rows
+//   module entry points, un-merged training, DSDF_FROWS=64                    -> n128 for narrow nets, else fp32; 64 rows
+//   merged training, narrow net of at most 32- / 64-wide layers               -> w32 / w32x2 (wave-private: 32 points per one-wave
+//                                                                                workgroup) at EVERY batch size
+//   batches of at most 32 points per CU (64-row workgroups would leave at least half of the chip idle: BASELINE config 4,
+//   one shape x 8000 points) -- inference and merged training                 -> h32, 32 rows, for narrow nets too
+//   otherwise                                                                 -> n128 for narrow nets, else fp32; 64 rows
+// Narrow: every layer input and hidden width <= 128 (the n128 variants run two workgroups per CU, fused.hpp); fp32 MFMA only.
+Path pick_path(const DsdfNet* net, int64_t n, Entry entry, const Switches& sw) {
+  Path p{FAM_LAYERED, FROWS, false, false};
+  if (sw.no_fused || !fused_eligible(net)) return p;
+  p.fused = true;
+  p.merged = entry == ENTRY_TRAIN && !sw.no_merge;
+  if (net->fwd_bf16 || net->gemm_split) {
+    p.family = !net->fwd_bf16 ? FAM_SPLIT : (net->gemm_split ? FAM_BF16_SPLIT : FAM_BF16);
+    return p;
+  }
   int wmax = 0;
   for (int l = 0; l < net->n_layers; ++l) {
     wmax = std::max(wmax, net->in_dim[l]);
     if (l < net->n_layers - 1) wmax = std::max(wmax, net->out_dim[l]);
   }
-  if (wmax <= FWW) return FWW;
-  if (wmax <= FWW2 && !getenv("DSDF_NO_W32X2")) return FWW2;
-  return 0;
+  const bool narrow = !sw.no_narrow && wmax <= 128;
+  p.family = narrow ? FAM_N128 : FAM_FP32;
+  const bool rows32 = entry == ENTRY_INFER || p.merged;   // (the separate backward kernel and the module path's plan keep 64 rows)
+  if (!rows32 || sw.frows64 || n <= 0) return p;
+  if (p.merged && narrow && !sw.no_w32 && (wmax <= FWW || (wmax <= FWW2 && !sw.no_w32x2))) {
+    p.family = wmax <= FWW ? FAM_W32 : FAM_W32X2;
+    p.frows = 32;
+  } else if (n <= 32ll * (chip_waves() / 4)) {
+    p.family = FAM_H32;
+    p.frows = 32;
+  }
+  return p;
 }
-bool w32_wanted(const DsdfNet* net) { return w32_width(net) != 0; }
-int pick_frows(const DsdfNet* net, int64_t n, bool merged = false) {
-  const char* e = getenv("DSDF_FROWS");      // read per call: the tests switch it inside one process
-  const bool off = e && !strcmp(e, "64");
-  if (off || !fused_enabled() || !fused_eligible(net) || net->gemm_split || net->fwd_bf16) return FROWS;
-  if (merged && n > 0 && w32_wanted(net)) return 32;
-  return n > 0 && n <= 32ll * (chip_waves() / 4) ? 32 : FROWS;
+
+// dropout of hidden layer `layer`'s output: the 16-bit keep threshold and the scale of what is kept
+struct Drop { bool on; uint32_t thr; float scale; };
+Drop drop_of(const DsdfNet* net, int layer, int training) {
+  Drop d{training && ((net->dropout_mask >> layer) & 1) && net->dropout_p > 0.f, 0u, 1.0f};
+  if (d.on) {
+    d.thr = (uint32_t)std::min(lround((double)net->dropout_p * 65536.0), 65535l);
+    d.scale = 1.0f / (1.0f - net->dropout_p);
+  }
+  return d;
 }
+float mask_scale_of(const DsdfNet* net, int layer, int training) { return drop_of(net, layer, training).scale; }
+
+#ifdef DSDF_LAB
+// lab builds: device buffers of per-wave clock stamps.  One static LabStamps per launch site (allocated once, when the environment
+// names a dump file); a LabScope around the launch zeroes it on the stream (sites that ask for it) and, when the scope ends,
+// synchronises the device and writes the stamps to that file.
+struct LabStamps { const char* env; size_t bytes; bool zero; unsigned long long* dev; };
+struct LabScope {
+  LabStamps& s;
+  LabScope(LabStamps& site, hipStream_t st) : s(site) {
+    if (!s.dev && getenv(s.env)) (void)hipMalloc(&s.dev, s.bytes);
+    if (s.dev && s.zero) (void)hipMemsetAsync(s.dev, 0, s.bytes, st);
+  }
+  ~LabScope() {
+    if (!s.dev || !getenv(s.env)) return;
+    (void)hipDeviceSynchronize();
+    std::vector<unsigned long long> h(s.bytes / 8);
+    (void)hipMemcpy(h.data(), s.dev, s.bytes, hipMemcpyDeviceToHost);
+    FILE* f = fopen(getenv(s.env), "wb");
+    if (f) { fwrite(h.data(), 1, s.bytes, f); fclose(f); }
+  }
+};
+#endif
 
 // all hidden layers + the last layer's forward in ONE launch (fused.hpp).  store_act: keep global copies of the
 // activations (training / module path) or not (inference).
@@ -678,8 +785,8 @@ int run_hoist(const DsdfNet* net, const Plan& P, void* ws, const float* packed, 
 }
 
 // seg != nullptr: segment mode (fused.hpp FusedSeg) -- x0 is not read at all, seg->h[] / seg->U come from run_hoist
-int run_fused_forward(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* params, int64_t n,
-                      int training, const uint32_t* keys, uint32_t row_offset, bool store_act, float* y_out, float* u_out,
+int run_fused_forward(const DsdfNet* net, const Path& path, const Plan& P, void* ws, const float* packed, const float* params,
+                      int64_t n, int training, const uint32_t* keys, uint32_t row_offset, bool store_act, float* y_out, float* u_out,
                       hipStream_t st, const FusedSeg* seg = nullptr, FusedFwdArgs* defer = nullptr) {
   // defer != nullptr: fill *defer and launch nothing -- the caller hands it to run_backward_fused, which launches forward and
   // backward as ONE kernel (fused_fwd_bwd_kernel)
@@ -701,12 +808,8 @@ int run_fused_forward(const DsdfNet* net, const Plan& P, void* ws, const float* 
     y.out = store_act ? at<float>(ws, P.in_off[l + 1]) : nullptr;
     y.ld_out = P.ld_in[l + 1];
     y.in = net->in_dim[l]; y.out_dim = net->out_dim[l]; y.U = pk.uf[l];
-    const bool drop = training && ((net->dropout_mask >> l) & 1) && net->dropout_p > 0.f;
-    if (drop) {
-      long thr = lround((double)net->dropout_p * 65536.0);
-      if (thr > 65535) thr = 65535;
-      y.drop_thr = (uint32_t)thr; y.drop_key = keys[l]; y.drop_scale = 1.0f / (1.0f - net->dropout_p);
-    }
+    const Drop drop = drop_of(net, l, training);
+    if (drop.on) { y.drop_thr = drop.thr; y.drop_key = keys[l]; y.drop_scale = drop.scale; }
     y.x0_col = ((net->skip_mask >> (l + 1)) & 1) ? net->out_dim[l] : -1;
     y.maskbits = store_act ? at<uint32_t>(ws, P.mask_off[l]) : nullptr;
     if (seg != nullptr) {   // hoisted x0 columns: nothing left to contract for layer 0, only the previous layer for the skip layer
@@ -726,32 +829,16 @@ int run_fused_forward(const DsdfNet* net, const Plan& P, void* ws, const float* 
   double wmac = 0;
   for (int l = 0; l < last; ++l) wmac += (double)net->in_dim[l] * net->out_dim[l];
   ProfScope ps(DSDF_PROF_FUSED_FWD, 2.0 * (double)n * wmac, st);
-  #ifdef DSDF_LAB
-  static unsigned long long* dbg = nullptr;
-  if (!dbg && getenv("DSDF_LAB_DBG")) { (void)hipMalloc(&dbg, 8192 * 64 * 8); }
-  a.dbg = dbg;
-#endif
-  const dim3 grid((unsigned)((n + P.frows - 1) / P.frows));
-  if (P.frows == 32)                 // small batch: 32 points per workgroup (pick_frows: fp32 MFMA only)
-    hipLaunchKernelGGL(fused_forward_h32_kernel, grid, dim3(256), 0, st, a);
-  else if (net_narrow(net))          // every layer <= 128 wide: two workgroups per CU
-    hipLaunchKernelGGL(fused_forward_n128_kernel, grid, dim3(256), 0, st, a);
-  else if (net->fwd_bf16 && !store_act)   // config 5, inference form: 8 staggered waves, transposed accumulators (fused_bf16x8.hpp)
-    hipLaunchKernelGGL(fused_forward_bf16x8_kernel, grid, dim3(F8_THREADS), 0, st, a);
-  else if (net->fwd_bf16)            // with activation copies (module path; training goes out merged with the backward)
-    hipLaunchKernelGGL(fused_forward_bf16_kernel, grid, dim3(256), 0, st, a);
-  else
-    if (net->gemm_split) hipLaunchKernelGGL(fused_forward_split_kernel, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(fused_forward_kernel, grid, dim3(256), 0, st, a);
 #ifdef DSDF_LAB
-  if (dbg && getenv("DSDF_LAB_DBG")) {
-    (void)hipDeviceSynchronize();
-    static unsigned long long h[8192 * 64];
-    (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-    FILE* f = fopen(getenv("DSDF_LAB_DBG"), "wb");
-    if (f) { fwrite(h, 1, sizeof(h), f); fclose(f); }
-  }
+  static LabStamps stamps{"DSDF_LAB_DBG", 8192 * 64 * 8, false, nullptr};
+  LabScope lab(stamps, st);
+  a.dbg = stamps.dev;
 #endif
+  const FamilyKernels& k = KERNELS[path.family];
+  const FwdKernel kernel = store_act ? k.fwd_act : k.fwd;
+  if (kernel == nullptr) return fail(DSDF_E_LAUNCH, "internal: kernel family %d has no forward of its own", (int)path.family);
+  const dim3 grid((unsigned)((n + P.frows - 1) / P.frows));
+  hipLaunchKernelGGL(kernel, grid, dim3(store_act ? k.block : k.fwd_block), 0, st, a);
   LAUNCH_OK("fused_forward_kernel");
   return 0;
 }
@@ -772,13 +859,7 @@ int run_hidden_forward(const DsdfNet* net, const Plan& P, void* ws, const float*
     a.M = (int)n; a.N = net->out_dim[l]; a.K = net->in_dim[l];
     a.bias = params + L.bias_off[l];
     a.relu = 1;
-    const bool drop = training && ((net->dropout_mask >> l) & 1) && net->dropout_p > 0.f;
-    uint32_t thr = 0;
-    if (drop) {
-      long t = lround((double)net->dropout_p * 65536.0);
-      if (t > 65535) t = 65535;
-      thr = (uint32_t)t;
-    }
+    const Drop drop = drop_of(net, l, training);
     if (ln_applied(net, l)) {
       a.C = at<float>(ws, P.lnx_off[l]);
       TRY(launch_nt<EPI_PLAIN>(a, st));
@@ -787,25 +868,81 @@ int run_hidden_forward(const DsdfNet* net, const Plan& P, void* ws, const float*
       f.y = a.C; f.ldy = a.ldc; f.gamma = params + L.ln_w_off[l]; f.beta = params + L.ln_b_off[l];
       f.out = at<float>(ws, P.in_off[l + 1]); f.ldo = P.ld_in[l + 1]; f.n = (int)n; f.width = net->out_dim[l];
       f.save = save_ln ? 1 : 0; f.rstd = save_ln ? at<float>(ws, P.lnr_off[l]) : nullptr;
-      if (drop) { f.drop_thr = thr; f.drop_key = keys[l]; f.drop_scale = 1.0f / (1.0f - net->dropout_p); f.row_offset = row_offset; }
+      if (drop.on) { f.drop_thr = drop.thr; f.drop_key = keys[l]; f.drop_scale = drop.scale; f.row_offset = row_offset; }
       hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, f);
       LAUNCH_OK("ln_fwd_kernel");
       continue;
     }
-    if (drop) {
-      a.drop_thr = thr;
-      a.drop_key = keys[l];
-      a.drop_scale = 1.0f / (1.0f - net->dropout_p);
-      a.row_offset = row_offset;
-    }
+    if (drop.on) { a.drop_thr = drop.thr; a.drop_key = keys[l]; a.drop_scale = drop.scale; a.row_offset = row_offset; }
     TRY(launch_nt<EPI_FWD>(a, st));
   }
   return 0;
 }
 
-float mask_scale_of(const DsdfNet* net, int layer, int training) {
-  const bool drop = training && ((net->dropout_mask >> layer) & 1) && net->dropout_p > 0.f;
-  return drop ? 1.0f / (1.0f - net->dropout_p) : 1.0f;
+struct FuseAdam { const DsdfAdamCfg* cfg; float* params; float* exp_avg; float* exp_avg_sq; float* packed; };
+
+// Where a layer's weight gradient comes from: its split-K slabs and the column-sum partials that are its bias gradient
+struct FinSrc { const float* slabs; int nsplit; long long slab; int ldc; const float* colsum; int npart; int ldcs; };
+// One layer's finalize descriptor: slab sums, weight-norm backward and bias gradient into the gradient arena -- or, fz != nullptr
+// (dsdf_train_step), consumed on the spot by Adam, which also writes the row's new weight-norm scale
+FinArgs fin_args(const DsdfNet* net, const DsdfParamLayout& L, const Packed& pk, int l, const FinSrc& src, const float* params,
+                 float* grads, int accumulate, const FuseAdam* fz = nullptr) {
+  FinArgs f;
+  memset(&f, 0, sizeof(f));
+  f.slabs = src.slabs; f.nsplit = src.nsplit; f.slab = src.slab; f.ldc = src.ldc;
+  f.colsum = src.colsum; f.npart = src.npart; f.ldcs = src.ldcs;
+  f.g = L.g_off[l] >= 0 ? params + L.g_off[l] : nullptr;
+  f.v = params + L.v_off[l];
+  f.dg = L.g_off[l] >= 0 ? grads + L.g_off[l] : nullptr;
+  f.dv = grads + L.v_off[l];
+  f.db = grads + L.bias_off[l];
+  f.out = net->out_dim[l]; f.in = net->in_dim[l]; f.accumulate = accumulate;
+  if (fz != nullptr) {
+    const DsdfAdamCfg* c = fz->cfg;
+    const double bc1 = 1.0 - pow((double)c->beta1, (double)c->step), bc2 = 1.0 - pow((double)c->beta2, (double)c->step);
+    f.adam = 1;
+    f.pb = fz->params + L.bias_off[l]; f.mb = fz->exp_avg + L.bias_off[l]; f.sb = fz->exp_avg_sq + L.bias_off[l];
+    f.pv = fz->params + L.v_off[l];    f.mv = fz->exp_avg + L.v_off[l];    f.sv = fz->exp_avg_sq + L.v_off[l];
+    if (L.g_off[l] >= 0) { f.pg = fz->params + L.g_off[l]; f.mg = fz->exp_avg + L.g_off[l]; f.sg = fz->exp_avg_sq + L.g_off[l]; }
+    int r0 = 0;
+    for (int q = 0; q < l; ++q) r0 += net->out_dim[q];
+    f.scale_out = fz->packed + pk.scale_off + r0;
+    f.omb1 = 1.0f - c->beta1; f.b2 = c->beta2; f.omb2 = 1.0f - c->beta2;
+    f.step_size = (float)((double)c->lr_decoder / bc1); f.bc2_sqrt = (float)sqrt(bc2); f.eps = c->eps;
+  }
+  return f;
+}
+
+// d_input [n][W0] = dzA (+ dzB): the x0 gradients of layer 0 and of the skip layer
+int add_dz_to_input(const Plan& P, void* ws, int64_t n, bool used_dzB, float* d_input, int64_t ld_din, hipStream_t st) {
+  const long long tot = (long long)n * P.W0;
+  hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dzA_off), P.ldz,
+                     used_dzB ? at<float>(ws, P.dzB_off) : nullptr, P.ldz, d_input, (long long)ld_din, (int)n, P.W0);
+  LAUNCH_OK("add2_kernel");
+  return 0;
+}
+
+// The output layer's arguments every mode shares; callers add their mode's fields
+LastArgs last_args(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* params, int64_t n) {
+  DsdfParamLayout L;
+  param_layout(net, &L);
+  const Packed pk = packed_layout(net);
+  const int last = net->n_layers - 1;
+  LastArgs a;
+  memset(&a, 0, sizeof(a));
+  a.a = at<float>(ws, P.in_off[last]); a.lda = P.ld_in[last]; a.in = net->in_dim[last];
+  a.w = packed + pk.w_off[last]; a.b = params + L.bias_off[last]; a.n = (int)n; a.use_tanh = net->use_tanh;
+  return a;
+}
+// ... and what the two backward modes (training, module) share: dP of the last hidden layer and the per-block partials
+void last_args_backward(LastArgs& a, const DsdfNet* net, const Plan& P, void* ws, int training) {
+  const int last = net->n_layers - 1;
+  a.dp_prev = at<float>(ws, P.dp_off[0]);
+  a.lddp = P.ld_dp; a.mask_scale = mask_scale_of(net, last - 1, training);
+  a.part_dw = at<float>(ws, P.part_off); a.ld_part = P.ld_part;
+  a.part_colsum = at<float>(ws, P.part_off) + P.ld_in[last];
+  a.part_db = at<float>(ws, P.partdb_off); a.part_loss = at<float>(ws, P.partloss_off);
+  a.n_act = net->out_dim[last - 1];
 }
 
 // shared backward over hidden layers, given dp of layer nl-2 in dp[0] and the last layer's partials.
@@ -827,16 +964,8 @@ int run_backward(const DsdfNet* net, const Plan& P, void* ws, const float* packe
     hipLaunchKernelGGL(reduce_rows_kernel, dim3((w + 63) / 64, LAST_GROUPS), dim3(256), 0, st,
                        ReduceRowsArgs{at<float>(ws, P.part_off), P.last_blocks, P.ld_part, w, at<float>(ws, P.part2_off), LAST_GROUPS});
     LAUNCH_OK("reduce_rows_kernel");
-    FinArgs f;
-    memset(&f, 0, sizeof(f));
-    f.slabs = at<float>(ws, P.part2_off); f.nsplit = LAST_GROUPS; f.slab = P.ld_part; f.ldc = P.ld_part;
-    f.colsum = at<float>(ws, P.partdb_off); f.npart = P.last_blocks; f.ldcs = 1;
-    f.g = L.g_off[last] >= 0 ? params + L.g_off[last] : nullptr;
-    f.v = params + L.v_off[last];
-    f.dg = L.g_off[last] >= 0 ? grads + L.g_off[last] : nullptr;
-    f.dv = grads + L.v_off[last];
-    f.db = grads + L.bias_off[last];
-    f.out = 1; f.in = net->in_dim[last]; f.accumulate = accumulate;
+    const FinSrc src{at<float>(ws, P.part2_off), LAST_GROUPS, P.ld_part, P.ld_part, at<float>(ws, P.partdb_off), P.last_blocks, 1};
+    const FinArgs f = fin_args(net, L, pk, last, src, params, grads, accumulate);      // (out_dim[last] == 1: one block)
     hipLaunchKernelGGL(finalize_layer_kernel, dim3(1), dim3(256), 0, st, f);
     LAUNCH_OK("finalize_layer_kernel(last)");
     if ((net->ln_param_mask >> last) & 1) {   // bn module of the last Linear: created by the reference, never called: zero gradient
@@ -883,16 +1012,7 @@ int run_backward(const DsdfNet* net, const Plan& P, void* ws, const float* packe
     t.C = at<float>(ws, P.slab_off); t.ldc = P.ld_in[l]; t.M = net->out_dim[l]; t.N = net->in_dim[l]; t.K = (int)n;
     t.kchunk = P.kchunk; t.slab = P.slab;
     TRY(launch_tn(t, P.nsplit, st));
-    FinArgs f;
-    memset(&f, 0, sizeof(f));
-    f.slabs = t.C; f.nsplit = P.nsplit; f.slab = P.slab; f.ldc = t.ldc;
-    f.colsum = cs_ptr; f.npart = cs_n; f.ldcs = cs_ld;
-    f.g = L.g_off[l] >= 0 ? params + L.g_off[l] : nullptr;
-    f.v = params + L.v_off[l];
-    f.dg = L.g_off[l] >= 0 ? grads + L.g_off[l] : nullptr;
-    f.dv = grads + L.v_off[l];
-    f.db = grads + L.bias_off[l];
-    f.out = net->out_dim[l]; f.in = net->in_dim[l]; f.accumulate = accumulate;
+    const FinArgs f = fin_args(net, L, pk, l, FinSrc{t.C, P.nsplit, P.slab, t.ldc, cs_ptr, cs_n, cs_ld}, params, grads, accumulate);
     hipLaunchKernelGGL(finalize_layer_kernel, dim3(f.out), dim3(256), 0, st, f);
     LAUNCH_OK("finalize_layer_kernel");
     }
@@ -936,37 +1056,31 @@ int run_backward(const DsdfNet* net, const Plan& P, void* ws, const float* packe
   return 0;
 }
 
-struct FuseAdam { const DsdfAdamCfg* cfg; float* params; float* exp_avg; float* exp_avg_sq; float* packed; };
-
-// Backward with the fused dX chain (fused.hpp): K3's second stage + last layer finalize, ONE launch for the whole
-// dX chain (writes every dP_l, column sums, latent-gradient inputs), then dW (split-K) + finalize per layer.
+// Backward with the fused dX chain (fused.hpp): ONE launch for the whole dX chain (writes every dP_l, column sums, latent-gradient
+// inputs; merged with the forward in training), the second stage of the head's partials, then all dW (split-K) in one launch and all
+// finalizes in one.  Five jobs, five functions, sequenced by run_backward_fused below.
 // Segment mode (sb != nullptr): what the weight gradients of the hoisted layers need from the batch
 struct SegBwd { const FusedSeg* seg; const int64_t* seg_scene; const float* table; int R;
-                ScatterArgs* scatter; bool* scatter_done;       // (scatter->nslice is set here: the latent role decides it)
-                const float* zr; };   // the segments' renormed latent rows (run_hoist), or nullptr: read table[seg_scene[r]]   // the dense latent-gradient scatter may ride on the finalize launch
+                ScatterArgs* scatter; bool* scatter_done;       // the dense latent-gradient scatter may ride on the finalize launch
+                                                                // (scatter->nslice is set there: the latent role decides it)
+                const float* zr; };   // the segments' renormed latent rows (run_hoist), or nullptr: read table[seg_scene[r]]
 
-int run_backward_fused(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* params, int64_t n,
-                       int training, float* grads, int accumulate, int ncols_dz, bool* used_dzB, hipStream_t st,
-                       bool want_dw, const FusedBwdHead& head, const FuseAdam* fz = nullptr, const SegBwd* sb = nullptr,
-                       const FusedFwdArgs* fwd = nullptr,     // fwd: the deferred forward of the same points -> one launch for both
-                       int phase = 0) {                       // DsdfLossCfg.dw_phase: 0 = everything; p >= 1: dW + finalize of bucket p - 1
-                                                              // only (p = 1: after the forward + backward launch and its roles)
-  const DwSched& DS = phase == 0 ? P.dw : P.dwph[phase - 1];
-  auto in_phase = [&](int l) { return phase == 0 || (l >= P.dw_cut[phase] && l < P.dw_cut[phase - 1]); };
-  DsdfParamLayout L;
-  param_layout(net, &L);
+// the layers whose dW + finalize a call of this phase does (DsdfLossCfg.dw_phase; 0: all)
+inline bool in_phase(const Plan& P, int phase, int l) { return phase == 0 || (l >= P.dw_cut[phase] && l < P.dw_cut[phase - 1]); }
+
+// (1) The dX chain's arguments: one descriptor per layer, deepest first (layer 0 only when d/dx0 is wanted: ncols_dz > 0)
+FusedBwdArgs dx_chain_args(const DsdfNet* net, const Plan& P, void* ws, const float* packed, int64_t n, int training, int ncols_dz,
+                           bool want_dw, const FusedBwdHead& head, const SegBwd* sb, bool* used_dzB) {
   const Packed pk = packed_layout(net);
-  const int nl = net->n_layers, last = nl - 1;
+  const int last = net->n_layers - 1, ks = skip_layer(net);
+  const bool segmode = sb != nullptr;
   *used_dzB = false;
   FusedBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.N = (int)n;
   a.head = head;
-  const bool segmode = sb != nullptr;
-  const int ks = skip_layer(net);
   if (segmode) { a.xyz = sb->seg->xyz; a.G = sb->seg->G; }
   int cnt = 0;
-  double wmac = 0;
   for (int l = last - 1; l >= 0; --l) {
     if (l == 0 && ncols_dz <= 0) break;
     FusedBwdLayer& y = a.ly[cnt++];
@@ -988,70 +1102,70 @@ int run_backward_fused(const DsdfNet* net, const Plan& P, void* ws, const float*
       y.mask_cols = 0; y.mask_scale = 1.f;
       y.dz_out = at<float>(ws, P.dzA_off); y.ldz = P.ldz; y.dz_cols = ncols_dz; y.ncols = ncols_dz;
     }
-    wmac += (double)y.K * y.ncols;
   }
   a.n_layers = cnt;
   if (last_layer_skip(net)) {   // the head hands the x0 columns' gradient du w[x0 cols] to the skip-layer buffer of d/dx0
     a.head.dz_out = ncols_dz > 0 ? at<float>(ws, P.dzB_off) : nullptr; a.head.ldz = P.ldz; a.head.dz_cols = ncols_dz;
     if (ncols_dz > 0) *used_dzB = true;
   }
-  if (phase <= 1) {
-    // algorithmic FLOPs of the dX chain (the reference back-propagates through every hidden layer down to x0); the
-    // executed count `wmac` is smaller: layer 0's dX and the skip layer's x0 columns come from column sums instead
-    double amac = 0;
-    for (int l = 0; l < last; ++l) amac += (double)net->in_dim[l] * net->out_dim[l];
-    (void)wmac;
-    if (fwd != nullptr) {
+  return a;
+}
+
+// (2) The dX chain's launch: merged with the deferred forward of the same points (fwd != nullptr), or the backward alone
+int launch_dx_chain(const DsdfNet* net, const Path& path, const Plan& P, int64_t n, FusedBwdArgs& a, const FusedFwdArgs* fwd,
+                    hipStream_t st) {
+  // algorithmic FLOPs of the dX chain (the reference back-propagates through every hidden layer down to x0); the executed count is
+  // smaller: layer 0's dX and the skip layer's x0 columns come from column sums instead
+  double amac = 0;
+  for (int l = 0; l < net->n_layers - 1; ++l) amac += (double)net->in_dim[l] * net->out_dim[l];
+  const FamilyKernels& k = KERNELS[path.family];
+  const dim3 grid((unsigned)P.nwg), block(k.block);
+  if (fwd != nullptr) {
+    if (k.fwd_bwd == nullptr) return fail(DSDF_E_LAUNCH, "internal: kernel family %d has no merged forward + backward", (int)path.family);
 #ifdef DSDF_LAB
-      // lab: stamps of the MERGED launch (forward slots 0.., backward slots 32..), dumped after every launch
-      static unsigned long long* mdbg = nullptr;
-      FusedFwdArgs fwd_l = *fwd;
-      if (!mdbg && getenv("DSDF_LAB_MDBG")) { (void)hipMalloc(&mdbg, 8192 * 64 * 8); }
-      if (mdbg) { (void)hipMemsetAsync(mdbg, 0, 8192 * 64 * 8, st); fwd_l.dbg = mdbg; a.dbg = mdbg; fwd = &fwd_l; }
+    // lab: stamps of the MERGED launch (forward slots 0.., backward slots 32..), dumped after every launch
+    static LabStamps stamps{"DSDF_LAB_MDBG", 8192 * 64 * 8, true, nullptr};
+    LabScope lab(stamps, st);
+    FusedFwdArgs fwd_l = *fwd;
+    if (stamps.dev) { fwd_l.dbg = stamps.dev; a.dbg = stamps.dev; fwd = &fwd_l; }
 #endif
-      ProfScope ps(DSDF_PROF_FUSED_FWD_BWD, 4.0 * (double)n * amac, st);   // forward + dX chain
-      if (net->fwd_bf16 && net->gemm_split) hipLaunchKernelGGL(fused_fwd_bf16_bwd_split_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, *fwd, a);
-      else if (net->fwd_bf16) hipLaunchKernelGGL(fused_fwd_bf16_bwd_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, *fwd, a);
-      else if (net->gemm_split) hipLaunchKernelGGL(fused_fwd_bwd_split_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, *fwd, a);
-      else if (P.frows == 32 && w32_width(net) == FWW) hipLaunchKernelGGL(fused_fwd_bwd_w32_kernel, dim3((unsigned)P.nwg), dim3(64), 0, st, *fwd, a);
-      else if (P.frows == 32 && w32_width(net) == FWW2) hipLaunchKernelGGL(fused_fwd_bwd_w32x2_kernel, dim3((unsigned)P.nwg), dim3(64), 0, st, *fwd, a);
-      else if (P.frows == 32) hipLaunchKernelGGL(fused_fwd_bwd_h32_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, *fwd, a);
-      else if (net_narrow(net)) hipLaunchKernelGGL(fused_fwd_bwd_n128_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, *fwd, a);
-      else hipLaunchKernelGGL(fused_fwd_bwd_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, *fwd, a);
-      LAUNCH_OK("fused_fwd_bwd_kernel");
-#ifdef DSDF_LAB
-      if (mdbg && getenv("DSDF_LAB_MDBG")) {
-        (void)hipDeviceSynchronize();
-        static unsigned long long h[8192 * 64];
-        (void)hipMemcpy(h, mdbg, sizeof(h), hipMemcpyDeviceToHost);
-        FILE* f = fopen(getenv("DSDF_LAB_MDBG"), "wb");
-        if (f) { fwrite(h, 1, sizeof(h), f); fclose(f); }
-      }
-#endif
-    } else {
-      ProfScope ps(DSDF_PROF_FUSED_BWD, 2.0 * (double)n * amac, st);
-      if (P.frows != FROWS) return fail(DSDF_E_LAUNCH, "internal: the separate backward kernel has 64-row workgroups only");
-      if (net->gemm_split) hipLaunchKernelGGL(fused_backward_split_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(fused_backward_kernel, dim3((unsigned)P.nwg), dim3(256), 0, st, a);
-      LAUNCH_OK("fused_backward_kernel");
-    }
+    ProfScope ps(DSDF_PROF_FUSED_FWD_BWD, 4.0 * (double)n * amac, st);   // forward + dX chain
+    hipLaunchKernelGGL(k.fwd_bwd, grid, block, 0, st, *fwd, a);
+    LAUNCH_OK("fused_fwd_bwd_kernel");
+    return 0;
   }
-  const ReduceRowsArgs rr{at<float>(ws, P.part_off), P.nwg, P.ld_part, P.ld_part, at<float>(ws, P.part2_off), LAST_GROUPS};
-  const int rr_bx = (P.ld_part + 63) / 64;
-  if (!segmode && phase <= 1) {
-    if (want_dw) {   // second stage of the head's per-workgroup partials
-      hipLaunchKernelGGL(reduce_rows_kernel, dim3(rr_bx, LAST_GROUPS), dim3(256), 0, st, rr);
-      LAUNCH_OK("reduce_rows_kernel");
-    }
-  }
-  // segment mode: everything that consumes only the backward's per-workgroup partials (kernels.hpp post_bwd_role) -- run by
-  // the workgroups the dW launch leaves idle, or by a launch of its own when there is no dW launch / no idle workgroup
-  PostBwdArgs q;
-  memset(&q, 0, sizeof(q));
-  int lat_n = 0, lat_slices = 1;
+  ProfScope ps(DSDF_PROF_FUSED_BWD, 2.0 * (double)n * amac, st);
+  if (path.frows != FROWS || k.bwd == nullptr)
+    return fail(DSDF_E_LAUNCH, "internal: the separate backward kernel has 64-row workgroups only");
+  hipLaunchKernelGGL(k.bwd, grid, block, 0, st, a);
+  LAUNCH_OK("fused_backward_kernel");
+  return 0;
+}
+
+// (3) Segment mode: everything that consumes only the backward's per-workgroup partials (kernels.hpp post_bwd_role) -- run by
+// the workgroups the dW launch leaves idle (rides), or by a launch of its own when there is no dW launch / no idle workgroup.
+// Decides, launches nothing.
+struct Roles {
+  ReduceRowsArgs rr; int rr_bx;      // second stage of the head's per-workgroup partials (general mode: a launch of its own)
+  PostBwdArgs q; int lat_n;          // segment mode: the role blocks, lat_n of them latent-gradient blocks
+  int lat_slices;                    //   slices of a segment's latent gradient the scatter has to add
+  int cus, dw_items, dw_busy;        // the dW launch: its items and the workgroups they keep busy
+  bool rides;
+};
+Roles plan_roles(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const DwSched& DS, bool want_dw, const SegBwd* sb,
+                 int phase) {
+  const Packed pk = packed_layout(net);
+  const int ks = skip_layer(net);
+  const bool segmode = sb != nullptr;
+  Roles R;
+  memset(&R, 0, sizeof(R));
+  R.rr = ReduceRowsArgs{at<float>(ws, P.part_off), P.nwg, P.ld_part, P.ld_part, at<float>(ws, P.part2_off), LAST_GROUPS};
+  R.rr_bx = (P.ld_part + 63) / 64;
+  R.lat_slices = 1;
+  PostBwdArgs& q = R.q;
   if (segmode) {
     if (want_dw) {
-      q.rr = rr; q.rr_bx = rr_bx; q.rr_n = rr_bx * LAST_GROUPS;
+      q.rr = R.rr; q.rr_bx = R.rr_bx; q.rr_n = R.rr_bx * LAST_GROUPS;
       SegDwArgs& d = q.dw;
       d.nh = ks > 0 ? 2 : 1;
       d.cs[0] = at<float>(ws, P.cs_off[0]); d.xsum[0] = at<float>(ws, P.xsum_off[0]); d.out[0] = net->out_dim[0];
@@ -1075,18 +1189,17 @@ int run_backward_fused(const DsdfNet* net, const Plan& P, void* ws, const float*
     g.segpart = at<float>(ws, P.segpart_off); g.segnorm = at<float>(ws, P.segnorm_off);
     q.lat_bx = sb->R;
     g.nchunk = (net->latent_size + 15) / 16;
-    lat_n = sb->R * g.nchunk;
+    R.lat_n = sb->R * g.nchunk;
     // few long segments in a launch of their own (config 4: one shape): cut each segment's workgroups into slices so that the launch
     // has blocks for the chip; the scatter adds the slices
     g.nslice = 1; g.slice_stride = (long long)sb->R * net->latent_size;
-    while (g.nslice < LAT_SLICES_MAX && lat_n * g.nslice * 2 <= chip_waves() / 4 && g.wg_per_seg / (g.nslice * 2) >= 16) g.nslice *= 2;
-    lat_n *= g.nslice;
-    lat_slices = g.nslice;
+    while (g.nslice < LAT_SLICES_MAX && R.lat_n * g.nslice * 2 <= chip_waves() / 4 && g.wg_per_seg / (g.nslice * 2) >= 16) g.nslice *= 2;
+    R.lat_n *= g.nslice;
+    R.lat_slices = g.nslice;
   }
-  auto tell_scatter = [&]() { if (segmode && sb->scatter != nullptr) { sb->scatter->nslice = lat_slices; sb->scatter->slice_stride = (long long)sb->R * net->latent_size; } };
-  const int cus = chip_waves() / 4;
-  const int dw_items = DS.n_full + DS.n_narrow;
-  const int dw_busy = want_dw ? ((dw_items + 3) / 4 < cus ? (dw_items + 3) / 4 : cus) : 0;
+  R.cus = chip_waves() / 4;
+  R.dw_items = DS.n_full + DS.n_narrow;
+  R.dw_busy = want_dw ? ((R.dw_items + 3) / 4 < R.cus ? (R.dw_items + 3) / 4 : R.cus) : 0;
   // the idle workgroups take the role blocks one after the other: that stays inside the dW time for batches of up to one
   // workgroup per CU (measured: 16384 points, 1168 role blocks on 16 workgroups, dW time unchanged); larger batches put
   // the roles on the critical path (65536 points: -5 %), so they get their own (wide) launch there
@@ -1097,113 +1210,119 @@ int run_backward_fused(const DsdfNet* net, const Plan& P, void* ws, const float*
   // seg_latgrad_all_body: one block per 16 latent columns takes all segments): they now end 242 us into the launch.
   // (gemm_split: measured again with the rebuilt roles -- they end 242 us into the launch, the split items 174 us: riding there made
   // the launch 253 us instead of 174 + 18 for a launch of their own, so they still do not ride in split mode)
-  const bool post_rides = segmode && want_dw && cus - dw_busy >= 8 && P.nwg <= cus && !no_ride && !net->gemm_split && phase <= 1 &&
-                          dw_items > 0;
-  if (post_rides) {   // the few-workgroups forms: 32 weight-gradient rows per block, one latent-gradient block per 16 columns
-    q.lat.nslice = 1; lat_slices = 1;
+  R.rides = segmode && want_dw && R.cus - R.dw_busy >= 8 && P.nwg <= R.cus && !no_ride && !net->gemm_split && phase <= 1 &&
+            R.dw_items > 0;
+  if (R.rides) {   // the few-workgroups forms: 32 weight-gradient rows per block, one latent-gradient block per 16 columns
+    q.lat.nslice = 1; R.lat_slices = 1;
     q.lat_bx = 0;
-    lat_n = (net->latent_size + 15) / 16;
+    R.lat_n = (net->latent_size + 15) / 16;
     q.rr_n = q.rr_bx;               // one block per 64-column strip of the head's partials takes all groups (reduce_rows_strip_body)
     q.dw_n = (q.dw.out[0] + SDW_ROWS_RIDE - 1) / SDW_ROWS_RIDE + (ks > 0 ? (q.dw.out[1] + SDW_ROWS_RIDE - 1) / SDW_ROWS_RIDE : 0);
   }
-  tell_scatter();
-  if (segmode && !post_rides && phase <= 1) {
-    hipLaunchKernelGGL(post_bwd_kernel, dim3((unsigned)(q.rr_n + q.dw_n + lat_n)), dim3(256), 0, st, q, lat_n);
-    LAUNCH_OK("post_bwd_kernel");
+  return R;
+}
+
+// (4) All dW_l = dP_l^T a_l (of this phase's layers) in one launch; the riding roles go to the workgroups its items leave idle
+int launch_dw(const DsdfNet* net, const Path& path, const Plan& P, void* ws, int64_t n, const DwSched& DS, const Roles& R, bool segmode,
+              int phase, hipStream_t st) {
+  const int last = net->n_layers - 1;
+  DwArgs d;
+  memset(&d, 0, sizeof(d));
+  d.n_layers = last; d.n_full = DS.n_full; d.n_narrow = DS.n_narrow; d.N = (int)n;
+  double fl = 0;
+  for (int l = 0; l < last; ++l) {
+    DwLayer& y = d.ly[l];
+    y.dp = at<float>(ws, P.dpl_off[l]); y.ld_dp = P.ld_dp;
+    y.act = at<float>(ws, P.in_off[l]); y.ld_act = P.ld_in[l];
+    y.slabs = at<float>(ws, P.dwslab_off[l]); y.slab = DS.slab[l];
+    y.M = net->out_dim[l]; y.Nc = dw_cols(net, l, segmode); y.ldc = P.ld_in[l];
+    y.tiles_m = DS.tiles_m[l]; y.tiles_n = DS.tiles_n[l]; y.last_nj = DS.last_nj[l]; y.nfull_n = DS.nfull_n[l];
+    y.nsplit = DS.nsplit[l]; y.kchunk = DS.kchunk[l]; y.full0 = DS.full0[l]; y.narrow0 = DS.narrow0[l];
+    if (in_phase(P, phase, l)) fl += 2.0 * (double)n * y.M * net->in_dim[l];   // algorithmic (segment mode executes fewer: hoisted x0 columns)
   }
-  if (want_dw && dw_items > 0) {   // all dW_l = dP_l^T a_l (of this phase's layers) in one launch
-    DwArgs d;
-    memset(&d, 0, sizeof(d));
-    d.n_layers = last; d.n_full = DS.n_full; d.n_narrow = DS.n_narrow; d.N = (int)n;
-    double fl = 0;
-    for (int l = 0; l < last; ++l) {
-      DwLayer& y = d.ly[l];
-      y.dp = at<float>(ws, P.dpl_off[l]); y.ld_dp = P.ld_dp;
-      y.act = at<float>(ws, P.in_off[l]); y.ld_act = P.ld_in[l];
-      y.slabs = at<float>(ws, P.dwslab_off[l]); y.slab = DS.slab[l];
-      y.M = net->out_dim[l]; y.Nc = dw_cols(net, l, segmode); y.ldc = P.ld_in[l];
-      y.tiles_m = DS.tiles_m[l]; y.tiles_n = DS.tiles_n[l]; y.last_nj = DS.last_nj[l]; y.nfull_n = DS.nfull_n[l];
-      y.nsplit = DS.nsplit[l]; y.kchunk = DS.kchunk[l]; y.full0 = DS.full0[l]; y.narrow0 = DS.narrow0[l];
-      if (in_phase(l)) fl += 2.0 * (double)n * y.M * net->in_dim[l];   // algorithmic (segment mode executes fewer: hoisted x0 columns)
-    }
+#ifdef DSDF_LAB
+  static LabStamps stamps{"DSDF_LAB_DWDBG", 1024 * 4 * 8 * 8, true, nullptr};      // lab: per-wave stamps of the LAST dW launch, dumped at every launch
+  LabScope lab(stamps, st);
+  d.dbg = stamps.dev;
+#endif
+  ProfScope ps(DSDF_PROF_DW_STREAM, fl, st);
+  const DwKernel kernel = KERNELS[path.family].dw;
+  if (R.rides) {
+    hipLaunchKernelGGL(kernel, dim3(R.cus), dim3(256), 0, st, d, R.q, R.lat_n, R.dw_busy);
+  } else {
     PostBwdArgs none;
     memset(&none, 0, sizeof(none));
-    int grid = dw_busy < 1 ? 1 : dw_busy;
-#ifdef DSDF_LAB
-    static unsigned long long* dwdbg = nullptr;      // lab: per-wave stamps of the LAST dW launch, dumped at every launch
-    if (!dwdbg && getenv("DSDF_LAB_DWDBG")) { (void)hipMalloc(&dwdbg, 1024 * 4 * 8 * 8); }
-    if (dwdbg) (void)hipMemsetAsync(dwdbg, 0, 1024 * 4 * 8 * 8, st);
-    d.dbg = dwdbg;
-#endif
-    ProfScope ps(DSDF_PROF_DW_STREAM, fl, st);
-    if (net->gemm_split) {
-      if (post_rides) hipLaunchKernelGGL(dw_stream_split_kernel, dim3(cus), dim3(256), 0, st, d, q, lat_n, dw_busy);
-      else hipLaunchKernelGGL(dw_stream_split_kernel, dim3(grid), dim3(256), 0, st, d, none, 0, grid);
-    } else if (post_rides) hipLaunchKernelGGL(dw_stream_kernel, dim3(cus), dim3(256), 0, st, d, q, lat_n, dw_busy);
-    else hipLaunchKernelGGL(dw_stream_kernel, dim3(grid), dim3(256), 0, st, d, none, 0, grid);
-    LAUNCH_OK("dw_stream_kernel");
-#ifdef DSDF_LAB
-    if (dwdbg && getenv("DSDF_LAB_DWDBG")) {
-      (void)hipDeviceSynchronize();
-      static unsigned long long h[1024 * 4 * 8];
-      (void)hipMemcpy(h, dwdbg, sizeof(h), hipMemcpyDeviceToHost);
-      FILE* f = fopen(getenv("DSDF_LAB_DWDBG"), "wb");
-      if (f) { fwrite(h, 1, sizeof(h), f); fclose(f); }
-    }
-#endif
+    const int grid = R.dw_busy < 1 ? 1 : R.dw_busy;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, d, none, 0, grid);
   }
-  if (want_dw) {   // split-K sums, weight-norm backward and bias gradients of ALL layers (last layer included) in one launch
-    FinAll fa;
-    memset(&fa, 0, sizeof(fa));
-    int rows = 0;
-    for (int l = last; l >= 0; --l) {
-      if (!in_phase(l)) continue;
-      FinArgs& f = fa.f[fa.n];
-      if (l == last) {
-        f.slabs = at<float>(ws, P.part2_off); f.nsplit = LAST_GROUPS; f.slab = P.ld_part; f.ldc = P.ld_part;
-        f.colsum = at<float>(ws, P.partdb_off); f.npart = P.nwg; f.ldcs = 1;
-      } else {
-        f.slabs = at<float>(ws, P.dwslab_off[l]); f.nsplit = DS.nsplit[l]; f.slab = DS.slab[l]; f.ldc = P.ld_in[l];
-        if (l == last - 1) { f.colsum = at<float>(ws, P.part2_off) + P.ld_in[last]; f.npart = LAST_GROUPS; f.ldcs = P.ld_part; }
-        else { f.colsum = at<float>(ws, P.cs_off[l]); f.npart = P.nwg; f.ldcs = P.ldcs; }
-      }
-      f.g = L.g_off[l] >= 0 ? params + L.g_off[l] : nullptr;
-      f.v = params + L.v_off[l];
-      f.dg = L.g_off[l] >= 0 ? grads + L.g_off[l] : nullptr;
-      f.dv = grads + L.v_off[l];
-      f.db = grads + L.bias_off[l];
-      f.out = net->out_dim[l]; f.in = net->in_dim[l]; f.accumulate = accumulate;
-      if (segmode && (l == 0 || l == ks)) {
-        f.hoist = 1; f.lat0 = l == 0 ? 0 : net->out_dim[l - 1]; f.hW = net->latent_size + net->geom_dim; f.ldh = P.ldh;
-        f.hs = at<float>(ws, P.hs_off) + (l == 0 ? 0 : P.hstride);
-      }
-      if (fz != nullptr) {
-        const DsdfAdamCfg* c = fz->cfg;
-        const double bc1 = 1.0 - pow((double)c->beta1, (double)c->step), bc2 = 1.0 - pow((double)c->beta2, (double)c->step);
-        f.adam = 1;
-        f.pb = fz->params + L.bias_off[l]; f.mb = fz->exp_avg + L.bias_off[l]; f.sb = fz->exp_avg_sq + L.bias_off[l];
-        f.pv = fz->params + L.v_off[l];    f.mv = fz->exp_avg + L.v_off[l];    f.sv = fz->exp_avg_sq + L.v_off[l];
-        if (L.g_off[l] >= 0) { f.pg = fz->params + L.g_off[l]; f.mg = fz->exp_avg + L.g_off[l]; f.sg = fz->exp_avg_sq + L.g_off[l]; }
-        int r0 = 0;
-        for (int q = 0; q < l; ++q) r0 += net->out_dim[q];
-        f.scale_out = fz->packed + pk.scale_off + r0;
-        f.omb1 = 1.0f - c->beta1; f.b2 = c->beta2; f.omb2 = 1.0f - c->beta2;
-        f.step_size = (float)((double)c->lr_decoder / bc1); f.bc2_sqrt = (float)sqrt(bc2); f.eps = c->eps;
-      }
-      fa.row0[fa.n] = rows;
-      rows += fin_blocks(f.out, f.in);     // (`rows` counts BLOCKS of the finalize launch)
-      ++fa.n;
+  LAUNCH_OK("dw_stream_kernel");
+  return 0;
+}
+
+// (5) The finalize table: split-K sums, weight-norm backward and bias gradients [+ Adam] of ALL of this phase's layers (last layer
+// included), one launch.  Returns the launch's block count (0: an empty bucket -- fewer layers than buckets).
+int fin_table(const DsdfNet* net, const Plan& P, void* ws, const DwSched& DS, const float* params, float* grads, int accumulate,
+              const FuseAdam* fz, bool segmode, int phase, FinAll* fa) {
+  DsdfParamLayout L;
+  param_layout(net, &L);
+  const Packed pk = packed_layout(net);
+  const int last = net->n_layers - 1, ks = skip_layer(net);
+  memset(fa, 0, sizeof(*fa));
+  int rows = 0;      // counts BLOCKS of the finalize launch
+  for (int l = last; l >= 0; --l) {
+    if (!in_phase(P, phase, l)) continue;
+    FinSrc src;
+    if (l == last) src = FinSrc{at<float>(ws, P.part2_off), LAST_GROUPS, P.ld_part, P.ld_part, at<float>(ws, P.partdb_off), P.nwg, 1};
+    else if (l == last - 1)
+      src = FinSrc{at<float>(ws, P.dwslab_off[l]), DS.nsplit[l], DS.slab[l], P.ld_in[l], at<float>(ws, P.part2_off) + P.ld_in[last], LAST_GROUPS, P.ld_part};
+    else src = FinSrc{at<float>(ws, P.dwslab_off[l]), DS.nsplit[l], DS.slab[l], P.ld_in[l], at<float>(ws, P.cs_off[l]), P.nwg, P.ldcs};
+    FinArgs& f = fa->f[fa->n];
+    f = fin_args(net, L, pk, l, src, params, grads, accumulate, fz);
+    if (segmode && (l == 0 || l == ks)) {
+      f.hoist = 1; f.lat0 = l == 0 ? 0 : net->out_dim[l - 1]; f.hW = net->latent_size + net->geom_dim; f.ldh = P.ldh;
+      f.hs = at<float>(ws, P.hs_off) + (l == 0 ? 0 : P.hstride);
     }
-    fa.row0[fa.n] = rows;
-    if (rows == 0) return 0;   // an empty bucket (fewer layers than buckets)
-    if (segmode && sb->scatter != nullptr && phase <= 1) {
-      hipLaunchKernelGGL(finalize_scatter_kernel, dim3(rows + sb->R), dim3(256), 0, st, fa, *sb->scatter, rows);
-      LAUNCH_OK("finalize_scatter_kernel");
-      *sb->scatter_done = true;
-    } else {
-      hipLaunchKernelGGL(finalize_all_kernel, dim3(rows), dim3(256), 0, st, fa);
-      LAUNCH_OK("finalize_all_kernel");
-    }
+    fa->row0[fa->n] = rows;
+    rows += fin_blocks(f.out, f.in);
+    ++fa->n;
+  }
+  fa->row0[fa->n] = rows;
+  return rows;
+}
+
+// fwd: the deferred forward of the same points -> one launch for both.
+// phase (DsdfLossCfg.dw_phase): 0 = everything; p >= 1: dW + finalize of bucket p - 1 only (p = 1: after the forward + backward launch
+// and its roles)
+int run_backward_fused(const DsdfNet* net, const Path& path, const Plan& P, void* ws, const float* packed, const float* params, int64_t n,
+                       int training, float* grads, int accumulate, int ncols_dz, bool* used_dzB, hipStream_t st, bool want_dw,
+                       const FusedBwdHead& head, const FuseAdam* fz = nullptr, const SegBwd* sb = nullptr,
+                       const FusedFwdArgs* fwd = nullptr, int phase = 0) {
+  const DwSched& DS = phase == 0 ? P.dw : P.dwph[phase - 1];
+  const bool segmode = sb != nullptr;
+  FusedBwdArgs a = dx_chain_args(net, P, ws, packed, n, training, ncols_dz, want_dw, head, sb, used_dzB);
+  if (phase <= 1) TRY(launch_dx_chain(net, path, P, n, a, fwd, st));
+  const Roles R = plan_roles(net, P, ws, packed, DS, want_dw, sb, phase);
+  if (!segmode && phase <= 1 && want_dw) {
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(R.rr_bx, LAST_GROUPS), dim3(256), 0, st, R.rr);
+    LAUNCH_OK("reduce_rows_kernel");
+  }
+  if (segmode && sb->scatter != nullptr) { sb->scatter->nslice = R.lat_slices; sb->scatter->slice_stride = (long long)sb->R * net->latent_size; }
+  if (segmode && !R.rides && phase <= 1) {
+    hipLaunchKernelGGL(post_bwd_kernel, dim3((unsigned)(R.q.rr_n + R.q.dw_n + R.lat_n)), dim3(256), 0, st, R.q, R.lat_n);
+    LAUNCH_OK("post_bwd_kernel");
+  }
+  if (!want_dw) return 0;
+  if (R.dw_items > 0) TRY(launch_dw(net, path, P, ws, n, DS, R, segmode, phase, st));
+  FinAll fa;
+  const int rows = fin_table(net, P, ws, DS, params, grads, accumulate, fz, segmode, phase, &fa);
+  if (rows == 0) return 0;
+  if (segmode && sb->scatter != nullptr && phase <= 1) {   // the dense latent-gradient scatter rides on the finalize launch
+    hipLaunchKernelGGL(finalize_scatter_kernel, dim3(rows + sb->R), dim3(256), 0, st, fa, *sb->scatter, rows);
+    LAUNCH_OK("finalize_scatter_kernel");
+    *sb->scatter_done = true;
+  } else {
+    hipLaunchKernelGGL(finalize_all_kernel, dim3(rows), dim3(256), 0, st, fa);
+    LAUNCH_OK("finalize_all_kernel");
   }
   return 0;
 }
@@ -1227,10 +1346,12 @@ FusedBwdHead make_head(const DsdfNet* net, const Plan& P, void* ws, const float*
   return h;
 }
 
-int check_common(const DsdfNet* net, const void* packed, const void* params, const void* ws) {
+// (validate() admits fwd_bf16 / gemm_split only for nets the fused kernels cover: without them the switch is the one reason)
+int check_common(const DsdfNet* net, const Switches& sw, const void* packed, const void* params, const void* ws) {
   TRY(validate(net));
-  if (net->fwd_bf16 && !fused_enabled()) return fail(DSDF_E_INVALID, "fwd_bf16 exists only in the fused kernels (DSDF_NO_FUSED is set)");
-  if (net->gemm_split && !fused_enabled()) return fail(DSDF_E_INVALID, "gemm_split exists only in the fused kernels (DSDF_NO_FUSED is set)");
+  const bool fused = pick_path(net, 0, ENTRY_MODULE_FWD, sw).fused;
+  if (net->fwd_bf16 && !fused) return fail(DSDF_E_INVALID, "fwd_bf16 exists only in the fused kernels (DSDF_NO_FUSED is set)");
+  if (net->gemm_split && !fused) return fail(DSDF_E_INVALID, "gemm_split exists only in the fused kernels (DSDF_NO_FUSED is set)");
   if (!packed || !params || !ws) return fail(DSDF_E_INVALID, "NULL packed/params/workspace pointer");
   if (!aligned16(packed) || !aligned16(params) || (reinterpret_cast<uintptr_t>(ws) & 255))
     return fail(DSDF_E_INVALID, "packed/params must be 16-byte and workspace 256-byte aligned");
@@ -1259,33 +1380,26 @@ int dsdf_packed_floats(const DsdfNet* net, int64_t* n_floats) {
   return 0;
 }
 
-int dsdf_workspace_bytes(const DsdfNet* net, int64_t n_points, int64_t n_segments, size_t* bytes) {
-  TRY(validate(net));
-  if (!bytes || n_points < 0 || n_segments < 0) return fail(DSDF_E_INVALID, "bad arguments");
-  if (n_points > (1ll << 30)) return fail(DSDF_E_INVALID, "n_points too large");
-  size_t best = 0;
-  for (int fr = 32; fr <= FROWS; fr += 32)      // (32-row workgroups double the per-workgroup partials: pick_frows decides per call)
-    for (int seg = 0; seg < 2; ++seg)           // segment mode lays the workspace out differently
-      best = std::max(best, make_plan(net, n_points, n_segments, false, seg != 0, 2, fr).total);
-  *bytes = best;
-  return 0;
-}
-
 int dsdf_workspace_bytes_buckets(const DsdfNet* net, int64_t n_points, int64_t n_segments, int32_t n_buckets, size_t* bytes) {
   TRY(validate(net));
   if (!bytes || n_points < 0 || n_segments < 0) return fail(DSDF_E_INVALID, "bad arguments");
   if (n_points > (1ll << 30)) return fail(DSDF_E_INVALID, "n_points too large");
   if (n_buckets < 0 || n_buckets > DSDF_MAX_BUCKETS) return fail(DSDF_E_INVALID, "n_buckets %d out of range [0, %d]", n_buckets, DSDF_MAX_BUCKETS);
   size_t best = 0;
-  for (int fr = 32; fr <= FROWS; fr += 32)
-    for (int seg = 0; seg < 2; ++seg) best = std::max(best, make_plan(net, n_points, n_segments, false, seg != 0, n_buckets, fr).total);
+  for (int fr = 32; fr <= FROWS; fr += 32)      // (32-row workgroups double the per-workgroup partials: pick_path decides per call)
+    for (int seg = 0; seg < 2; ++seg)           // segment mode lays the workspace out differently
+      best = std::max(best, make_plan(net, n_points, n_segments, false, seg != 0, n_buckets, fr).total);
   *bytes = best;
   return 0;
 }
 
+int dsdf_workspace_bytes(const DsdfNet* net, int64_t n_points, int64_t n_segments, size_t* bytes) {
+  return dsdf_workspace_bytes_buckets(net, n_points, n_segments, 2, bytes);
+}
+
 int dsdf_dw_phase_supported(const DsdfNet* net) {
   TRY(validate(net));
-  return fused_enabled() && fused_eligible(net) ? 1 : 0;
+  return pick_path(net, 0, ENTRY_TRAIN, Switches::read()).fused ? 1 : 0;
 }
 
 int dsdf_grad_buckets(const DsdfNet* net, int32_t n_buckets, int32_t* first_layer, int64_t* arena_off) {
@@ -1324,24 +1438,18 @@ int dsdf_materialize_weights(const DsdfNet* net, const float* params, float* pac
 
 int dsdf_decode(const DsdfNet* net, const float* packed, const float* params, const float* input, int64_t ld_in,
                 int64_t n, float* sdf_out, void* ws, size_t ws_bytes, void* stream) {
-  TRY(check_common(net, packed, params, ws));
+  const Switches sw = Switches::read();
+  TRY(check_common(net, sw, packed, params, ws));
   if (n == 0) return 0;
   if (!input || !sdf_out || n < 0 || ld_in < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in");
-  const Plan P = make_plan(net, n, 0, true, false, 2, pick_frows(net, n), &t_last_plan);
+  const Path path = pick_path(net, n, ENTRY_INFER, sw);
+  const Plan P = make_plan(net, n, 0, true, false, 2, path.frows, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   TRY(run_gather(net, P, ws, nullptr, nullptr, input, ld_in, n, st));
-  if (fused_enabled() && fused_eligible(net))
-    return run_fused_forward(net, P, ws, packed, params, n, 0, nullptr, 0, false, sdf_out, nullptr, st);
+  if (path.fused) return run_fused_forward(net, path, P, ws, packed, params, n, 0, nullptr, 0, false, sdf_out, nullptr, st);
   TRY(run_hidden_forward(net, P, ws, packed, params, n, 0, nullptr, 0, st, false));
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1;
-  LastArgs a;
-  memset(&a, 0, sizeof(a));
-  a.a = at<float>(ws, P.in_off[last]); a.lda = P.ld_in[last]; a.in = net->in_dim[last];
-  a.w = packed + pk.w_off[last]; a.b = params + L.bias_off[last]; a.n = (int)n; a.use_tanh = net->use_tanh;
+  LastArgs a = last_args(net, P, ws, packed, params, n);
   a.y_out = sdf_out;
   int blocks = (int)((n + 15) / 16);
   if (blocks > 2048) blocks = 2048;
@@ -1350,43 +1458,36 @@ int dsdf_decode(const DsdfNet* net, const float* packed, const float* params, co
 
 // dsdf_decode_latent's own layout: the one-row "scene table" index and U [1][2][FMAXW] behind it.  The caller's buffer is still
 // sized like dsdf_decode's (at least 16384 bytes); none of that plan's regions is touched.
-static Plan decode_latent_plan(const DsdfNet* net, int64_t n, size_t* scene_off, size_t* need, WsTable* rec) {
-  Plan P = make_plan(net, n, 0, true, false, 2, pick_frows(net, n));
-  const size_t guard = g_redzone.load(std::memory_order_relaxed);
-  size_t o = 0;
-  if (rec) rec->reset();
-  auto take = [&](const char* name, size_t bytes) {
-    const size_t r = o;
-    o += (size_t)rup((int64_t)bytes, 256) + guard;
-    if (rec) rec->add(name, -1, r, bytes);
-    return r;
-  };
-  *scene_off = take("dl_scene", 8);                                             // seg_scene[0] = 0: the "table" is the single latent row
-  P.hoistU_off = take("dl_hoistU", (size_t)2 * FMAXW * 4); P.ldu = FMAXW;      // U [1][2][512] behind it
-  *need = std::max(std::max<size_t>(P.total, 16384), o);
-  if (rec) rec->total = *need;
+static Plan decode_latent_plan(const DsdfNet* net, int64_t n, int frows, size_t* scene_off, size_t* need, WsTable* rec) {
+  Plan P = make_plan(net, n, 0, true, false, 2, frows);
+  WsCarver c(rec);
+  *scene_off = c.take("dl_scene", -1, 8);                                             // seg_scene[0] = 0: the "table" is the single latent row
+  P.hoistU_off = c.take("dl_hoistU", -1, (size_t)2 * FMAXW * 4); P.ldu = FMAXW;      // U [1][2][512] behind it
+  *need = c.finish(std::max(std::max<size_t>(P.total, 16384), c.o));
   return P;
 }
 
-static bool decode_latent_ok(const DsdfNet* net) {
-  return fused_enabled() && fused_eligible(net) && net->geom_dim <= FGEO && net->latent_size <= HOIST_MAXL &&
+static bool decode_latent_ok(const DsdfNet* net, const Path& path) {
+  return path.fused && net->geom_dim <= FGEO && net->latent_size <= HOIST_MAXL &&
          net->latent_size >= 1 && net->n_layers >= 3 && !last_layer_skip(net);
 }
 
 int dsdf_decode_latent_supported(const DsdfNet* net) {
   TRY(validate(net));
-  return decode_latent_ok(net) ? 1 : 0;
+  return decode_latent_ok(net, pick_path(net, 0, ENTRY_INFER, Switches::read())) ? 1 : 0;
 }
 
 int dsdf_decode_latent(const DsdfNet* net, const float* packed, const float* params, const float* latent, const float* xyz,
                        int64_t n, float* sdf_out, void* ws, size_t ws_bytes, void* stream) {
-  TRY(check_common(net, packed, params, ws));
+  const Switches sw = Switches::read();
+  TRY(check_common(net, sw, packed, params, ws));
   if (n == 0) return 0;
   if (!latent || !xyz || !sdf_out || n < 0) return fail(DSDF_E_INVALID, "bad latent/xyz/sdf_out");
-  if (!decode_latent_ok(net))
+  const Path path = pick_path(net, n, ENTRY_INFER, sw);
+  if (!decode_latent_ok(net, path))
     return fail(DSDF_E_INVALID, "dsdf_decode_latent needs the fused forward (widths <= 512, geom_dim <= 4): use dsdf_decode");
   size_t scene_off = 0, need = 0;
-  const Plan P = decode_latent_plan(net, n, &scene_off, &need, &t_last_plan);
+  const Plan P = decode_latent_plan(net, n, path.frows, &scene_off, &need, &t_last_plan);
   if (ws_bytes < need) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   // ONE segment covering every point: the segment-mode forward with the latent's products hoisted (fused.hpp FusedSeg)
@@ -1397,7 +1498,7 @@ int dsdf_decode_latent(const DsdfNet* net, const float* packed, const float* par
   FusedSeg seg;
   TRY(run_hoist(net, P, ws, packed, latent, &b, &seg, st));
   seg.wg_per_seg = (int)((n + P.frows - 1) / P.frows);  // every workgroup belongs to segment 0
-  return run_fused_forward(net, P, ws, packed, params, n, 0, nullptr, 0, false, sdf_out, nullptr, st, &seg);
+  return run_fused_forward(net, path, P, ws, packed, params, n, 0, nullptr, 0, false, sdf_out, nullptr, st, &seg);
 }
 
 // ---- debug only: red zones and the region table of the workspace planners (include/dsdf.h) ----------------
@@ -1436,7 +1537,7 @@ int dsdf_debug_ws_plan(const DsdfNet* net, int64_t n_points, int64_t n_segments,
     case DSDF_WS_PLAN_DECODE: make_plan(net, n_points, 0, true, false, 2, frows, &t_last_plan); return 0;
     case DSDF_WS_PLAN_DECODE_LATENT: {
       size_t scene_off = 0, need = 0;
-      decode_latent_plan(net, n_points, &scene_off, &need, &t_last_plan);
+      decode_latent_plan(net, n_points, frows, &scene_off, &need, &t_last_plan);
       return 0;
     }
     default: return fail(DSDF_E_INVALID, "plan kind %d", kind);
@@ -1446,25 +1547,20 @@ int dsdf_debug_ws_plan(const DsdfNet* net, int64_t n_points, int64_t n_segments,
 int dsdf_module_forward(const DsdfNet* net, const float* packed, const float* params, const float* input,
                         int64_t ld_in, int64_t n, int32_t training, const uint32_t* dropout_key, float* sdf_out,
                         void* ws, size_t ws_bytes, void* stream) {
-  TRY(check_common(net, packed, params, ws));
+  const Switches sw = Switches::read();
+  TRY(check_common(net, sw, packed, params, ws));
   if (n == 0) return 0;
   if (!input || !sdf_out || n < 0 || ld_in < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in");
   if (training && net->dropout_p > 0.f && net->dropout_mask && !dropout_key) return fail(DSDF_E_INVALID, "dropout_key is NULL");
-  const Plan P = make_plan(net, n, 0, false, false, 2, FROWS, &t_last_plan);
+  const Path path = pick_path(net, n, ENTRY_MODULE_FWD, sw);
+  const Plan P = make_plan(net, n, 0, false, false, 2, path.frows, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   TRY(run_gather(net, P, ws, nullptr, nullptr, input, ld_in, n, st, training, dropout_key, 0));
-  if (fused_enabled() && fused_eligible(net))
-    return run_fused_forward(net, P, ws, packed, params, n, training, dropout_key, 0, true, sdf_out, at<float>(ws, P.u_off), st);
+  if (path.fused)
+    return run_fused_forward(net, path, P, ws, packed, params, n, training, dropout_key, 0, true, sdf_out, at<float>(ws, P.u_off), st);
   TRY(run_hidden_forward(net, P, ws, packed, params, n, training, dropout_key, 0, st));
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1;
-  LastArgs a;
-  memset(&a, 0, sizeof(a));
-  a.a = at<float>(ws, P.in_off[last]); a.lda = P.ld_in[last]; a.in = net->in_dim[last];
-  a.w = packed + pk.w_off[last]; a.b = params + L.bias_off[last]; a.n = (int)n; a.use_tanh = net->use_tanh;
+  LastArgs a = last_args(net, P, ws, packed, params, n);
   a.y_out = sdf_out; a.u_save = at<float>(ws, P.u_off);
   return launch_last<LAST_FWD>(a, P.last_blocks, st);
 }
@@ -1473,38 +1569,29 @@ int dsdf_module_forward(const DsdfNet* net, const float* packed, const float* pa
 static int module_backward_impl(const DsdfNet* net, const float* packed, const float* params, const float* d_sdf, int64_t n,
                                 int32_t training, const uint32_t* dropout_key, float* grads, int32_t accumulate, float* d_input,
                                 int64_t ld_din, void* ws, size_t ws_bytes, void* stream, bool want_dw) {
-  TRY(check_common(net, packed, params, ws));
+  const Switches sw = Switches::read();
+  TRY(check_common(net, sw, packed, params, ws));
   if (n == 0) return 0;
   if (!d_sdf || (want_dw && !grads) || n < 0) return fail(DSDF_E_INVALID, "bad d_sdf/grads");
   if (d_input && ld_din < net->in_dim[0]) return fail(DSDF_E_INVALID, "ld_din too small");
   if (training && net->latent_dropout && d_input && !dropout_key)
     return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key for d/d(input))");
-  const Plan P = make_plan(net, n, 0, false, false, 2, FROWS, &t_last_plan);
+  const Path path = pick_path(net, n, ENTRY_MODULE_BWD, sw);
+  const Plan P = make_plan(net, n, 0, false, false, 2, path.frows, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1;
-  LastArgs a;
-  memset(&a, 0, sizeof(a));
-  a.a = at<float>(ws, P.in_off[last]); a.lda = P.ld_in[last]; a.in = net->in_dim[last];
-  a.w = packed + pk.w_off[last]; a.b = params + L.bias_off[last]; a.n = (int)n; a.use_tanh = net->use_tanh;
-  a.d_sdf = d_sdf; a.u_in = at<float>(ws, P.u_off);
-  const bool fusedb = fused_enabled() && fused_eligible(net);
-  a.dp_prev = at<float>(ws, P.dp_off[0]);
-  a.lddp = P.ld_dp; a.mask_scale = mask_scale_of(net, last - 1, training);
-  a.part_dw = at<float>(ws, P.part_off); a.ld_part = P.ld_part;
-  a.part_colsum = at<float>(ws, P.part_off) + P.ld_in[last];
-  a.part_db = at<float>(ws, P.partdb_off); a.part_loss = at<float>(ws, P.partloss_off);
-  a.n_act = net->out_dim[last - 1];
-  if (last_layer_skip(net) && d_input) { a.dz = at<float>(ws, P.dzB_off); a.ldz = P.ldz; a.dz_cols = P.W0; }
   bool used_dzB = false;
-  if (fusedb) {
+  if (path.fused) {
     FusedBwdHead h = make_head(net, P, ws, packed, params, HEAD_EXT, training);
     h.d_sdf = d_sdf; h.u_in = at<float>(ws, P.u_off);
-    TRY(run_backward_fused(net, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, want_dw, h));
+    TRY(run_backward_fused(net, path, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, want_dw, h));
   } else {
+    const Packed pk = packed_layout(net);
+    const int last = net->n_layers - 1;
+    LastArgs a = last_args(net, P, ws, packed, params, n);
+    last_args_backward(a, net, P, ws, training);
+    a.d_sdf = d_sdf; a.u_in = at<float>(ws, P.u_off);
+    if (last_layer_skip(net) && d_input) { a.dz = at<float>(ws, P.dzB_off); a.ldz = P.ldz; a.dz_cols = P.W0; }
     TRY(launch_last<LAST_BWD_EXT>(a, P.last_blocks, st));
     bool xyz_acc = false;
     if (d_input && net->xyz_in_all && last > 0) {   // the last layer's input is [a || xyz] too: its own d/d(xyz) opens the running sum
@@ -1519,10 +1606,7 @@ static int module_backward_impl(const DsdfNet* net, const float* packed, const f
                      (d_input && net->xyz_in_all) ? &xyz_acc : nullptr));
     if (last_layer_skip(net) && d_input) used_dzB = true;      // (last_layer_kernel wrote it)
     if (d_input) {
-      const long long tot = (long long)n * P.W0;
-      hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dzA_off), P.ldz,
-                         used_dzB ? at<float>(ws, P.dzB_off) : nullptr, P.ldz, d_input, (long long)ld_din, (int)n, P.W0);
-      LAUNCH_OK("add2_kernel");
+      TRY(add_dz_to_input(P, ws, n, used_dzB, d_input, ld_din, st));
       if (xyz_acc) {
         const long long tx = (long long)n * net->geom_dim;
         hipLaunchKernelGGL(acc_cols_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dxz_off[1]), 4, d_input,
@@ -1532,12 +1616,7 @@ static int module_backward_impl(const DsdfNet* net, const float* packed, const f
     }
     return 0;
   }
-  if (d_input) {
-    const long long tot = (long long)n * P.W0;
-    hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dzA_off), P.ldz,
-                       used_dzB ? at<float>(ws, P.dzB_off) : nullptr, P.ldz, d_input, (long long)ld_din, (int)n, P.W0);
-    LAUNCH_OK("add2_kernel");
-  }
+  if (d_input) TRY(add_dz_to_input(P, ws, n, used_dzB, d_input, ld_din, st));
   return 0;
 }
 
@@ -1561,7 +1640,7 @@ int dsdf_module_input_grad(const DsdfNet* net, const float* packed, const float*
 // Layer-by-layer MFMA GEMM launches (gemm.hpp) -- this is the one-extra-pass tool of mesh.py:420, not the training hot path.
 int dsdf_module_jvp(const DsdfNet* net, const float* packed, const float* params, const float* tangent, int64_t ld_t,
                     int64_t n, int32_t training, const uint32_t* dropout_key, float* jvp_out, void* ws, size_t ws_bytes, void* stream) {
-  TRY(check_common(net, packed, params, ws));
+  TRY(check_common(net, Switches::read(), packed, params, ws));
   if (n == 0) return 0;
   if (!tangent || !jvp_out || n < 0 || ld_t < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad tangent/jvp_out/ld_t");
   const bool lat_drop = net->latent_dropout && training && net->latent_size > 0;
@@ -1650,7 +1729,8 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
                   const DsdfBatch* b, const DsdfLossCfg* cfg, float* grads, float* dlat, float* loss_out, float* sdf_out,
                   int32_t accumulate, void* ws, size_t ws_bytes, void* stream, const FuseAdam* fz, int* adam_fused) {
   if (adam_fused) *adam_fused = 0;
-  TRY(check_common(net, packed, params, ws));
+  const Switches sw = Switches::read();
+  TRY(check_common(net, sw, packed, params, ws));
   if (!b || !cfg || !latent_table || !grads || !dlat || !loss_out) return fail(DSDF_E_INVALID, "NULL argument");
   const int64_t n = b->n_points, R = b->n_segments;
   if (n <= 0 || R <= 0 || n_scenes <= 0) return fail(DSDF_E_INVALID, "empty batch (n_points %lld, n_segments %lld)", (long long)n, (long long)R);
@@ -1660,16 +1740,10 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
   // Segment mode: the batch is scenes x samples with every segment a whole number of 64-row workgroups, so a workgroup
   // sees ONE latent vector: its products with the weights are hoisted out of the per-point work (fused.hpp FusedSeg),
   // and the latent gradient / the x0 columns of the weight gradients come from per-workgroup column sums.
-  const bool fusedb = fused_enabled() && fused_eligible(net);
+  const Path path = pick_path(net, n, ENTRY_TRAIN, sw);
+  const bool fusedb = path.fused, merged = path.merged;
   const int skip_l = skip_layer(net);
-  // (32-row workgroups exist for the merged forward + backward launch only)
-  const bool can_merge = fusedb && !getenv("DSDF_NO_MERGE")
-#ifdef DSDF_LAB
-                         && !getenv("DSDF_LAB_DBG")
-#endif
-      ;
-  const int frows = can_merge ? pick_frows(net, n, true) : FROWS;
-  const bool segsum = fusedb && b->seg_len > 0 && b->seg_len % frows == 0 && b->seg_len * R == n && net->n_layers > 2 &&
+  const bool segsum = fusedb && b->seg_len > 0 && b->seg_len % path.frows == 0 && b->seg_len * R == n && net->n_layers > 2 &&
                       skip_l != net->n_layers - 2 &&   // the deepest hidden layer's dP column sums live in the head's partials
                       !last_layer_skip(net) &&
                       net->geom_dim <= FGEO && net->latent_size >= 1 && net->latent_size <= HOIST_MAXL;   // (config 5 too: bf16 rounding is element-wise
@@ -1678,7 +1752,7 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
   if (nbk < 0 || nbk > DSDF_MAX_BUCKETS) return fail(DSDF_E_INVALID, "dw_buckets %d out of range [0, %d]", nbk, DSDF_MAX_BUCKETS);
   if (phase < 0 || (nbk <= 1 ? phase != 0 : phase < 1 || phase > nbk))
     return fail(DSDF_E_INVALID, "dw_phase %d out of range for dw_buckets %d (0 without buckets, 1..K with K >= 2)", phase, nbk);
-  const Plan P = make_plan(net, n, R, false, segsum, nbk, frows, &t_last_plan);
+  const Plan P = make_plan(net, n, R, false, segsum, nbk, path.frows, &t_last_plan);
   if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
   hipStream_t st = (hipStream_t)stream;
   const int Lc = net->latent_size;
@@ -1690,7 +1764,7 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
     const FusedBwdHead h0 = make_head(net, P, ws, packed, params, HEAD_TRAIN, cfg->training);
     const SegBwd sb0{&seg0, b->seg_scene, latent_table, (int)R, nullptr, nullptr, nullptr};
     bool used = false;
-    return run_backward_fused(net, P, ws, packed, params, n, cfg->training, grads, 0, segsum ? 0 : Lc, &used, st, true, h0, nullptr,
+    return run_backward_fused(net, path, P, ws, packed, params, n, cfg->training, grads, 0, segsum ? 0 : Lc, &used, st, true, h0, nullptr,
                               segsum ? &sb0 : nullptr, nullptr, phase);
   }
 
@@ -1706,40 +1780,28 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
   }
   FusedSeg seg;
   memset(&seg, 0, sizeof(seg));
-  FusedFwdArgs fwd_args;                                   // fp32 fused path: forward + backward go out as ONE launch below
-  const bool merged = can_merge;   // (DSDF_NO_MERGE -- lab / tests: forward and backward as two launches in fp32 too; lab builds with
-                                   // DSDF_LAB_DBG: per-layer stamps are dumped after a forward launch of its own)
+  FusedFwdArgs fwd_args;                                   // merged: forward + backward go out as ONE launch below
   if (segsum) {
     const HoistRenorm hr{cfg->code_bound > 0.f ? cfg->code_bound : 0.f, dlat, accumulate ? 0 : (long long)n_scenes * Lc};
     TRY(run_hoist(net, P, ws, packed, latent_table, b, &seg, st, &hr));
-    TRY(run_fused_forward(net, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, true,
+    TRY(run_fused_forward(net, path, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, true,
                           nullptr, nullptr, st, &seg, merged ? &fwd_args : nullptr));
   } else {
     TRY(run_gather(net, P, ws, latent_table, b, nullptr, 0, n, st, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset));
     if (fusedb)
-      TRY(run_fused_forward(net, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, true,
+      TRY(run_fused_forward(net, path, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, true,
                             nullptr, nullptr, st, nullptr, merged ? &fwd_args : nullptr));
     else
       TRY(run_hidden_forward(net, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, st));
   }
 
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1;
-  LastArgs a;
-  memset(&a, 0, sizeof(a));
-  a.a = at<float>(ws, P.in_off[last]); a.lda = P.ld_in[last]; a.in = net->in_dim[last];
-  a.w = packed + pk.w_off[last]; a.b = params + L.bias_off[last]; a.n = (int)n; a.use_tanh = net->use_tanh;
-  a.y_out = sdf_out; a.gt = b->sdf_gt; a.delta = cfg->clamp_dist; a.inv_n = 1.0f / (float)b->n_norm;
-  a.dp_prev = at<float>(ws, P.dp_off[0]);
-  a.lddp = P.ld_dp; a.mask_scale = mask_scale_of(net, last - 1, cfg->training);
-  a.part_dw = at<float>(ws, P.part_off); a.ld_part = P.ld_part;
-  a.part_colsum = at<float>(ws, P.part_off) + P.ld_in[last];
-  a.part_db = at<float>(ws, P.partdb_off); a.part_loss = at<float>(ws, P.partloss_off);
-  a.n_act = net->out_dim[last - 1];
-  if (last_layer_skip(net)) { a.dz = at<float>(ws, P.dzB_off); a.ldz = P.ldz; a.dz_cols = Lc; }
-  if (!fusedb) TRY(launch_last<LAST_TRAIN>(a, P.last_blocks, st));
+  if (!fusedb) {
+    LastArgs a = last_args(net, P, ws, packed, params, n);
+    last_args_backward(a, net, P, ws, cfg->training);
+    a.y_out = sdf_out; a.gt = b->sdf_gt; a.delta = cfg->clamp_dist; a.inv_n = 1.0f / (float)b->n_norm;
+    if (last_layer_skip(net)) { a.dz = at<float>(ws, P.dzB_off); a.ldz = P.ldz; a.dz_cols = Lc; }
+    TRY(launch_last<LAST_TRAIN>(a, P.last_blocks, st));
+  }
 
   bool used_dzB = false;
   const bool want_dw = cfg->frozen_decoder == 0;
@@ -1758,7 +1820,7 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
     h.gt = b->sdf_gt; h.delta = cfg->clamp_dist; h.inv_n = 1.0f / (float)b->n_norm; h.y_out = sdf_out;
     const FuseAdam* use = (fz != nullptr && want_dw && !accumulate) ? fz : nullptr;
     const SegBwd sb{&seg, b->seg_scene, latent_table, (int)R, &sc, &scatter_done, sc.zr};
-    TRY(run_backward_fused(net, P, ws, packed, params, n, cfg->training, grads, accumulate, segsum ? 0 : Lc, &used_dzB, st, want_dw, h,
+    TRY(run_backward_fused(net, path, P, ws, packed, params, n, cfg->training, grads, accumulate, segsum ? 0 : Lc, &used_dzB, st, want_dw, h,
                            use, segsum ? &sb : nullptr, merged ? &fwd_args : nullptr, phase));
     if (use != nullptr && adam_fused) *adam_fused = 1;
   } else {
@@ -1805,10 +1867,9 @@ int dsdf_grad_norm(const float* grads, int64_t n, float max_norm, float* norm_ou
   if (!grads || !norm_out || !coef_out || !ws || n <= 0) return fail(DSDF_E_INVALID, "bad arguments");
   int blocks = (int)((n + 4095) / 4096);
   if (blocks > 1024) blocks = 1024;
-  t_last_plan.reset();
-  t_last_plan.add("gn_partials", -1, 0, (size_t)blocks * 4);
-  t_last_plan.total = (size_t)blocks * 4 + g_redzone.load(std::memory_order_relaxed);
-  if (ws_bytes < t_last_plan.total) return fail(DSDF_E_WORKSPACE, "workspace too small");
+  WsCarver c(&t_last_plan, 1);
+  c.take("gn_partials", -1, (size_t)blocks * 4);
+  if (ws_bytes < c.finish(c.o)) return fail(DSDF_E_WORKSPACE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(blocks), dim3(256), 0, st, grads, (long long)n, (float*)ws);
   LAUNCH_OK("sumsq_partial_kernel");
@@ -2004,13 +2065,10 @@ int dsdf_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float
   memset(&f, 0, sizeof(f));
   if (N > 2048 || ldc != N) return fail(DSDF_E_INVALID, "gemm_tn test entry needs ldc == N <= 2048");
   f.slabs = t.C; f.nsplit = nsplit; f.slab = slab; f.ldc = (int)ldc; f.colsum = nullptr; f.npart = 0; f.ldcs = 0;
-  const size_t guard = g_redzone.load(std::memory_order_relaxed), db_off = (size_t)nsplit * slab * 4 + guard;
-  t_last_plan.reset();
-  t_last_plan.add("tn_slabs", -1, 0, (size_t)nsplit * slab * 4);
-  t_last_plan.add("tn_db", -1, db_off, (size_t)M * 4);
-  t_last_plan.total = db_off + (size_t)M * 4 + guard;
-  f.dv = C; f.db = at<float>(ws, db_off);               // scratch row of M floats behind the slabs
-  if (ws_bytes < t_last_plan.total) return fail(DSDF_E_WORKSPACE, "gemm_tn workspace too small");
+  WsCarver c(&t_last_plan, 1);
+  c.take("tn_slabs", -1, (size_t)nsplit * slab * 4);
+  f.dv = C; f.db = at<float>(ws, c.take("tn_db", -1, (size_t)M * 4));   // scratch row of M floats behind the slabs
+  if (ws_bytes < c.finish(c.o)) return fail(DSDF_E_WORKSPACE, "gemm_tn workspace too small");
   f.out = (int)M; f.in = (int)N;
   hipLaunchKernelGGL(finalize_layer_kernel, dim3((unsigned)M), dim3(256), 0, st, f);
   LAUNCH_OK("finalize_layer_kernel(test)");
@@ -2040,24 +2098,15 @@ int mc_plan(int32_t nx, int32_t ny, int32_t nz, McPlan* P, WsTable* rec = nullpt
     return fail(DSDF_E_INVALID, "marching cubes: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
   P->npts = (int64_t)nx * ny * nz;
   P->nblocks = (P->npts + MC_BLOCK - 1) / MC_BLOCK;
-  size_t o = 0;
-  const size_t guard = g_redzone.load(std::memory_order_relaxed);
-  if (rec) rec->reset();
-  auto take = [&](const char* name, size_t bytes) {
-    const size_t at = o;
-    o = (size_t)rup((int64_t)(o + bytes), 256) + guard;
-    if (rec) rec->add(name, -1, at, bytes);
-    return at;
-  };
-  P->mask = take("mc_mask", (size_t)P->npts);
-  P->cas = take("mc_cas", (size_t)P->npts);
-  P->vbase = take("mc_vbase", (size_t)P->npts * 4);
-  P->bv = take("mc_bv", (size_t)P->nblocks * 4);
-  P->bf = take("mc_bf", (size_t)P->nblocks * 4);
-  P->ov = take("mc_ov", (size_t)(P->nblocks + 1) * 8);
-  P->of = take("mc_of", (size_t)(P->nblocks + 1) * 8);
-  P->total = o;
-  if (rec) rec->total = o;
+  WsCarver c(rec);
+  P->mask = c.take("mc_mask", -1, (size_t)P->npts);
+  P->cas = c.take("mc_cas", -1, (size_t)P->npts);
+  P->vbase = c.take("mc_vbase", -1, (size_t)P->npts * 4);
+  P->bv = c.take("mc_bv", -1, (size_t)P->nblocks * 4);
+  P->bf = c.take("mc_bf", -1, (size_t)P->nblocks * 4);
+  P->ov = c.take("mc_ov", -1, (size_t)(P->nblocks + 1) * 8);
+  P->of = c.take("mc_of", -1, (size_t)(P->nblocks + 1) * 8);
+  P->total = c.finish(c.o);
   return 0;
 }
 
@@ -2172,9 +2221,9 @@ int msdf_plan(int64_t nf, int64_t nq, MsdfPlan* P, WsTable* rec = nullptr) {
   P->n_splits = (int32_t)ns;
   P->chunk = (int32_t)((nf + ns - 1) / ns);
   P->tri = (size_t)nf * sizeof(MsdfTri);
-  const size_t part = (size_t)ns * (size_t)nq * 12;          // d2, face, winding per (split, query): one block
-  P->ws = part + g_redzone.load(std::memory_order_relaxed);
-  if (rec) { rec->reset(); rec->add("msdf_partials", -1, 0, part); rec->total = P->ws; }
+  WsCarver c(rec, 1);
+  c.take("msdf_partials", -1, (size_t)ns * (size_t)nq * 12);          // d2, face, winding per (split, query): one block
+  P->ws = c.finish(c.o);
   return 0;
 }
 }  // namespace
@@ -2264,12 +2313,9 @@ int nn_plan(int64_t nq, int64_t nr, NnPlan* P, WsTable* rec = nullptr) {
   P->n_splits = (int32_t)ns;
   P->chunk = (int32_t)((nr + ns - 1) / ns);
   const size_t part = ns > 1 ? (size_t)ns * (size_t)nq * 8 : 0;          // d2 and index per (split, query); one split writes the outputs
-  P->ws = part ? part + g_redzone.load(std::memory_order_relaxed) : 0;
-  if (rec) {
-    rec->reset();
-    if (part) rec->add("nn_partials", -1, 0, part);
-    rec->total = P->ws;
-  }
+  WsCarver c(rec, 1);
+  if (part) c.take("nn_partials", -1, part);
+  P->ws = c.finish(c.o);
   return 0;
 }
 
@@ -2527,8 +2573,9 @@ int msd_plan(int64_t n_verts, int64_t ncp, int32_t L, MsdPlan* P, WsTable* rec =
   P->n_tiles = (int32_t)((P->per + MSD_VJP_TILE - 1) / MSD_VJP_TILE);
   if (P->n_tiles > 65535) return fail(DSDF_E_INVALID, "mesh derivative: control net of %lld floats (the adjoint takes at most %lld)", (long long)P->per, 65535ll * MSD_VJP_TILE);
   P->part = (size_t)P->n_parts * (size_t)P->per * 4;
-  P->ws = (size_t)rup((int64_t)P->part, 256) + g_redzone.load(std::memory_order_relaxed);
-  if (rec) { rec->reset(); rec->add("msd_vjp_part", -1, 0, P->part); rec->total = P->ws; }
+  WsCarver c(rec);
+  c.take("msd_vjp_part", -1, P->part);
+  P->ws = c.finish(c.o);
   return 0;
 }
 
