@@ -349,7 +349,8 @@ int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width);
  *             a zero-area face counts as its longest edge (or its point).  face = the LOWEST index attaining the minimum,
  *             closest = c on that face.
  *   winding   sum over faces of 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) / 4 pi, a, b, c = vertices - p
- *             (Van Oosterom-Strackee); zero-area faces add nothing.
+ *             (Van Oosterom-Strackee); zero-area faces add nothing, and neither does a face one of whose vertices is p itself
+ *             (the angle is undefined there).
  *   sdf       p is inside iff floor(|winding| + 0.5) is odd: sdf = inside ? -sqrt(sqr_dist) : sqrt(sqr_dist), negated when
  *             flip_sign.  For a closed mesh this is the parity of a ray test and does not depend on face orientation.
  * Use: dsdf_msdf_plan, dsdf_msdf_prepare once per mesh (verts [n_verts][3] fp32, faces [n_faces][3] int32, 0-based; indices are
@@ -360,6 +361,13 @@ int dsdf_mc_case_table(int8_t* table, size_t table_bytes, int32_t* width);
  * face range is cut into n_splits = min(ceil(2048 / that), floor(n_faces / 1024), 64) contiguous pieces (at least 1), one
  * workgroup per (query block, piece), combined in piece order without atomics: sqr_dist, face and closest do not depend on
  * the split, winding only through its summation order.  Two identical calls give identical bytes.
+ * Accuracy and range: a face is zero-area when |ab x ac|^2 <= 1e-14 * (its longest edge)^4, evaluated in fp64 on the fp32
+ * vertices.  For every other face -- slivers down to that threshold included -- sqrt(sqr_dist) and closest are good to a few 1e-7
+ * of the distance from p to the face's vertices, and winding to ~1e-5 of a turn at distances above 1e-3 of the face's size: the
+ * face normal and the denominator of the solid angle are taken in fp64.  The differences p - a are formed first, so a translated
+ * mesh costs only the rounding of its fp32 coordinates.  Scaling vertices and queries by a power of two scales sqr_dist, closest
+ * and sdf exactly and leaves face and the inside decision unchanged, as long as squared lengths, face areas and their products
+ * with a distance (a length cubed) remain normal fp32 numbers: edge lengths and distances within about [2^-30, 2^30].
  * n_faces and n_queries must fit int32.  n_queries == 0 is valid and launches nothing. */
 int dsdf_msdf_plan(int64_t n_faces, int64_t n_queries, size_t* tri_bytes, size_t* ws_bytes, int32_t* n_splits); /* [host] */
 int dsdf_msdf_prepare(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, void* tri, size_t tri_bytes,

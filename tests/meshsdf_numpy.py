@@ -1,8 +1,8 @@
 """fp64 numpy oracle of the mesh SDF (include/dsdf.h dsdf_msdf_*, csrc/meshsdf.hpp) and the test meshes.  No torch.
 
 Oracle, restated from the spec: closest point of the closed triangle by Ericson's region tests (Real-Time Collision Detection
-5.1.5) -- a zero-area face by its three edges instead --, squared distance from the explicit difference vector, lowest face
-index on ties; winding number = sum of Van Oosterom-Strackee solid angles / 4 pi; inside iff floor(|w| + 0.5) is odd.  The
+5.1.5; va, vb, vc from triple products with the normal) -- a zero-area face by its three edges instead --, squared distance
+from the explicit difference vector, lowest face index on ties; winding number = sum of Van Oosterom-Strackee solid angles / 4 pi; inside iff floor(|w| + 0.5) is odd.  The
 inputs are rounded to fp32 first (what the kernel sees), then everything runs in fp64, queries in chunks.
 """
 import numpy as np
@@ -20,52 +20,67 @@ def _segment(p, a, b):
     return a + np.clip(t, 0.0, 1.0)[..., None] * ab
 
 
+def _dot(x, y):
+    return np.einsum("...i,...i->...", x, y)
+
+
+def _ericson(p, a, b, c):
+    """(d1 .. d6, va, vb, vc, ab, ac) of Ericson's test for points p against triangles (a, b, c), broadcast, fp64.
+    d3 .. d6 follow from d1, d2 and the edges' dot products (bp = ap - ab, cp = ap - ac).  va, vb, vc are |n|^2 times the
+    barycentric coordinates.  Ericson takes them from the dot products (vc = d1 d4 - d3 d2, ...), whose rounding is absolute,
+    ~1e-16 of |ab|^2 |ap|^2: on a sliver of height 1e-6 (|n|^2 = 1e-12) that leaves the interior quotient four digits.  By
+    Lagrange's identity they are triple products with the normal, vc = n . (ab x ap) = ap . (n x ab) and so on, whose rounding
+    is relative to |n|; the vectors n x ab, ac x n, n x bc belong to the face alone."""
+    ab, ac, ap = b - a, c - a, p - a
+    d1, d2 = _dot(ab, ap), _dot(ac, ap)
+    bb, bc, cc = _dot(ab, ab), _dot(ab, ac), _dot(ac, ac)
+    d3, d4, d5, d6 = d1 - bb, d2 - bc, d1 - bc, d2 - cc
+    n = np.cross(ab, ac)
+    vc, vb = _dot(ap, np.cross(n, ab)), _dot(ap, np.cross(ac, n))
+    va = _dot(ap, np.cross(n, ac - ab)) + _dot(n, n)             # bp . (n x bc), with ab . (n x bc) = -|n|^2
+    return (d1, d2, d3, d4, d5, d6), (va, vb, vc), ab, ac
+
+
+def _region_tests(d, v):
+    """Ericson's six tests in his order: A, B, AB, C, AC, BC (interior: none of them)."""
+    (d1, d2, d3, d4, d5, d6), (va, vb, vc) = d, v
+    return [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+            (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0)]
+
+
 def closest_points(p, a, b, c):
     """Closest points of triangles (a, b, c) to points p (all [..., 3], broadcast), fp64.  Ericson's regions; degenerate
     triangles (zero area) take the closest of their three edges."""
-    ab, ac, ap = b - a, c - a, p - a
-    d1, d2 = (ab * ap).sum(-1), (ac * ap).sum(-1)
-    bp = p - b
-    d3, d4 = (ab * bp).sum(-1), (ac * bp).sum(-1)
-    cp = p - c
-    d5, d6 = (ab * cp).sum(-1), (ac * cp).sum(-1)
-    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
-    n = np.cross(ab, ac)
-    nn = (n * n).sum(-1)
-    lmax = np.maximum(np.maximum((ab * ab).sum(-1), (ac * ac).sum(-1)), ((c - b) ** 2).sum(-1))
+    d, vs, ab, ac = _ericson(p, a, b, c)
+    (d1, d2, d3, d4, d5, d6), (va, vb, vc) = d, vs
+    nn = _dot(np.cross(ab, ac), np.cross(ab, ac))
+    lmax = np.maximum(np.maximum(_dot(ab, ab), _dot(ac, ac)), _dot(c - b, c - b))
     degen = nn <= 1e-14 * lmax * lmax
     with np.errstate(divide="ignore", invalid="ignore"):
         den = va + vb + vc
-        v_in, w_in = vb / den, vc / den
-        t_ab = d1 / (d1 - d3)
-        t_ac = d2 / (d2 - d6)
-        t_bc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
-        out = a + v_in[..., None] * ab + w_in[..., None] * ac        # NaN only on degenerate faces, replaced below
-    regions = [  # Ericson's order reversed: later assignments win
-        ((va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0), lambda: b + t_bc[..., None] * (c - b)),
-        ((vb <= 0) & (d2 >= 0) & (d6 <= 0), lambda: a + t_ac[..., None] * ac),
-        ((d6 >= 0) & (d5 <= d6), lambda: np.broadcast_to(c, out.shape)),
-        ((vc <= 0) & (d1 >= 0) & (d3 <= 0), lambda: a + t_ab[..., None] * ab),
-        ((d3 >= 0) & (d4 <= d3), lambda: np.broadcast_to(b, out.shape)),
-        ((d1 <= 0) & (d2 <= 0), lambda: np.broadcast_to(a, out.shape)),
-    ]
-    for m, f in regions:
-        out = np.where(m[..., None], f(), out)
+        v, w = vb / den, vc / den                                  # interior; NaN only on degenerate faces, replaced below
+        t_ab, t_ac, t_bc = d1 / (d1 - d3), d2 / (d2 - d6), (d4 - d3) / ((d4 - d3) + (d5 - d6))
+    one, zero = np.ones_like(v), np.zeros_like(v)
+    tests = _region_tests(d, vs)
+    for m, vv, ww in reversed(list(zip(tests, (zero, one, t_ab, zero, zero, 1 - t_bc), (zero, zero, zero, one, t_ac, t_bc)))):
+        v, w = np.where(m, vv, v), np.where(m, ww, w)              # the first match in Ericson's order is assigned last
+    out = a + v[..., None] * ab + w[..., None] * ac
     if np.any(degen):
         s = [_segment(p, a, b), _segment(p, b, c), _segment(p, c, a)]
-        d = np.stack([((p - x) ** 2).sum(-1) for x in s], -1)
-        k = np.argmin(d, -1)
+        dd = np.stack([((p - x) ** 2).sum(-1) for x in s], -1)
+        k = np.argmin(dd, -1)
         seg = np.choose(k[..., None], s)
         out = np.where(degen[..., None], seg, out)
     return out
 
 
 def solid_angles(p, a, b, c):
-    """Signed solid angles of triangles (a, b, c) seen from p (Van Oosterom-Strackee), fp64."""
+    """Signed solid angles of triangles (a, b, c) seen from p (Van Oosterom-Strackee), fp64.  The numerator A . (B x C) equals
+    A . ((b - a) x (c - a)): one dot product with the face's normal."""
     A, B, Cc = a - p, b - p, c - p
-    la, lb, lc = (np.linalg.norm(x, axis=-1) for x in (A, B, Cc))
-    det = (A * np.cross(B, Cc)).sum(-1)
-    den = la * lb * lc + (A * B).sum(-1) * lc + (B * Cc).sum(-1) * la + (Cc * A).sum(-1) * lb
+    la, lb, lc = (np.sqrt(_dot(x, x)) for x in (A, B, Cc))
+    det = _dot(A, np.cross(b - a, c - a))
+    den = la * lb * lc + _dot(A, B) * lc + _dot(B, Cc) * la + _dot(Cc, A) * lb
     return 2.0 * np.arctan2(det, den)
 
 
@@ -182,3 +197,111 @@ def hemisphere(subdiv=2):
     V, F = icosphere(subdiv)
     keep = (V[F][:, :, 2] >= -1e-9).all(1)
     return V, F[keep]
+
+
+# ---- a second fp64 formulation, region names, and the inputs of tests/test_gpu_meshsdf_faces.py -----------------------------
+def closest_points_edges_plane(p, a, b, c):
+    """Closest points of non-degenerate triangles by another route than closest_points: the nearest of the three clamped edge
+    segments, or the foot of the perpendicular on the plane when it lies on the inner side of all three edges (signed areas
+    against the normal).  fp64, broadcast like closest_points."""
+    p, a, b, c = np.broadcast_arrays(p, a, b, c)
+    n = np.cross(b - a, c - a)
+    s = [_segment(p, a, b), _segment(p, b, c), _segment(p, c, a)]
+    d = np.stack([((p - x) ** 2).sum(-1) for x in s], -1)
+    out = np.choose(np.argmin(d, -1)[..., None], s)
+    side = [(np.cross(y - x, p - x) * n).sum(-1) for x, y in ((a, b), (b, c), (c, a))]
+    foot = p - ((p - a) * n).sum(-1, keepdims=True) / (n * n).sum(-1, keepdims=True) * n
+    return np.where(((side[0] >= 0) & (side[1] >= 0) & (side[2] >= 0))[..., None], foot, out)
+
+
+REGIONS = ("A", "B", "AB", "C", "AC", "BC", "IN")
+
+
+def regions(p, a, b, c):
+    """Index into REGIONS of Ericson's region of each query, first match in his order (what closest_points resolves)."""
+    d, v, _, _ = _ericson(p, a, b, c)
+    tests = _region_tests(d, v)
+    out = np.full(tests[0].shape, 6)
+    for k in range(5, -1, -1):
+        out = np.where(tests[k], k, out)
+    return out
+
+
+def is_zero_area(V, F):
+    """The spec's zero-area rule per face, fp64 on the fp32-rounded vertices."""
+    V = _f32(V)
+    a, b, c = (V[np.asarray(F)[:, k]] for k in range(3))
+    n = (np.cross(b - a, c - a) ** 2).sum(-1)
+    lmax = np.max(np.stack([((b - a) ** 2).sum(-1), ((c - a) ** 2).sum(-1), ((c - b) ** 2).sum(-1)]), 0)
+    return n <= 1e-14 * lmax * lmax
+
+
+def random_rotation(g):
+    """A proper rotation drawn from generator g (QR of a Gaussian matrix)."""
+    q, r = np.linalg.qr(g.normal(size=(3, 3)))
+    q = q * np.sign(np.diag(r))
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+VERTEX_ORDERS = ((0, 1, 2), (1, 2, 0), (2, 0, 1), (0, 2, 1), (2, 1, 0), (1, 0, 2))
+SLIVER_HEIGHTS = (1e-1, 1e-2, 1e-3, 1e-4, 1e-5, 1e-6)
+SLIVER_QUERY_HEIGHTS = (0.0, 1e-3, -1e-3, 0.05, -0.05, 0.3, -0.3)
+
+
+def sliver(family, h, g):
+    """One triangle with unit longest edge and height h, in its own frame (long axis x, lateral y, normal z): 'needle' has its
+    apex over the middle third of the base, 'short_base' a base of length h."""
+    if family == "needle":
+        return np.array([[0, 0, 0], [1, 0, 0], [g.uniform(1 / 3, 2 / 3), h, 0]], dtype=np.float64)
+    return np.array([[0, 0, 0], [1, -h / 2, 0], [1, h / 2, 0]], dtype=np.float64)
+
+
+def sliver_queries(h, g, per_height=150):
+    """Queries over and beside a sliver of sliver(): along the long axis in [-0.2, 1.2], laterally N(0, 3h), at the heights of
+    SLIVER_QUERY_HEIGHTS."""
+    return np.concatenate([np.stack([g.uniform(-0.2, 1.2, per_height), g.normal(0, 3 * h, per_height),
+                                     np.full(per_height, z)], 1) for z in SLIVER_QUERY_HEIGHTS])
+
+
+def sliver_cases(h, seed=0, poses=3, per_height=150):
+    """The sliver sweep at height h: (family, V [3, 3], F [1, 3], P) for both families, every vertex order and `poses` seeded
+    rotations and offsets in [-0.5, 0.5]^3.  V and P are rounded to fp32 (what the kernel sees)."""
+    g = np.random.default_rng([seed, int(round(-np.log10(h)))])
+    for family in ("needle", "short_base"):
+        for _ in range(poses):
+            T, R, off = sliver(family, h, g), random_rotation(g), g.uniform(-0.5, 0.5, 3)
+            P = _f32(sliver_queries(h, g, per_height) @ R.T + off)
+            V = _f32(T @ R.T + off)
+            for order in VERTEX_ORDERS:
+                yield family, V, np.array([order], dtype=np.int64), P
+
+
+def plate(t, g):
+    """cube() scaled by (1, 1, t) and rotated: a closed mesh whose four side walls are slivers of aspect t."""
+    V, F = cube()
+    return (V * [1, 1, t]) @ random_rotation(g).T, F
+
+
+def plate_queries(V, F, t, g, n=1500):
+    """Queries around the rim and near the faces of plate(): random surface points plus offsets at the plate's own scale (t) and
+    at 0.05, half each, and a few far ones."""
+    f = g.integers(0, len(F), n)
+    u, v = g.random(n), g.random(n)
+    flip = u + v > 1
+    u, v = np.where(flip, 1 - u, u), np.where(flip, 1 - v, v)
+    a, b, c = V[F[f, 0]], V[F[f, 1]], V[F[f, 2]]
+    s = np.where(np.arange(n) % 2 == 0, 2 * t, 0.05)[:, None]
+    return np.concatenate([a + u[:, None] * (b - a) + v[:, None] * (c - a) + g.normal(0, 1, (n, 3)) * s,
+                           g.uniform(-1.5, 1.5, (n // 5, 3))])
+
+
+def ribbon(aspect, g, n=40):
+    """An open strip of n needle triangles: unit length, width `aspect`, cut across n / 2 times, so every triangle has height
+    ~aspect against a longest edge of 1; randomly rotated."""
+    k = n // 2
+    y = np.linspace(0, aspect, k + 1)
+    V = np.concatenate([np.stack([np.zeros(k + 1), y, np.zeros(k + 1)], 1), np.stack([np.ones(k + 1), y, np.zeros(k + 1)], 1)])
+    F = np.array([t for i in range(k) for t in ((i, k + 1 + i, k + 2 + i), (i, k + 2 + i, i + 1))], dtype=np.int64)
+    return V @ random_rotation(g).T, F

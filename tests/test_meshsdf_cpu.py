@@ -68,6 +68,43 @@ def test_oracle_degenerate_faces_are_segments():
     assert np.allclose(cp[3, 2], [0, 1, 0])
 
 
+@pytest.mark.parametrize("h", mn.SLIVER_HEIGHTS)
+def test_oracle_agrees_with_the_edges_and_plane_formulation_on_slivers(h):
+    """A second opinion on the inputs of tests/test_gpu_meshsdf_faces.py's sliver sweep (unit longest edge, height h): the
+    oracle's closest point against the nearest of three clamped edges and the plane foot, to 1e-9 of the longest edge.  With
+    va, vb, vc from Ericson's dot products the oracle missed this from h = 1e-4 down (2.7e-7 at 1e-5, 1.7e-5 at 1e-6)."""
+    worst = 0.0
+    for _, V, F, P in mn.sliver_cases(h):
+        a, b, c = (V[F[0, k]] for k in range(3))
+        assert abs(max(np.linalg.norm(b - a), np.linalg.norm(c - a), np.linalg.norm(c - b)) - 1.0) <= h * h + 1e-6
+        c1, c2 = mn.closest_points(P, a, b, c), mn.closest_points_edges_plane(P, a, b, c)
+        worst = max(worst, np.linalg.norm(c1 - c2, axis=1).max(),
+                    np.abs(np.linalg.norm(P - c1, axis=1) - np.linalg.norm(P - c2, axis=1)).max())
+    print("sliver", h, f"{worst:.2e}")
+    assert worst <= 1e-9
+
+
+def test_oracle_solid_angle_numerator_equals_the_textbook_triple_product():
+    """solid_angles takes Van Oosterom-Strackee's numerator A . (B x C) as A . ((b - a) x (c - a)).  On well-shaped faces both
+    are sums of products of O(1) numbers in fp64: they agree to 1e-14 of |A||B||C|, the angles to 1e-12 away from the faces."""
+    for V, F in (mn.icosphere(2), mn.torus(), mn.cube()):
+        P = np.random.default_rng(9).uniform(-1.2, 1.2, (300, 3))[:, None]
+        a, b, c = (V[F[:, k]][None] for k in range(3))
+        A, B, Cc = a - P, b - P, c - P
+        la, lb, lc = (np.linalg.norm(x, axis=-1) for x in (A, B, Cc))
+        det = (A * np.cross(B, Cc)).sum(-1)
+        assert np.abs(det - (A * np.cross(b - a, c - a)).sum(-1)).max() <= 1e-14 * (la * lb * lc).max()
+        den = la * lb * lc + (A * B).sum(-1) * lc + (B * Cc).sum(-1) * la + (Cc * A).sum(-1) * lb
+        far = np.sqrt(mn.mesh_query(V, F, P[:, 0])[0]) > 1e-3
+        assert np.abs(2 * np.arctan2(det, den) - mn.solid_angles(P, a, b, c))[far].max() <= 1e-12
+
+
+def test_oracle_region_names_cover_a_triangle():
+    a, b, c = np.array([0.0, 0, 0]), np.array([1.0, 0, 0]), np.array([0.0, 1, 0])
+    P = np.array([[-1, -1, 1], [2, -0.5, 0], [0.5, -1, 2], [-0.5, 2, 0], [-1, 0.5, 0], [1, 1, -1], [0.25, 0.25, 3.0]])
+    assert [mn.REGIONS[k] for k in mn.regions(P, a, b, c)] == ["A", "B", "AB", "C", "AC", "BC", "IN"]
+
+
 # ---- readers ------------------------------------------------------------------------------------------------------------------
 def test_ply_round_trip_through_write_ply(tmp_path):
     from deepsdf_amd.mesh import write_ply

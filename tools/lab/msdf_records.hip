@@ -45,11 +45,8 @@ __global__ __launch_bounds__(MSDF_BLOCK) void lds_query_kernel(const MsdfTri* __
       const MsdfTri t = tile[j];
       const float3 ap = make_float3(p.x - t.a.x, p.y - t.a.y, p.z - t.a.z);
       if (DIST) {
-        float v, w;
-        msdf_closest_bary(t, ap, v, w);
-        const float3 c = msdf_point(t, v, w);
-        const float3 d = f3sub(p, c);
-        const float d2 = f3dot(d, d);
+        float3 rel;
+        const float d2 = msdf_face_d2(t, ap, rel);
         const bool better = d2 < best;
         best = better ? d2 : best;
         bestf = better ? base + j : bestf;
