@@ -7,6 +7,28 @@ namespace dsdf {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// Single rounded fp32 operations, for arithmetic whose bits a host restatement has to reproduce.  hipcc contracts a * b + c into an
+// FMA by default and the __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn intrinsics are plain operators to it (and __fsqrt_rn is the
+// approximate root), so they promise nothing.  The pragma keeps the contract flag off the instruction itself, which survives
+// inlining: neither operand nor result of these is ever fused with a neighbouring operation.  The quotient is the correctly
+// rounded one (hipcc's default for fp32 division and sqrtf; the build sets no fast-math flag).
+__device__ __forceinline__ float rn_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float rn_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float rn_sub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ float rn_div(float a, float b) {
+#pragma clang fp contract(off)
+  return a / b;
+}
+
 // 32-bit avalanche mix; specification: oracle/deepsdf_oracle.py _lowbias32
 __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   x ^= x >> 16;

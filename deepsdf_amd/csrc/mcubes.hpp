@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "common.hpp"
 #include "mc_table.hpp"
 
 namespace dsdf {
@@ -179,13 +180,14 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_vertex_kernel(McGrid g, McWs w, M
   for (int a = 0; a < 3; ++a) {
     if (!((m >> a) & 1u)) continue;
     const float v1 = g.sdf[p + stride[a]];
-    // v0 and v1 lie on different sides of the level, so v1 != v0.  Every operation rounds on its own (no contraction).
-    const float t = __fdiv_rn(__fsub_rn(g.level, v0), __fsub_rn(v1, v0));
+    // v0 and v1 lie on different sides of the level, so v1 != v0.  Every operation rounds on its own: the rn_* helpers of
+    // common.hpp keep the compiler from contracting origin + x * spacing (or any other pair) into an FMA.
+    const float t = rn_div(rn_sub(g.level, v0), rn_sub(v1, v0));
     if (id < o.nv) {
       float* out = o.verts + id * 3;
       for (int b = 0; b < 3; ++b) {
-        const float x = b == a ? __fadd_rn((float)idx[b], t) : (float)idx[b];
-        out[b] = __fadd_rn(o.origin[b], __fmul_rn(x, o.spacing[b]));
+        const float x = b == a ? rn_add((float)idx[b], t) : (float)idx[b];
+        out[b] = rn_add(o.origin[b], rn_mul(x, o.spacing[b]));
       }
     }
     ++id;

@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "common.hpp"
+
 namespace dsdf {
 
 constexpr int MS_BLOCK = 256;
@@ -47,28 +49,13 @@ struct MsSpline {
 struct MsCapRec { int dim, cap; float m, c; };     // c = m * (1 - measure)
 struct MsCaps { int n; MsCapRec r[MS_MAX_CAPS]; };
 
-// Single rounded operations.  hipcc contracts a * b + c into an FMA by default and the __f*_rn intrinsics are plain operators to
-// it, so the coordinate arithmetic goes through these: the pragma keeps the contract flag off the instruction itself, which
-// survives inlining.
-__device__ __forceinline__ float ms_mul(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float ms_add(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float ms_sub(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
-
-__device__ __forceinline__ float ms_xo(int i, float vs, float org) { return ms_add(ms_mul((float)i, vs), org); }
+// The coordinate arithmetic goes through the single rounded operations of common.hpp (rn_mul, rn_add, rn_sub): never an FMA.
+__device__ __forceinline__ float ms_xo(int i, float vs, float org) { return rn_add(rn_mul((float)i, vs), org); }
 
 __device__ __forceinline__ float ms_fold(float x, float sub, float mod, float p, float scale) {
-  float r = fmodf(ms_sub(x, sub), mod);
-  if (r != 0.f && r < 0.f) r = ms_add(r, mod);          // floored remainder, mod > 0
-  return ms_sub(ms_mul(scale, fabsf(ms_sub(r, p))), 1.f);
+  float r = fmodf(rn_sub(x, sub), mod);
+  if (r != 0.f && r < 0.f) r = rn_add(r, mod);          // floored remainder, mod > 0
+  return rn_sub(rn_mul(scale, fabsf(rn_sub(r, p))), 1.f);
 }
 
 __device__ __forceinline__ void ms_index(int64_t idx, const MsGrid& g, int& i, int& j, int& k) {
@@ -219,15 +206,15 @@ __global__ __launch_bounds__(MS_BLOCK) void ms_caps_kernel(MsGrid g, MsCaps caps
   for (int r = 0; r < caps.n; ++r) {
     const MsCapRec R = caps.r[r];
     const float x = R.dim == 0 ? xo[0] : (R.dim == 1 ? xo[1] : xo[2]);
-    const float border = ms_mul(ms_sub(x, R.c), -R.m);
+    const float border = rn_mul(rn_sub(x, R.c), -R.m);
     if (R.cap < 0) { const float nb = -border; v = nb > v ? nb : v; }     // a NaN sdf stays, as with numpy's maximum
     else v = border < v ? border : v;
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float lo = -ms_mul(ms_sub(xo[a], -1.f), 1.f);
+    const float lo = -rn_mul(rn_sub(xo[a], -1.f), 1.f);
     v = lo > v ? lo : v;
-    const float hi = -ms_mul(ms_sub(xo[a], 1.f), -1.f);
+    const float hi = -rn_mul(rn_sub(xo[a], 1.f), -1.f);
     v = hi > v ? hi : v;
   }
   sdf[q] = v;

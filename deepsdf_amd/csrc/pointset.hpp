@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "common.hpp"
+
 namespace dsdf {
 
 constexpr int NN_BLOCK = 256;
@@ -153,18 +155,20 @@ __device__ __forceinline__ void surf_face(const float* __restrict__ V, int nv, c
   ac = make_float3(v[2].x - v[0].x, v[2].y - v[0].y, v[2].z - v[0].z);
 }
 
-// area = 0.5 * sqrt(n.n), n = ab x ac; every product and sum rounded on its own (no contraction), so the host can restate it
+// area = 0.5 * sqrt(n.n), n = ab x ac; every product, difference and sum rounded on its own -- the rn_* helpers of common.hpp keep
+// the compiler from contracting them -- and sqrtf is the correctly rounded root (__fsqrt_rn is not), so the host can restate the
+// areas bit for bit (tests/pointset_numpy.py face_areas_f32).  Once per mesh: the root's refinement costs nothing that matters.
 __global__ __launch_bounds__(SURF_BLOCK) void surf_area_kernel(const float* __restrict__ V, int nv, const int32_t* __restrict__ F,
                                                                int nf, float* __restrict__ area) {
   const int64_t f = (int64_t)blockIdx.x * SURF_BLOCK + threadIdx.x;
   if (f >= nf) return;
   float3 a, ab, ac;
   surf_face(V, nv, F, f, a, ab, ac);
-  const float nx = __fsub_rn(__fmul_rn(ab.y, ac.z), __fmul_rn(ab.z, ac.y));
-  const float ny = __fsub_rn(__fmul_rn(ab.z, ac.x), __fmul_rn(ab.x, ac.z));
-  const float nz = __fsub_rn(__fmul_rn(ab.x, ac.y), __fmul_rn(ab.y, ac.x));
-  const float nn = __fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz));
-  area[f] = 0.5f * __fsqrt_rn(nn);
+  const float nx = rn_sub(rn_mul(ab.y, ac.z), rn_mul(ab.z, ac.y));
+  const float ny = rn_sub(rn_mul(ab.z, ac.x), rn_mul(ab.x, ac.z));
+  const float nz = rn_sub(rn_mul(ab.x, ac.y), rn_mul(ab.y, ac.x));
+  const float nn = rn_add(rn_add(rn_mul(nx, nx), rn_mul(ny, ny)), rn_mul(nz, nz));
+  area[f] = 0.5f * sqrtf(nn);
 }
 
 // Inclusive scan of the workgroup's 256 lane values (Hillis-Steele in LDS); returns the lane's inclusive prefix.
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void surf_sample_kernel(const float* __
   philox4x32_10(ilo, 0u, ihi, 0u, k0, k1, w);
   const double total = cdf[nf - 1];
   const double r = __ull2double_rn(((uint64_t)w[0] << 32) | w[3]) * 5.421010862427522170037e-20;      // 2^-64
-  const double x = __dmul_rn(r, total);
+  const double x = __dmul_rn(r, total);                  // a lone product that is only compared: nothing to contract it with
   // first f with cdf[f] > x; x >= total (r rounds to 1): first f with cdf[f] >= total, the last face that added area
   const bool clamp = !(x < total);
   int lo = 0, hi = nf - 1;                               // the answer lies in [lo, hi]: cdf[nf - 1] = total satisfies both tests
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void surf_sample_kernel(const float* __
     lo = ok ? lo : mid + 1;
   }
   float u = (float)(w[1] >> 8) * 5.9604644775390625e-8f, v = (float)(w[2] >> 8) * 5.9604644775390625e-8f;      // 2^-24
-  if (__fadd_rn(u, v) > 1.f) {
+  if (__fadd_rn(u, v) > 1.f) {                           // u, v: 24-bit integers times 2^-24, exact; fusing either into the sum changes nothing
     u = 1.f - u;
     v = 1.f - v;
   }

@@ -405,7 +405,7 @@ int dsdf_mean_f64(const float* x, int64_t n, double* mean, void* ws, size_t ws_b
 /* Area-weighted sampling of a triangle mesh's surface (verts [n_verts][3] fp32, faces [n_faces][3] int32 as for dsdf_msdf_prepare).
  * dsdf_surf_prepare, once per mesh, fills the `surf` buffer (dsdf_surf_plan: *surf_bytes; 8-byte aligned):
  *   area  [n_faces] fp32 at byte *area_offset: 0.5 * sqrt(n.n), n = ab x ac, ab = b - a, ac = c - a, every product, difference and
- *         sum rounded to fp32 on its own (n.n = (nx nx + ny ny) + nz nz)
+ *         sum rounded to fp32 on its own (n.n = (nx nx + ny ny) + nz nz), the square root correctly rounded
  *   cdf   [n_faces] fp64 at byte 0: the inclusive prefix sums of area, formed in fp64 by a fixed three-pass scan over tiles of
  *         1024 faces (*n_tiles = ceil(n_faces / 1024)) -- deterministic, and within n_faces * 2^-53 * total of the exact sums;
  *         total = cdf[n_faces - 1]

@@ -4,6 +4,8 @@ tests/test_pointset_cpu.py and tests/test_gpu_pointset.py.  No torch, no device.
     nn_bruteforce       fp64 brute-force nearest neighbour on the fp32-rounded inputs, lowest index on ties
     philox4x32_10       Philox4x32-10 (Salmon et al., SC'11), vectorised over counters
     surface_samples     the sampler's face / barycentric / point rule in fp64, taking the fp32 face areas as input
+    face_areas_f32      the prepare pass's fp32 face areas, operation for operation (bit-exact by construction)
+    triangle_soup, sliver_between_faces      inputs shared by the CPU and the GPU tests
 """
 import numpy as np
 
@@ -94,3 +96,57 @@ def face_areas(V, F):
     V, F = f32(V), np.asarray(F, dtype=np.int64)
     n = np.cross(V[F[:, 1]] - V[F[:, 0]], V[F[:, 2]] - V[F[:, 0]])
     return 0.5 * np.linalg.norm(n, axis=1)
+
+
+def face_areas_f32(V, F, contracted=False):
+    """The fp32 areas of dsdf_surf_prepare, operation for operation (include/dsdf.h): ab = b - a, ac = c - a, n = ab x ac,
+    area = 0.5 * sqrt((nx nx + ny ny) + nz nz), every difference, product and sum rounded to fp32 on its own, the square root
+    correctly rounded (np.sqrt on float32 is), the factor 0.5 exact.
+
+    contracted=True is what a compiler makes of the same expressions when it may contract: every normal component is
+    fma(p, q, -(r * s)) with r * s rounded, and n.n is fma(nz, nz, fma(ny, ny, nx * nx)); the fused operations are formed in fp64
+    from the fp32 operands (products exact) and rounded to fp32 once.  It is NOT the specification: it exists so that a test can
+    prove that its inputs tell the two apart."""
+    V, F = np.asarray(V, dtype=np.float32), np.asarray(F, dtype=np.int64)
+    a = V[F[:, 0]]
+    ab, ac = V[F[:, 1]] - a, V[F[:, 2]] - a
+    x, y, z = 0, 1, 2
+    if not contracted:
+        n = [ab[:, i] * ac[:, j] - ab[:, j] * ac[:, i] for i, j in ((y, z), (z, x), (x, y))]
+        nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]
+    else:
+        d = np.float64
+        n = [(ab[:, i].astype(d) * ac[:, j].astype(d) - (ab[:, j] * ac[:, i]).astype(d)).astype(np.float32)
+             for i, j in ((y, z), (z, x), (x, y))]
+        s = (n[1].astype(d) * n[1].astype(d) + (n[0] * n[0]).astype(d)).astype(np.float32)
+        nn = (n[2].astype(d) * n[2].astype(d) + s.astype(d)).astype(np.float32)
+    assert nn.dtype == np.float32
+    return np.float32(0.5) * np.sqrt(nn)
+
+
+SOUP_SPLIT = 262144          # 256 scan tiles of 1024 faces: the faces from here on lie behind the tile scan's first round
+
+
+def triangle_soup(nf, seed, heavy_tail=False):
+    """(V float32 [3 nf, 3], F int64 [nf, 3]): nf seeded triangles with three fresh vertices each, centres in [-1, 1]^3, edges of
+    about 0.05; no coordinate is dyadic.  The first nf faces of a larger soup of the same seed are this soup.  heavy_tail: the
+    faces from SOUP_SPLIT on are scaled about their first vertex so that together they carry about half of the total area."""
+    big = max(nf, SOUP_SPLIT + 1025)
+    g = np.random.default_rng(seed)
+    c = g.uniform(-1, 1, (big, 1, 3))
+    V = (c + g.uniform(-0.03, 0.03, (big, 3, 3))).astype(np.float32)[:nf]
+    if heavy_tail and nf > SOUP_SPLIT:
+        area = face_areas(V.reshape(-1, 3), np.arange(3 * nf).reshape(nf, 3))
+        k = np.sqrt(area[:SOUP_SPLIT].sum() / area[SOUP_SPLIT:].sum())
+        a = V[SOUP_SPLIT:, :1].astype(np.float64)
+        V[SOUP_SPLIT:] = (a + k * (V[SOUP_SPLIT:].astype(np.float64) - a)).astype(np.float32)
+    return V.reshape(-1, 3), np.arange(3 * nf, dtype=np.int64).reshape(nf, 3)
+
+
+def sliver_between_faces():
+    """(V float32, F): the degenerate face (0, d, 2 d) with a non-dyadic d between two real faces.  ab = d and ac = 2 d exactly, so
+    both products of every normal component round to the same number and the specification's area is exactly 0; a contracted
+    cross product keeps the rounding error of one product instead."""
+    d = np.array([0.3, 0.7, 1.1], dtype=np.float32)
+    V = np.array([[0, 0, 0], d, 2 * d, [1.1, 0.2, 0.3], [0.1, 1.3, 0.2], [0.3, 0.1, 0.9], [-0.7, 0.6, -1.3]], dtype=np.float32)
+    return V, np.array([[0, 3, 4], [0, 1, 2], [3, 5, 6]], dtype=np.int64)

@@ -27,28 +27,39 @@ def _gpu_mc(grid, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0)):
     return v.cpu().numpy(), f.cpu().numpy()
 
 
-def _same_mesh(grid, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0)):
+def _same_bits(what, v, vr):
+    """The vertices are the specification's bit for bit; the count of differing coordinates and their distance are printed first."""
+    assert v.dtype == np.float32 and vr.dtype == np.float32 and v.shape == vr.shape
+    d, n = mc_numpy.differing(v, vr)
+    if d:
+        print(f"{what}: {d} of {n} coordinates differ from the single-rounded specification, by at most {mc_numpy.ulp_distance(v, vr)} ulp")
+    assert d == 0, (what, d, n)
+
+
+def _has_power(what, grid, level, spacing, origin, vr):
+    """The input tells a fused origin + x * spacing from the specification: at least a tenth of the coordinates differ."""
+    d, n = mc_numpy.differing(vr, mc_numpy.vertices(np.asarray(grid), level, spacing, origin, contracted=True))
+    print(f"{what}: a fused last step would change {d} of {n} coordinates")
+    assert d >= 0.1 * n, (what, d, n)
+
+
+def _same_mesh(grid, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0), power=False):
     v, f = _gpu_mc(grid, level, spacing, origin)
     vr, fr = mc_numpy.marching_cubes(np.asarray(grid), level, spacing, origin)
     assert f.shape == fr.shape and np.array_equal(f, fr)
-    assert v.shape == vr.shape and (v.size == 0 or np.abs(v - vr).max() <= 1e-6)
+    if power:
+        _has_power("input", grid, level, spacing, origin, vr)
+    _same_bits(f"grid {tuple(np.asarray(grid).shape)}", v, vr)
     return v, f
 
 
-def _smooth(shape, seed):
-    g = np.random.default_rng(seed)
-    axes = np.meshgrid(*[np.linspace(0, 1, n) for n in shape], indexing="ij")
-    out = np.zeros(shape)
-    for _ in range(6):
-        k, ph, a = g.uniform(1, 6, 3), g.uniform(0, 2 * np.pi, 3), g.uniform(0.2, 1.0)
-        out += a * np.sin(k[0] * axes[0] + ph[0]) * np.sin(k[1] * axes[1] + ph[1]) * np.sin(k[2] * axes[2] + ph[2])
-    return out.astype(np.float32)
+_smooth = mc_numpy.smooth_field
 
 
 def test_analytic_fields_match_numpy_and_are_closed():
     for make, chi in ((mc_numpy.sphere, 2), (mc_numpy.torus, 0)):
         sdf, h = make(64)
-        v, f = _same_mesh(sdf, 0.0, (h, h, h), (-1, -1, -1))
+        v, f = _same_mesh(sdf, 0.0, (h, h, h), (-1, -1, -1), power=True)
         ok, euler, vol = mc_numpy.closed_manifold_stats(v, f)
         assert ok and euler == chi and vol > 0
 
@@ -61,6 +72,25 @@ def test_random_and_quantised_fields_on_a_non_cubic_grid():
     assert (q == 0.125).sum() > 100
     for level in (0.125, 0.0):
         _same_mesh(q.astype(np.float32), level)
+
+
+def test_non_dyadic_spacing_and_origin_bit_for_bit_and_from_the_edges():
+    """Spacing and origin that are not dyadic on any axis: x * spacing is inexact, so a contracted origin + x * spacing would show in
+    the bits (asserted on the oracle first).  Every vertex recomputed from its edge (p, a) and the edge's two grid values with the
+    specification's formula is the returned vertex."""
+    from deepsdf_amd.mesh import marching_cubes
+    from tests import msdiff_numpy
+    nd = mc_numpy.NON_DYADIC
+    g = _smooth(nd["shape"], nd["seed"])
+    level, spacing, origin = nd["level"], nd["spacing"], nd["origin"]
+    v, f = _same_mesh(g, level, spacing, origin, power=True)
+    assert len(f) > 1000
+    verts, faces, ep, ea = marching_cubes(torch.from_numpy(g).cuda(), level, spacing, origin, return_edges=True)
+    assert np.array_equal(verts.cpu().numpy().view(np.uint32), v.view(np.uint32)) and np.array_equal(faces.cpu().numpy(), f)
+    ep, ea = ep.cpu().numpy(), ea.cpu().numpy()
+    wp, wa = msdiff_numpy.edges(g, level)
+    assert np.array_equal(ep, wp) and np.array_equal(ea, wa) and set(ea.tolist()) == {0, 1, 2}
+    _same_bits("vertices from their edges", v, msdiff_numpy.vertices_from_edges(g, ep, ea, level, spacing, origin))
 
 
 def test_all_256_cases_on_2x2x2_grids():
@@ -97,7 +127,7 @@ def test_empty_surface(tmp_path):
 
 def test_large_sphere_n256():
     sdf, h = mc_numpy.sphere(256)
-    v, f = _same_mesh(sdf, 0.0, (h, h, h), (-1, -1, -1))
+    v, f = _same_mesh(sdf, 0.0, (h, h, h), (-1, -1, -1), power=True)
     ok, euler, vol = mc_numpy.closed_manifold_stats(v, f)
     assert ok and euler == 2 and abs(vol - 4 / 3 * math.pi * 0.125) <= 2e-3 * vol
 
@@ -150,7 +180,9 @@ def test_create_mesh_on_real_and_seeded_weights(tmp_path):
         create_mesh(dec, z.cuda(), path, N=N, max_batch=mb)
         _, v, f = mc_numpy.read_ply(path)
         vr, fr = mc_numpy.marching_cubes(grid.cpu().numpy(), 0.0, (h, h, h), (-1, -1, -1))
-        assert len(f) > 100 and np.array_equal(f, fr) and np.abs(v - vr).max() <= 1e-6, name
+        assert len(f) > 100 and np.array_equal(f, fr), name
+        _has_power(name, grid.cpu().numpy(), 0.0, (h, h, h), (-1, -1, -1), vr)
+        _same_bits(name, v, vr)                          # no host arithmetic between the kernel and the file
 
 
 def test_create_mesh_offset_scale_and_stock_module(tmp_path):
@@ -170,7 +202,9 @@ def test_create_mesh_offset_scale_and_stock_module(tmp_path):
     assert np.abs(grid - (grid_coords(N, 0, N ** 3).norm(dim=1) - 0.5).reshape(N, N, N).numpy()).max() <= 1e-6
     vr, fr = mc_numpy.marching_cubes(grid, 0.0, (h, h, h), (-1, -1, -1))
     assert np.array_equal(f, fr)
-    assert np.abs(v - ((vr / np.float32(2.0)) - np.array([0.5, 0, -1.0], np.float32))).max() <= 1e-6
+    _has_power("sphere", grid, 0.0, (h, h, h), (-1, -1, -1), vr)
+    # the host step as convert_sdf_samples_to_ply does it: an fp32 division by the scale, then an fp32 subtraction of the offset
+    _same_bits("offset and scale", v, (vr / np.float32(2.0)) - np.array([0.5, 0, -1.0], np.float32))
 
 
 def test_variant_net_takes_the_engine_decode_path():

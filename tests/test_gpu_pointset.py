@@ -1,6 +1,7 @@
 """-m gpu: the point-set kernels (dsdf_nn_*, dsdf_mean_f64, dsdf_surf_*; deepsdf_amd/metrics.py, TriangleMesh.sample_surface)
 against the numpy oracle of tests/pointset_numpy.py; split and call determinism; the Chamfer distance end to end; the
 sampling and evaluation command lines."""
+import ctypes as C
 import json
 import math
 import os
@@ -11,12 +12,18 @@ import numpy as np
 import pytest
 import torch
 
+from tests import mc_numpy
 from tests import meshsdf_numpy as mn
 from tests import pointset_numpy as pn
+from tests import ws_guard
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+K = ws_guard.constants()                         # the planners' break points, read from the kernel sources
+NN_TILE = K["NN_BLOCK"] * K["NN_QPL"]            # queries per workgroup
+SURF_TILE = K["SURF_BLOCK"] * K["SURF_PER_LANE"]  # faces per workgroup of the scan
+SOUP_SEED = 13                                   # tests/test_pointset_cpu.py checks this seed's margins and shares on the CPU
 
 
 def _mc_sphere(n, radius):
@@ -136,6 +143,124 @@ def test_nearest_neighbour_determinism_outputs_and_errors():
         nearest_neighbor(qn, np.zeros((5, 4)))
 
 
+
+def _check_nn(Q, R, d2, idx, what):
+    """Every query against the fp64 brute force, under the tolerances of test_nearest_neighbour_matches_the_oracle."""
+    ref, _ = pn.nn_bruteforce(Q, R, block=64)
+    err = np.abs(d2 - ref) / ref
+    back = pn.pair_d2(Q, R, idx) / ref
+    print(f"{what}: max rel err {err.max():.2e}, returned pair / min {back.max():.9f}")
+    assert idx.min() >= 0 and idx.max() < len(R)
+    assert np.all(np.abs(d2 - ref) <= 1e-6 * ref), (what, err.max())
+    assert np.all(pn.pair_d2(Q, R, idx) <= ref * (1 + 1e-6)), (what, back.max())
+
+
+@pytest.mark.parametrize("nq", [1023, 1024, 1025, 2049])
+def test_nearest_neighbour_query_tile_tails(nq):
+    """One query short of a tile, a full tile, one into the second, one into the third: every query against the oracle, with one
+    split (the query kernel writes the outputs) and with three (partials and the combine pass)."""
+    from deepsdf_amd.metrics import nearest_neighbor, plan
+    assert NN_TILE == 1024
+    g = np.random.default_rng(300 + nq)
+    Q = g.uniform(-1, 1, (nq, 3))
+    for want, nr in ((1, 900), (3, 3 * K["NN_MIN_SPLIT_REFS"] + 77)):
+        assert plan(nq, nr)[1] == want
+        R = g.uniform(-1, 1, (nr, 3))
+        d2, idx = nearest_neighbor(Q, R)
+        assert d2.shape == (nq,) and idx.shape == (nq,)
+        _check_nn(Q, R, d2, idx, f"nq {nq} nr {nr} splits {want}")
+
+
+@pytest.mark.parametrize("nq,nr,want", [(300, 65535, 63), (300, 65536, 64), (300, 65536 + 77, 64), (300, 131072 + 5, 64),
+                                        (1025, 65536 + 77, 64)])
+def test_nearest_neighbour_at_the_split_cap_is_exact_on_dyadic_points(nq, nr, want):
+    """Up to and beyond NN_MAX_SPLITS splits, on coordinates k / 64 (every d2 exact in fp32): values and indices are the oracle's
+    bit for bit.  The LAST split repeats points of split 0 and queries sit AT them, so the lowest index has to win through every
+    partial of the combine pass."""
+    from deepsdf_amd.metrics import nearest_neighbor, plan
+    assert K["NN_MAX_SPLITS"] == 64 and plan(nq, nr)[1] == want
+    g = np.random.default_rng(nr + nq)
+    R = g.integers(-128, 129, (nr, 3)) / 64.0
+    Q = g.integers(-128, 129, (nq, 3)) / 64.0
+    chunk = -(-nr // want)
+    last = (want - 1) * chunk
+    assert last + 5 < nr - 1
+    R[last + 5] = R[3]                       # the last split repeats a point of split 0 ...
+    R[nr - 1] = R[chunk - 1]                 # ... and, as its last point, the last point of split 0
+    Q[0], Q[1] = R[3], R[chunk - 1]
+    Q[2:200] = R[g.integers(0, nr, 198)] + g.integers(-1, 2, (198, 3)) / 64.0       # many near ties
+    d2, idx = nearest_neighbor(Q, R)
+    ref, ridx = pn.nn_bruteforce(Q, R, block=32)
+    print(f"nq {nq} nr {nr} splits {want}: {int((idx != ridx).sum())} indices and {int((d2.astype(np.float64) != ref).sum())} values differ")
+    assert np.array_equal(d2.astype(np.float64), ref)
+    assert np.array_equal(idx, ridx)
+    assert idx[0] <= 3 and idx[1] <= chunk - 1 and d2[0] == 0 and d2[1] == 0
+
+
+def test_nearest_neighbour_split_count_bound_by_the_query_tiles():
+    """513 query tiles leave room for ceil(2048 / 513) = 4 splits although the reference set would allow 8: the tile-bound branch
+    of the planner.  A sample of the queries against the oracle; all of them against a second call and against a one-split call."""
+    from deepsdf_amd.metrics import nearest_neighbor, plan
+    nq, nr = 512 * NN_TILE + 3, 8 * K["NN_MIN_SPLIT_REFS"] + 1
+    tiles = -(-nq // NN_TILE)
+    assert (nq, nr, tiles) == (524291, 8193, 513)
+    assert plan(nq, nr)[1] == -(-K["NN_TARGET_WG"] // tiles) == 4 < nr // K["NN_MIN_SPLIT_REFS"]
+    big = (K["NN_TARGET_WG"] - 1) * NN_TILE + 1
+    assert plan(big, nr)[1] == 1
+    gen = torch.Generator().manual_seed(17)
+    Q = (torch.rand(big, 3, generator=gen) * 2 - 1).cuda()
+    R = (torch.rand(nr, 3, generator=gen) * 2 - 1).cuda()
+    a = nearest_neighbor(Q[:nq], R)
+    a2 = nearest_neighbor(Q[:nq], R)
+    one = nearest_neighbor(Q, R)
+    assert torch.equal(a[0], a2[0]) and torch.equal(a[1], a2[1])
+    assert torch.equal(a[0], one[0][:nq]) and torch.equal(a[1], one[1][:nq])
+    others = np.random.default_rng(17).choice(np.arange(NN_TILE, nq - 1027), 1000, replace=False)
+    sel = np.concatenate([np.arange(NN_TILE), np.sort(others), np.arange(nq - 1027, nq)])
+    st = torch.from_numpy(sel).cuda()
+    _check_nn(Q[st].cpu().numpy(), R.cpu().numpy(), a[0][st].cpu().numpy(), a[1][st].cpu().numpy(), f"{len(sel)} of {nq} queries")
+
+
+def test_nearest_neighbour_without_a_comparable_pair():
+    """include/dsdf.h: a query with no comparable reference point (every d2 NaN or +inf) reports (+inf, 0) -- index 0, not the
+    first index of some split.  Three splits, both outputs."""
+    from deepsdf_amd.metrics import nearest_neighbor, plan
+    nq, nr = 300, 3 * K["NN_MIN_SPLIT_REFS"] + 5
+    assert plan(nq, nr)[1] == 3
+    chunk = -(-nr // 3)
+    g = np.random.default_rng(23)
+    Q, R = g.uniform(-1, 1, (nq, 3)), g.uniform(-1, 1, (nr, 3))
+    inf = np.float32(np.inf)
+
+    def nothing(d2, idx, rows):
+        assert d2.dtype == np.float32 and np.array_equal(d2[rows], np.full(len(d2[rows]), inf)), d2[rows][:8]
+        assert np.array_equal(idx[rows], np.zeros(len(idx[rows]), np.int32)), idx[rows][:8]
+
+    Qn = Q.copy()
+    Qn[7, 1] = np.nan                                    # a NaN query: one coordinate, and all three
+    Qn[299] = np.nan
+    d2, idx = nearest_neighbor(Qn, R)
+    nothing(d2, idx, [7, 299])
+    keep = np.setdiff1d(np.arange(nq), [7, 299])
+    _check_nn(Qn[keep], R, d2[keep], idx[keep], "the other queries")
+    d2, idx = nearest_neighbor(Q, np.full((nr, 3), np.nan))      # every reference point NaN
+    nothing(d2, idx, np.arange(nq))
+    Ri = np.full((nr, 3), np.nan)                        # the only points that are not NaN sit at +inf, none of them in split 0
+    Ri[chunk + 3] = [np.inf, 0.25, -0.5]
+    Ri[2 * chunk + 1] = np.inf
+    Ri[nr - 1] = [0.0, np.inf, np.inf]
+    d2, idx = nearest_neighbor(Q, Ri)
+    nothing(d2, idx, np.arange(nq))
+    for dead in range(3):                                # one split all NaN: the answer comes from the two others
+        Rd = R.copy()
+        Rd[dead * chunk:min(nr, (dead + 1) * chunk)] = np.nan
+        alive = np.nonzero(~np.isnan(Rd[:, 0]))[0]
+        d2, idx = nearest_neighbor(Q, Rd)
+        ref, ridx = pn.nn_bruteforce(Q, Rd[alive])
+        assert np.array_equal(idx, alive[ridx]), dead
+        assert np.all(np.abs(d2 - ref) <= 1e-6 * ref), dead
+
+
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 65537])
 def test_mean_f64(n):
     from deepsdf_amd.metrics import mean_f64
@@ -150,7 +275,55 @@ def test_mean_f64(n):
         mean_f64(x[:0])
 
 
+def _mean_plan(n):
+    """(workgroups, values per workgroup) of dsdf_mean_f64, as include/dsdf.h states them."""
+    blocks = min(-(-n // K["MEAN_MIN_SLICE"]), K["MEAN_MAX_BLOCKS"])
+    return blocks, -(-n // blocks)
+
+
+# n, workgroups, slice: one workgroup up to 4096 values; two from 4097; 257 partials send the final pass's loop round a second
+# time; all 1024 workgroups at the smallest slice; a slice above it, with a short last one
+@pytest.mark.parametrize("n,blocks,slice_", [(4095, 1, 4095), (4096, 1, 4096), (4097, 2, 2049), (256 * 4096 + 1, 257, 4081),
+                                             (1024 * 4096, 1024, 4096), (1024 * 4096 + 1025, 1024, 4098)])
+def test_mean_f64_at_the_planner_break_points(n, blocks, slice_):
+    from deepsdf_amd.metrics import mean_f64
+    assert (K["MEAN_MIN_SLICE"], K["MEAN_MAX_BLOCKS"], K["MEAN_BLOCK"]) == (4096, 1024, 256) and _mean_plan(n) == (blocks, slice_)
+    assert (blocks - 1) * slice_ < n <= blocks * slice_            # every workgroup has values; the last may be short
+    x = torch.rand(n, generator=torch.Generator().manual_seed(n)) * 3 + 0.01
+    ref = math.fsum(x.tolist()) / n
+    xd = x.cuda()
+    m1, m2 = mean_f64(xd).item(), mean_f64(xd).item()
+    print(f"n {n} ({blocks} x {slice_}): mean {m1!r} exact {ref!r} rel diff {abs(m1 - ref) / ref:.2e}")
+    assert abs(m1 - ref) <= n * 2.0 ** -53 * ref
+    assert m1 == m2
+
+
+def test_mean_f64_never_accumulates_in_fp32():
+    """2^22 + 1025 values, all 1 + 2^-23: every partial sum k (1 + 2^-23), k < 2^23, is exact in fp64 (47 bits), so the mean is
+    1 + 2^-23 exactly; an fp32 accumulation anywhere loses the low bit."""
+    from deepsdf_amd.metrics import mean_f64
+    n = 2 ** 22 + 1025
+    assert _mean_plan(n) == (1024, 4098)
+    one = 1.0 + 2.0 ** -23
+    x = torch.full((n,), one, dtype=torch.float32).cuda()
+    assert x[0].item() == one
+    assert mean_f64(x).item() == one
+
+
 # ---- surface sampler --------------------------------------------------------------------------------------------------------
+def _areas_are_the_specification(name, V, F, area32, power=True):
+    """The prepare pass's fp32 areas equal pn.face_areas_f32 bit for bit; the count of differing areas and their distance are
+    printed first.  power: a contracted cross product would give at least a tenth of the faces another area."""
+    want = pn.face_areas_f32(V, F)
+    if power:
+        d = int((want.view(np.uint32) != pn.face_areas_f32(V, F, contracted=True).view(np.uint32)).sum())
+        print(f"{name}: a contracted cross product would change {d} of {len(F)} areas")
+        assert d >= 0.1 * len(F), (name, d)
+    d, n = mc_numpy.differing(area32, want)
+    print(f"{name}: {d} of {n} areas differ from the single-rounded specification, by at most {mc_numpy.ulp_distance(area32, want)} ulp")
+    assert d == 0, (name, d, n)
+
+
 def _six_face_mesh():
     """Four triangles of different areas with two zero-area faces between them (a repeated vertex; three collinear vertices)."""
     V = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0.5], [2, 0, 0], [0, 0, 2], [0.25, 3, 1], [-1, -1, 0.75]], dtype=np.float64)
@@ -167,12 +340,14 @@ def test_sampler_matches_the_oracle(name, seed):
     area32, cdf = (t.cpu().numpy() for t in m.face_areas())
     exact = pn.face_areas(V, F)
     assert np.abs(area32 - exact).max() <= 1e-5 * exact.max()
+    _areas_are_the_specification(name, V, F, area32, power=name == "mc_sphere")      # six_faces is dyadic: its products are exact
     # the scan: deterministic and within n_faces * 2^-53 * total of the exact prefix sums
     want, ext = pn.exact_cdf(area32)
     total = want[-1]
     scan_err = np.abs(cdf.astype(np.longdouble) - ext).max()
     print(f"{name}: {len(F)} faces, total {total!r}, scan error / total {float(scan_err) / total:.2e}")
     assert scan_err <= len(F) * 2.0 ** -53 * total
+    assert np.all(np.diff(cdf) >= 0)
     assert abs(m.area() - total) <= len(F) * 2.0 ** -53 * total
     assert np.array_equal(TriangleMesh(V, F).face_areas()[1].cpu().numpy(), cdf)
     pts, face, bary = (t.cpu().numpy() for t in m.sample_surface(n, seed=seed, return_bary=True))
@@ -192,6 +367,64 @@ def test_sampler_matches_the_oracle(name, seed):
     assert np.array_equal(pts2.cpu().numpy(), pts) and np.array_equal(face2.cpu().numpy(), face)
     other = m.sample_surface(n, seed=seed + 1)[0].cpu().numpy()
     assert not np.array_equal(other, pts)
+
+
+def test_face_without_area_between_two_real_faces_is_never_drawn():
+    """The face (0, d, 2 d) with a non-dyadic d: its two products per normal component round alike, so the specification's area is
+    exactly 0 and the face is never chosen; a contracted cross product leaves it a rounding error of area and a place in the CDF."""
+    from deepsdf_amd.meshsdf import TriangleMesh
+    V, F = pn.sliver_between_faces()
+    assert pn.face_areas_f32(V, F)[1] == 0.0 and pn.face_areas_f32(V, F, contracted=True)[1] > 0.0
+    m = TriangleMesh(V, F)
+    area32, cdf = (t.cpu().numpy() for t in m.face_areas())
+    print(f"area of the face without area: {area32[1]!r}")
+    _areas_are_the_specification("sliver", V, F, area32)
+    assert area32[1] == 0.0 and cdf[1] == cdf[0] and np.all(np.diff(cdf) >= 0)
+    face = m.sample_surface(65536, seed=3)[1].cpu().numpy()
+    assert set(np.unique(face)) == {0, 2}
+
+
+def _surf_tiles(nf):
+    from deepsdf_amd import _lib
+    nt = C.c_int32()
+    _lib.check(_lib.lib().dsdf_surf_plan(nf, None, None, C.byref(nt)))
+    return nt.value
+
+
+@pytest.mark.parametrize("nf", [1023, 1024, 1025, pn.SOUP_SPLIT, pn.SOUP_SPLIT + 1, pn.SOUP_SPLIT + 1025])
+def test_scan_and_sampler_at_the_tile_break_points(nf):
+    """A seeded triangle soup cut around one scan tile (1024 faces) and around 256 of them, where the scan of the tile sums goes
+    round its carry loop a second time; there the faces behind the first 256 tiles carry half of the area, so that carry decides
+    half of the samples."""
+    from deepsdf_amd.meshsdf import TriangleMesh
+    assert SURF_TILE == 1024 and pn.SOUP_SPLIT == K["SURF_BLOCK"] * SURF_TILE
+    tiles = _surf_tiles(nf)
+    assert tiles == -(-nf // SURF_TILE) and (tiles > K["SURF_BLOCK"]) == (nf > pn.SOUP_SPLIT)
+    V, F = pn.triangle_soup(nf, SOUP_SEED, heavy_tail=True)
+    m = TriangleMesh(V, F)
+    area32, cdf = (t.cpu().numpy() for t in m.face_areas())
+    _areas_are_the_specification(f"soup {nf}", V, F, area32)
+    want, ext = pn.exact_cdf(area32)
+    total = want[-1]
+    scan_err = np.abs(cdf.astype(np.longdouble) - ext).max()
+    print(f"soup {nf}: {tiles} tiles, total {total!r}, scan error / total {float(scan_err) / total:.2e}")
+    assert scan_err <= nf * 2.0 ** -53 * total
+    assert np.all(np.diff(cdf) >= 0)
+    assert m.area() == cdf[-1]
+    n = 4096
+    pts, face, bary = (t.cpu().numpy() for t in m.sample_surface(n, seed=SOUP_SEED, return_bary=True))
+    o = pn.surface_samples(V, F, area32, n, SOUP_SEED)
+    assert o["margin"].min() > 1e-12, o["margin"].min()        # the oracle alone: no sample sits in the undecided band
+    behind = float((o["face"] >= pn.SOUP_SPLIT).mean())
+    print(f"soup {nf}: share of the samples behind the first 256 tiles {behind:.3f}, smallest margin {o['margin'].min():.2e}")
+    if nf > pn.SOUP_SPLIT:
+        assert behind >= 0.25
+    assert np.array_equal(face, o["face"])
+    assert np.array_equal(bary[:, 0], o["u"]) and np.array_equal(bary[:, 1], o["v"])
+    extent = np.abs(V).max()
+    perr = np.abs(pts - o["point"]).max()
+    print(f"soup {nf}: max point error {perr:.2e} (extent {extent})")
+    assert perr <= 1e-6 * extent
 
 
 def test_sampler_statistics():

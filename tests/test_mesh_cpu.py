@@ -134,6 +134,66 @@ def test_numpy_torus_has_euler_characteristic_zero():
     assert ok and euler == 0 and vol > 0
 
 
+# ---- the fp32 vertex arithmetic: the bound against fp64, and inputs that tell a fused last step from the specification ------
+# Error of the specification's fp32 vertex against the same formula in fp64 on the same fp32 inputs, u = 2^-24 (round to nearest):
+#   t = (level - v0) / (v1 - v0): two subtractions and a division, (1 + u)^3 - 1 <= 3.01 u relative, and 0 <= t <= 1
+#   x = p + t (p an exact integer):   3.01 u t + u |x|
+#   y = x * spacing:                  (3.01 u t + u |x|) |s| + u |x s| <= u |s| (3.01 + 2 |x|)
+#   v = origin + y:                   that + u |v|
+# VERTEX_TOL multiplies |s| (3.01 + 2 |x|) + |v|, with 2 % on top for the second-order terms and the fp64 side's own rounding.
+VERTEX_TOL = 1.02 * 2.0 ** -24
+
+
+def _mc_cases():
+    """(name, field, level, spacing, origin) of every marching-cubes input whose vertices the GPU tests compare bit for bit with a
+    spacing and an origin that make x * spacing inexact."""
+    nd = mc_numpy.NON_DYADIC
+    yield "non_dyadic", mc_numpy.smooth_field(nd["shape"], nd["seed"]), nd["level"], nd["spacing"], nd["origin"]
+    for make, n in ((mc_numpy.sphere, 24), (mc_numpy.sphere, 64), (mc_numpy.torus, 64)):
+        sdf, h = make(n)
+        yield f"{make.__name__}{n}", sdf, 0.0, (h, h, h), (-1, -1, -1)
+
+
+def test_fp32_vertices_lie_within_the_rounding_bound_of_fp64():
+    from tests import msdiff_numpy
+    for name, sdf, level, spacing, origin in _mc_cases():
+        v, _ = mc_numpy.marching_cubes(sdf, level, spacing, origin)
+        p, a = msdiff_numpy.edges(sdf, level)
+        assert np.array_equal(msdiff_numpy.vertices_from_edges(sdf, p, a, level, spacing, origin).view(np.uint32), v.view(np.uint32))
+        f = sdf.reshape(-1).astype(np.float64)
+        stride = np.array([sdf.shape[1] * sdf.shape[2], sdf.shape[2], 1], dtype=np.int64)
+        v0, v1 = f[p], f[p + stride[a]]
+        x = np.stack(np.unravel_index(p, sdf.shape), 1).astype(np.float64)
+        x[np.arange(len(p)), a] += (np.float64(np.float32(level)) - v0) / (v1 - v0)
+        s, o = np.asarray(spacing, np.float32).astype(np.float64), np.asarray(origin, np.float32).astype(np.float64)
+        want = o + x * s
+        bound = VERTEX_TOL * (np.abs(s) * (3.01 + 2 * np.abs(x)) + np.abs(want))
+        err = np.abs(v.astype(np.float64) - want)
+        print(f"{name}: {len(v)} vertices, max error / bound {(err / bound).max():.3f}")
+        assert (err <= bound).all(), name
+        assert err.max() > 0, name
+
+
+def test_a_fused_last_step_shows_on_the_inputs_the_gpu_tests_use():
+    """The contracted variant is not the specification: it differs from it in at least a tenth of the coordinates on every input
+    above, and in none with origin 0 or a dyadic spacing (where bit-equal vertices would prove nothing about contraction)."""
+    for name, sdf, level, spacing, origin in _mc_cases():
+        spec, f = mc_numpy.marching_cubes(sdf, level, spacing, origin)
+        fused, f2 = mc_numpy.marching_cubes(sdf, level, spacing, origin, contracted=True)
+        assert np.array_equal(f, f2)
+        d, n = mc_numpy.differing(spec, fused)
+        print(f"{name}: {d} of {n} coordinates differ")
+        assert d >= 0.1 * n, (name, d, n)
+        # ... by no more than the product's rounding error and one rounding of the sum: u |x s| + u |v|, |x s| <= |v| + |origin|
+        assert np.abs(spec.astype(np.float64) - fused).max() <= 2.0 ** -23 * (np.abs(spec).max() + np.abs(origin).max())
+    nd = mc_numpy.NON_DYADIC
+    sdf = mc_numpy.smooth_field(nd["shape"], nd["seed"])
+    for spacing, origin in ((nd["spacing"], (0, 0, 0)), ((0.5, 0.25, 2.0), nd["origin"])):
+        d, _ = mc_numpy.differing(mc_numpy.marching_cubes(sdf, nd["level"], spacing, origin)[0],
+                                  mc_numpy.marching_cubes(sdf, nd["level"], spacing, origin, contracted=True)[0])
+        assert d == 0, (spacing, origin, d)
+
+
 # ---- PLY ----------------------------------------------------------------------------------------------------------------
 HEADER = (b"ply\nformat binary_little_endian 1.0\nelement vertex 4\nproperty float x\nproperty float y\nproperty float z\n"
           b"element face 2\nproperty list uchar int vertex_indices\nend_header\n")

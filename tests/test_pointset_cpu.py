@@ -66,6 +66,88 @@ def test_oracle_sampler_rule():
     assert np.array_equal(two["face"], s["face"][19900:]) and np.array_equal(two["u"], s["u"][19900:])
 
 
+# Error of the fp32 area (pn.face_areas_f32) against the fp64 area of the same fp32 vertices (pn.face_areas), u = 2^-24, M = |ab| |ac|:
+#   ab, ac: fp32 differences, each component within u relative: n = ab x ac moves by at most 2 u M (norm)
+#   a normal component p - q: products and the difference rounded, error <= u (|p| + |q|) + u |p - q| <= 2 u |ab'| |ac'| with ab', ac'
+#       the two-dimensional projections (Cauchy-Schwarz); over the three components the norm of the errors is <= 2 sqrt(3) u M
+#   n.n: squares, two sums: (1 + u)^3 relative; the correctly rounded root of it: 1.5 u + u = 2.5 u relative to |n| <= M
+#   |n| within (2 + 3.47 + 2.5) u M = 7.97 u M, the area within half of that.
+# AREA_TOL multiplies M, with 2 % on top for the second-order terms and the fp64 side's own rounding.
+AREA_TOL = 1.02 * 0.5 * 7.97 * 2.0 ** -24
+SOUP_SEED = 13
+SOUP_CUTS = (1023, 1024, 1025, pn.SOUP_SPLIT, pn.SOUP_SPLIT + 1, pn.SOUP_SPLIT + 1025)
+
+
+def _area_cases():
+    """(name, V, F, is rounding visible) of the meshes whose areas the GPU tests compare bit for bit."""
+    from tests import mc_numpy
+    sdf, h = mc_numpy.sphere(24, 0.6)
+    v, f = mc_numpy.marching_cubes(sdf, 0.0, (h, h, h), (-1, -1, -1))
+    yield "mc_sphere", v, f.astype(np.int64), True
+    V = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0.5], [2, 0, 0], [0, 0, 2], [0.25, 3, 1], [-1, -1, 0.75]], dtype=np.float32)
+    yield "six_faces", V, np.array([[0, 1, 2], [3, 3, 5], [1, 3, 2], [1, 4, 3], [0, 1, 4], [5, 6, 7]]), False      # dyadic: exact products
+    V, F = pn.sliver_between_faces()
+    yield "sliver", V, F, True
+    for nf in SOUP_CUTS:
+        V, F = pn.triangle_soup(nf, SOUP_SEED, heavy_tail=True)
+        yield f"soup{nf}", V, F, True
+
+
+def test_fp32_areas_lie_within_the_rounding_bound_of_fp64():
+    for name, V, F, _ in _area_cases():
+        a32, a64 = pn.face_areas_f32(V, F), pn.face_areas(V, F)
+        assert a32.dtype == np.float32 and a32.shape == (len(F),)
+        Vd = pn.f32(V)
+        M = np.linalg.norm(Vd[F[:, 1]] - Vd[F[:, 0]], axis=1) * np.linalg.norm(Vd[F[:, 2]] - Vd[F[:, 0]], axis=1)
+        err = np.abs(a32.astype(np.float64) - a64)
+        print(f"{name}: {len(F)} faces, max error / bound {(err[M > 0] / (AREA_TOL * M[M > 0])).max():.3f}")
+        assert (err <= AREA_TOL * M).all(), name
+
+
+def test_a_contracted_cross_product_shows_on_the_inputs_the_gpu_tests_use():
+    """The contracted variant is not the specification.  On every mesh whose coordinates are not dyadic it gives at least a tenth
+    of the faces another area (the soups hold 3 fresh vertices per face, so no two faces share a rounding), always within the
+    bound above; on the dyadic six-face mesh, whose products are exact, it gives the same bits -- that mesh checks the zero-area
+    rule, not the rounding."""
+    for name, V, F, visible in _area_cases():
+        spec, fused = pn.face_areas_f32(V, F), pn.face_areas_f32(V, F, contracted=True)
+        d = int((spec.view(np.uint32) != fused.view(np.uint32)).sum())
+        print(f"{name}: {d} of {len(F)} areas differ")
+        if visible:
+            assert d >= 0.1 * len(F), (name, d)
+        else:
+            assert d == 0, (name, d)
+
+
+def test_the_doubled_edge_face_has_exactly_no_area_in_the_specification_only():
+    V, F = pn.sliver_between_faces()
+    spec, fused = pn.face_areas_f32(V, F), pn.face_areas_f32(V, F, contracted=True)
+    assert spec[1] == 0.0 and spec[0] > 0 and spec[2] > 0
+    assert fused[1] > 0.0                                            # the rounding error of one product survives the fused form
+    assert not any(float(c) == int(c * 2 ** 20) / 2 ** 20 for c in V[1])       # d is not dyadic (to 20 bits): the products round
+    s = pn.surface_samples(V, F, spec, 65536, seed=3)
+    assert set(np.unique(s["face"])) == {0, 2}
+
+
+def test_soup_is_nested_and_its_tail_carries_half_the_area():
+    """The soup's contract: a cut is a prefix of the full soup; with heavy_tail the faces behind the first 256 scan tiles carry
+    about half of the area, and the oracle's samples of every cut stay clear of the undecided band."""
+    full_V, full_F = pn.triangle_soup(SOUP_CUTS[-1], SOUP_SEED, heavy_tail=True)
+    plain_V, _ = pn.triangle_soup(SOUP_CUTS[-1], SOUP_SEED)
+    assert np.array_equal(full_V[:3 * pn.SOUP_SPLIT], plain_V[:3 * pn.SOUP_SPLIT])
+    edges = np.linalg.norm(plain_V[1::3].astype(np.float64) - plain_V[0::3], axis=1)
+    assert 0.03 < edges.mean() < 0.07
+    for nf in SOUP_CUTS:
+        V, F = pn.triangle_soup(nf, SOUP_SEED, heavy_tail=True)
+        assert F.shape == (nf, 3) and np.array_equal(V[:3 * min(nf, pn.SOUP_SPLIT)], full_V[:3 * min(nf, pn.SOUP_SPLIT)])
+        area = pn.face_areas_f32(V, F)
+        o = pn.surface_samples(V, F, area, 4096, SOUP_SEED)
+        assert o["margin"].min() > 1e-12, (nf, o["margin"].min())
+        if nf > pn.SOUP_SPLIT:
+            share = area[pn.SOUP_SPLIT:].astype(np.float64).sum() / area.astype(np.float64).sum()
+            assert 0.45 < share < 0.55 and (o["face"] >= pn.SOUP_SPLIT).mean() >= 0.25, (nf, share)
+
+
 def test_plans_at_their_break_points(lib):
     """dsdf_nn_plan: n_splits = min(ceil(2048 / ceil(nq / 1024)), floor(nr / 1024), 64), at least 1; the workspace holds 8 bytes
     per (split, query) when there is more than one split.  dsdf_surf_plan: tiles of 1024 faces."""
