@@ -1,0 +1,115 @@
+"""``analysis/geometry.py`` of the reference, its surface half, on the GPU.
+
+``DeepSDFMesh`` takes the reference's option dictionary and gives the optimiser what it needs from the surface alone: a clean,
+closed surface (deepsdf_amd.surface.SurfaceMesh), its vertex normals, the normal-projected shape derivative (``get_dTheta_surface``)
+and the enclosed volume with its derivative with respect to the control points.  The tetrahedral half (tetgenpy, gustaf, MFEM) is
+not part of this package: ``tetrahedralize_surface`` and ``export_volume_mesh`` raise NotImplementedError."""
+import logging
+import os
+import pathlib
+
+import numpy as np
+import torch
+
+from deepsdf_amd import workspace as ws
+from deepsdf_amd.mesh import microstructure_mesh_diff, sdf_struct  # noqa: F401  (sdf_struct: re-exported)
+from deepsdf_amd.spline import BSplineField
+from deepsdf_amd.surface import SurfaceMesh
+
+STRETCH = (2.0, 1.0, 1.0)      # the reference's "freeform deformation": x is doubled
+CLIP = 1.0                     # its outlier rule: Jacobian entries outside [-1, 1] are zeroed
+
+
+class DeepSDFMesh:
+    """Generates a microstructure surface, and its derivatives, from a DeepSDF experiment."""
+
+    def __init__(self, mesh_options, experiment_location=None):
+        if "experiment_directory" not in mesh_options:
+            raise KeyError("Key experiment_directory not found in general settings")
+        if "checkpoint" not in mesh_options:
+            raise KeyError("Key checkpoint not found in general settings")
+        if not os.path.exists(mesh_options["experiment_directory"]):
+            raise FileNotFoundError(f"Experiment directory {mesh_options['experiment_directory']} not found")
+        self.options = mesh_options
+        location = pathlib.Path("." if experiment_location is None else experiment_location)
+        self.exp_dir = location / self.options["experiment_directory"]
+        checkpoint = self.options["checkpoint"]
+        latent = ws.load_latent_vectors(str(self.exp_dir), checkpoint)
+        if isinstance(latent, list):
+            latent = torch.stack([c.reshape(-1) for c in latent])
+        self.latent = latent.to("cpu").numpy()
+        self.decoder = ws.load_trained_model(str(self.exp_dir), checkpoint)
+        self.decoder.eval()
+        degrees = [int(p) for p in self.options["degrees"]]
+        knots = [[-1.0] * (p + 1) + [1.0] * (p + 1) for p in degrees]
+        n_initial = int(np.prod([p + 1 for p in degrees]))
+        field = BSplineField(degrees, knots, np.zeros((n_initial, self.latent.shape[1])))      # zero codes at every control point
+        field.uniform_refine(self.options["refinement"])
+        self.latent_vec_interpolation = field
+        self.surface_mesh = self.jacobian = self.diff = None
+        self.logger = logging.getLogger(__name__)
+        self.logger.debug(f"Initialied latent vector with {field.control_mesh_resolutions} control points")
+
+    def get_latent_shape(self) -> int:
+        return self.latent.shape[1]
+
+    def get_n_control_points(self) -> int:
+        return self.latent_vec_interpolation.control_points.shape[0]
+
+    def generate_surface_mesh(self, control_points):
+        """Mesh and d vertices / d control points for these control points; x stretched by 2; then the reference's clean-up:
+        the largest face-adjacency component when ``remove_orphans``, the watertightness test, and degenerate faces dropped when it
+        fails.  Sets ``surface_mesh`` (a SurfaceMesh whose vertex ids are those of the derivative) and ``jacobian`` (the
+        MicrostructureMeshDiff: its vjp / jvp / jacobian(), unstretched and unclipped; get_dTheta_surface applies both)."""
+        tiling = self.options["tiling"]
+        N = [self.options["N_base_reconstruction"] * t + 1 for t in tiling]
+        self.latent_vec_interpolation.control_points = control_points
+        self.diff = microstructure_mesh_diff(tiling, self.decoder, self.latent_vec_interpolation, N,
+                                             cap_border_dict=self.options["cap_border_dict"])
+        mesh = SurfaceMesh.from_diff(self.diff, STRETCH)
+        if self.options["remove_orphans"]:
+            self.logger.debug("Removing orphan meshs")
+            mesh = mesh.keep_largest_component()
+        if not mesh.is_watertight:
+            self.logger.debug("Mesh is not watertight - trying to fix by eliminating degenerate faces")
+            mesh = mesh.drop_degenerate_faces()
+            if not mesh.is_watertight:
+                self.logger.warning("Mesh is still not watertight after eliminating degenerate faces")
+            else:
+                self.logger.debug("Successfully fixed mesh.")
+        self.surface_mesh = mesh
+        self.jacobian = self.diff
+
+    def _mesh(self):
+        if self.surface_mesh is None:
+            raise RuntimeError("call generate_surface_mesh(control_points) first")
+        return self.surface_mesh
+
+    def get_dTheta_surface(self):
+        """The reference's get_dTheta restricted to the surface vertices: [V, 3, ncp * L] fp32 on the device."""
+        normals = self._mesh().vertex_normals()
+        n_zero = int((normals == 0).all(1).sum())
+        if n_zero > 0:
+            self.logger.debug(f"{n_zero} 0-Normal vectors detected")
+        return self._mesh().dtheta(clip=CLIP)
+
+    def volume(self):
+        return self._mesh().volume()
+
+    def volume_gradient(self):
+        """d volume / d control points [ncp, L] on the device."""
+        return self._mesh().volume_gradient()
+
+    def tetrahedralize_surface(self):
+        raise NotImplementedError("tetrahedralize_surface needs tetgenpy, which this package does not carry: only the surface stage "
+                                  "(normals, volume, shape derivative) is implemented")
+
+    def export_volume_mesh(self, filename, show_mesh=False, export_abaqus=False):
+        raise NotImplementedError("export_volume_mesh needs a tetrahedral mesh (tetgenpy) and gustaf, which this package does not "
+                                  "carry")
+
+
+def transform(x, t):
+    """The folding of an unfolded coordinate into one cell of a tiling of t cells (the fold of csrc/msgrid.hpp, in torch)."""
+    period = 4.0 / t                                            # two cells: one and its mirror image
+    return t * torch.abs(torch.remainder(x - t % 2, period) - period / 2) - 1

@@ -154,6 +154,14 @@ PROTOTYPES = {
     "dsdf_surf_plan": [_I64, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_I32)],
     "dsdf_surf_prepare": [_P, _I64, _P, _I64, _P, _SZ, C.POINTER(C.c_double), _P],
     "dsdf_surf_sample": [_P, _I64, _P, _I64, _P, _SZ, _I64, C.c_uint64, C.c_uint64, _F, _P, _P, _P, _P],
+    "dsdf_mt_plan": [_I64, _I64, C.POINTER(_SZ)],
+    "dsdf_mt_edge_keys": [_P, _I64, _I64, _P, _P],
+    "dsdf_mt_adjacency": [_P, _I64, _P, _P, _P, _P, _P, _SZ, _P],
+    "dsdf_mt_components": [_P, _I64, _P, _P, C.POINTER(_I32), _P, _SZ, _P],
+    "dsdf_mt_face_degenerate": [_P, _I64, _P, _I64, _P, _P],
+    "dsdf_mt_vertex_geometry": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P],
+    "dsdf_mt_volume": [_P, _I64, _P, _I64, _P, _P, _SZ, _P],
+    "dsdf_mt_project": [_P, _P, _P, _I64, _I64, C.POINTER(_F), _F, _P, _P],
 }
 
 _lib = None

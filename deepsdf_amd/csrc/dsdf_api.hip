@@ -27,6 +27,7 @@
 #include "msgrid.hpp"
 #include "msdiff.hpp"
 #include "pointset.hpp"
+#include "meshtopo.hpp"
 
 using namespace dsdf;
 
@@ -2696,6 +2697,187 @@ int dsdf_ms_caps(const DsdfMsGrid* grid, int64_t start, int64_t end, const DsdfM
   hipLaunchKernelGGL(ms_caps_kernel, dim3((unsigned)((n + MS_BLOCK - 1) / MS_BLOCK)), dim3(MS_BLOCK), 0, (hipStream_t)stream, g, c,
                      start, n, sdf);
   LAUNCH_OK("ms_caps_kernel");
+  return 0;
+}
+
+// ---- surface topology and geometry (meshtopo.hpp) ----------------------------------------------------------
+namespace {
+struct MtPlan { int64_t stat_blocks, vol_blocks, vol_slice; size_t stat_off, gf_off, flag_off, vol_off, ws; };
+constexpr int64_t MT_MAX_FACES = INT32_MAX / 3;   // a half-edge index 3 f + k is an int32
+
+int mt_plan(int64_t nf, MtPlan* P, WsTable* rec = nullptr) {
+  if (nf < 0 || nf > MT_MAX_FACES) return fail(DSDF_E_INVALID, "surface mesh: %lld faces (0 .. %lld)", (long long)nf, (long long)MT_MAX_FACES);
+  P->stat_blocks = (3 * nf + MT_BLOCK - 1) / MT_BLOCK;
+  P->vol_blocks = std::max<int64_t>(1, std::min<int64_t>((nf + MT_VOL_MIN_SLICE - 1) / MT_VOL_MIN_SLICE, MT_VOL_MAX_BLOCKS));
+  P->vol_slice = (nf + P->vol_blocks - 1) / P->vol_blocks;
+  WsCarver c(rec);
+  P->stat_off = c.take("mt_stat_part", -1, (size_t)std::max<int64_t>(P->stat_blocks, 1) * MT_STATS * 8);
+  P->gf_off = c.take("mt_cc_gf", -1, (size_t)std::max<int64_t>(nf, 1) * 4);
+  P->flag_off = c.take("mt_cc_flags", -1, (size_t)MT_CC_GROUP * 4);
+  P->vol_off = c.take("mt_vol_part", -1, (size_t)MT_VOL_MAX_BLOCKS * 8);
+  P->ws = c.finish(c.o);
+  return 0;
+}
+
+int mt_nverts(int64_t nv) {
+  if (nv < 1 || nv > INT32_MAX) return fail(DSDF_E_INVALID, "surface mesh: %lld vertices (1 .. %d)", (long long)nv, INT32_MAX);
+  return 0;
+}
+
+int mt_ws(const MtPlan& P, const void* ws, size_t ws_bytes) {
+  if (!ws) return fail(DSDF_E_INVALID, "surface mesh: NULL workspace");
+  if (ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "surface mesh: workspace %zu < %zu bytes", ws_bytes, P.ws);
+  if (((uintptr_t)ws & 255) != 0) return fail(DSDF_E_INVALID, "surface mesh: workspace not 256-byte aligned");
+  return 0;
+}
+
+inline dim3 mt_grid(int64_t n) { return dim3((unsigned)((n + MT_BLOCK - 1) / MT_BLOCK)); }
+}  // namespace
+
+int dsdf_mt_plan(int64_t n_verts, int64_t n_faces, size_t* ws_bytes) {
+  MtPlan P;
+  TRY(mt_plan(n_faces, &P, &t_last_plan));
+  if (n_verts < 0 || n_verts > INT32_MAX) return fail(DSDF_E_INVALID, "surface mesh: %lld vertices (0 .. %d)", (long long)n_verts, INT32_MAX);
+  if (!ws_bytes) return fail(DSDF_E_INVALID, "surface mesh plan: NULL output");
+  *ws_bytes = P.ws;
+  return 0;
+}
+
+int dsdf_mt_edge_keys(const int32_t* faces, int64_t n_faces, int64_t n_verts, int64_t* keys, void* stream) {
+  MtPlan P;
+  TRY(mt_plan(n_faces, &P));
+  TRY(mt_nverts(n_verts));
+  if (n_faces == 0) return 0;
+  if (!faces || !keys) return fail(DSDF_E_INVALID, "surface mesh: NULL faces or keys");
+  hipLaunchKernelGGL(mt_edge_keys_kernel, mt_grid(3 * n_faces), dim3(MT_BLOCK), 0, (hipStream_t)stream, faces, 3 * n_faces, (int)n_verts, keys);
+  LAUNCH_OK("mt_edge_keys_kernel");
+  return 0;
+}
+
+int dsdf_mt_adjacency(const int32_t* faces, int64_t n_faces, const int64_t* sorted_keys, const int64_t* order, int32_t* mate,
+                      int64_t* stats, void* ws, size_t ws_bytes, void* stream) {
+  MtPlan P;
+  TRY(mt_plan(n_faces, &P, &t_last_plan));
+  if (!stats) return fail(DSDF_E_INVALID, "surface mesh: NULL stats");
+  TRY(mt_ws(P, ws, ws_bytes));
+  if (n_faces == 0) return 0;
+  if (!faces || !sorted_keys || !order || !mate) return fail(DSDF_E_INVALID, "surface mesh: NULL faces, keys, order or mate");
+  hipStream_t st = (hipStream_t)stream;
+  int64_t* part = (int64_t*)((char*)ws + P.stat_off);
+  hipLaunchKernelGGL(mt_adjacency_kernel, mt_grid(3 * n_faces), dim3(MT_BLOCK), 0, st, faces, 3 * n_faces, sorted_keys, order, mate, part);
+  LAUNCH_OK("mt_adjacency_kernel");
+  hipLaunchKernelGGL(mt_stats_sum_kernel, dim3(1), dim3(MT_BLOCK), 0, st, (const int64_t*)part, P.stat_blocks, stats);
+  LAUNCH_OK("mt_stats_sum_kernel");
+  return 0;
+}
+
+// Waits for the stream: the change flags of every MT_CC_GROUP rounds are read on the host (as dsdf_surf_prepare reads its total).
+int dsdf_mt_components(const int32_t* mate, int64_t n_faces, int32_t* label, int32_t* size, int32_t* n_rounds, void* ws,
+                       size_t ws_bytes, void* stream) {
+  MtPlan P;
+  TRY(mt_plan(n_faces, &P, &t_last_plan));
+  if (n_rounds) *n_rounds = 0;
+  if (n_faces == 0) return 0;
+  if (!mate || !label) return fail(DSDF_E_INVALID, "surface mesh: NULL mate or label");
+  TRY(mt_ws(P, ws, ws_bytes));
+  hipStream_t st = (hipStream_t)stream;
+  const int nf = (int)n_faces;
+  int32_t* gf = (int32_t*)((char*)ws + P.gf_off);
+  int32_t* flags = (int32_t*)((char*)ws + P.flag_off);
+  const dim3 grid = mt_grid(n_faces);
+  hipLaunchKernelGGL(mt_cc_init_kernel, grid, dim3(MT_BLOCK), 0, st, label, nf);
+  LAUNCH_OK("mt_cc_init_kernel");
+  int rounds = 0;
+  for (bool done = false; !done;) {                          // no cap: f only decreases, so a round without a change comes
+    hipLaunchKernelGGL(mt_cc_flags_kernel, dim3(1), dim3(MT_BLOCK), 0, st, flags);
+    LAUNCH_OK("mt_cc_flags_kernel");
+    for (int r = 0; r < MT_CC_GROUP; ++r) {
+      hipLaunchKernelGGL(mt_cc_grand_kernel, grid, dim3(MT_BLOCK), 0, st, (const int32_t*)label, nf, gf);
+      LAUNCH_OK("mt_cc_grand_kernel");
+      hipLaunchKernelGGL(mt_cc_hook_kernel, grid, dim3(MT_BLOCK), 0, st, mate, nf, label, (const int32_t*)gf, flags + r);
+      LAUNCH_OK("mt_cc_hook_kernel");
+    }
+    int32_t host[MT_CC_GROUP];
+    HIP_OK(hipMemcpyAsync(host, flags, sizeof(host), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int r = 0; r < MT_CC_GROUP && !done; ++r) {
+      ++rounds;
+      done = host[r] == 0;
+    }
+  }
+  if (n_rounds) *n_rounds = rounds;
+  if (size) {
+    hipLaunchKernelGGL(mt_cc_zero_kernel, grid, dim3(MT_BLOCK), 0, st, size, nf);
+    LAUNCH_OK("mt_cc_zero_kernel");
+    hipLaunchKernelGGL(mt_cc_size_kernel, grid, dim3(MT_BLOCK), 0, st, (const int32_t*)label, nf, size);
+    LAUNCH_OK("mt_cc_size_kernel");
+  }
+  return 0;
+}
+
+int dsdf_mt_face_degenerate(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, uint8_t* out, void* stream) {
+  MtPlan P;
+  TRY(mt_plan(n_faces, &P));
+  TRY(mt_nverts(n_verts));
+  if (n_faces == 0) return 0;
+  if (!verts || !faces || !out) return fail(DSDF_E_INVALID, "surface mesh: NULL verts, faces or output");
+  hipLaunchKernelGGL(mt_degenerate_kernel, mt_grid(n_faces), dim3(MT_BLOCK), 0, (hipStream_t)stream, verts, (int)n_verts, faces, (int)n_faces, out);
+  LAUNCH_OK("mt_degenerate_kernel");
+  return 0;
+}
+
+int dsdf_mt_vertex_geometry(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int64_t* corner_order,
+                            const int64_t* vstart, float* normals, float* vol_grad, void* stream) {
+  MtPlan P;
+  TRY(mt_plan(n_faces, &P));
+  TRY(mt_nverts(n_verts));
+  if (!normals && !vol_grad) return fail(DSDF_E_INVALID, "surface mesh: every output is NULL");
+  if (!verts || !vstart || (n_faces > 0 && (!faces || !corner_order)))
+    return fail(DSDF_E_INVALID, "surface mesh: NULL verts, faces, corner_order or vstart");
+  hipLaunchKernelGGL(mt_vertex_kernel, mt_grid(n_verts), dim3(MT_BLOCK), 0, (hipStream_t)stream, verts, (int)n_verts, faces, 3 * n_faces,
+                     corner_order, vstart, normals, vol_grad);
+  LAUNCH_OK("mt_vertex_kernel");
+  return 0;
+}
+
+int dsdf_mt_volume(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, double* volume, void* ws,
+                   size_t ws_bytes, void* stream) {
+  MtPlan P;
+  TRY(mt_plan(n_faces, &P, &t_last_plan));
+  TRY(mt_nverts(n_verts));
+  if (!volume || ((uintptr_t)volume & 7) != 0) return fail(DSDF_E_INVALID, "surface mesh: NULL or misaligned volume");
+  TRY(mt_ws(P, ws, ws_bytes));
+  if (n_faces == 0) return 0;
+  if (!verts || !faces) return fail(DSDF_E_INVALID, "surface mesh: NULL verts or faces");
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)((char*)ws + P.vol_off);
+  hipLaunchKernelGGL(mt_volume_part_kernel, dim3((unsigned)P.vol_blocks), dim3(MT_BLOCK), 0, st, verts, (int)n_verts, faces, n_faces,
+                     P.vol_slice, part);
+  LAUNCH_OK("mt_volume_part_kernel");
+  hipLaunchKernelGGL(mt_volume_final_kernel, dim3(1), dim3(MT_BLOCK), 0, st, (const double*)part, (int)P.vol_blocks, volume);
+  LAUNCH_OK("mt_volume_final_kernel");
+  return 0;
+}
+
+int dsdf_mt_project(const float* jac, const int32_t* axis, const float* normals, int64_t n_verts, int64_t R, const float* stretch,
+                    float clip, float* out, void* stream) {
+  if (n_verts < 0 || n_verts > INT32_MAX) return fail(DSDF_E_INVALID, "surface mesh: %lld vertices (0 .. %d)", (long long)n_verts, INT32_MAX);
+  if (R < 1 || R > INT32_MAX) return fail(DSDF_E_INVALID, "projection: %lld Jacobian columns (1 .. %d)", (long long)R, INT32_MAX);
+  if (!stretch) return fail(DSDF_E_INVALID, "projection: NULL stretch");
+  MtStretch s;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(stretch[a])) return fail(DSDF_E_INVALID, "projection: stretch %d is not finite", a);
+    s.s[a] = stretch[a];
+  }
+  if (std::isnan(clip)) return fail(DSDF_E_INVALID, "projection: clip is NaN");
+  if (n_verts == 0) return 0;
+  if (!jac || !axis || !normals || !out) return fail(DSDF_E_INVALID, "projection: NULL jac, axis, normals or out");
+  const bool vec = R % 4 == 0 && ((reinterpret_cast<uintptr_t>(jac) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const int64_t Rq = vec ? R / 4 : R, total = n_verts * Rq;
+  if ((total + MT_BLOCK - 1) / MT_BLOCK > INT32_MAX) return fail(DSDF_E_INVALID, "projection: %lld x %lld entries in one call", (long long)n_verts, (long long)R);
+  if (vec) hipLaunchKernelGGL((mt_project_kernel<4>), mt_grid(total), dim3(MT_BLOCK), 0, (hipStream_t)stream, jac, axis, normals, total, Rq, s, clip, out);
+  else hipLaunchKernelGGL((mt_project_kernel<1>), mt_grid(total), dim3(MT_BLOCK), 0, (hipStream_t)stream, jac, axis, normals, total, Rq, s, clip, out);
+  LAUNCH_OK("mt_project_kernel");
   return 0;
 }
 

@@ -534,6 +534,60 @@ int dsdf_msd_jvp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* 
 int dsdf_msd_vjp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* grad_verts, float* grad_cp, void* ws,
                  size_t ws_bytes, void* stream);
 
+/* ---- surface topology and geometry: the surface half of analysis/geometry.py DeepSDFMesh (trimesh's face_adjacency, connected
+ * components, is_watertight, vertex_normals; the volume and the normal-projected shape derivative), on the device (csrc/meshtopo.hpp)
+ * verts [n_verts][3] fp32, faces [n_faces][3] int32 as for dsdf_msdf_prepare; n_faces <= INT32_MAX / 3.  Every index read from a
+ * caller's array (face indices, order, corner_order, vstart, mate, axis) is clamped into its range on the device before it is used
+ * as an address: a badly sorted or out-of-range array gives an unspecified result and no access outside the arrays.  Sorting is
+ * the caller's (a stable sort); the entries take the sorted arrays.  n_faces == 0 launches nothing.  No floating-point atomics
+ * anywhere; two identical calls give identical bytes.
+ *   dsdf_mt_plan             [host] one workspace (256-byte aligned, planner conventions: dsdf_debug_ws_redzone / _regions) serves
+ *                            dsdf_mt_adjacency, dsdf_mt_components and dsdf_mt_volume of a mesh of n_faces faces
+ *   dsdf_mt_edge_keys        keys [3 n_faces] int64: half-edge h = 3 f + k runs faces[f][k] -> faces[f][(k + 1) % 3]; its key is
+ *                            (min << 32) | max of the two vertex ids, -1 when they are equal (an index-degenerate face)
+ *   dsdf_mt_adjacency        sorted_keys [3 n_faces] = the keys in non-decreasing order, order [3 n_faces] int64 = the half-edge at each
+ *                            sorted position.  mate [3 n_faces] int32: a half-edge whose key is >= 0 and occurs exactly twice gets the
+ *                            other half-edge of that key, every other one -1 (trimesh's face_adjacency: an edge of one face or of more
+ *                            than two joins nothing).  stats [6] int64 (device): distinct edges, boundary edges (one face), non-manifold
+ *                            edges (more than two), paired edges, paired edges whose two half-edges run in the SAME direction
+ *                            (inconsistent winding), half-edges with key -1.  Watertight: the boundary, non-manifold and key -1
+ *                            counts are 0; winding-consistent: also the same-direction count.  Integer sums in a fixed order.
+ *   dsdf_mt_components       label [n_faces] int32: the lowest face index of the face's component under the mate relation; size
+ *                            [n_faces] int32 (may be NULL): the face count of the component whose lowest face is r at r, 0 elsewhere.
+ *                            Min-hooking with shortcutting, repeated until a round changes nothing; *n_rounds ([host], may be NULL) =
+ *                            the rounds run, the unchanged one included.  int32 atomicMin / atomicAdd decide only the order of the
+ *                            work: the fixed point and the sizes do not depend on it.  This entry WAITS FOR THE STREAM: it reads the
+ *                            rounds' change flags on the host, four rounds at a time (as dsdf_surf_prepare reads its total).
+ *   dsdf_mt_face_degenerate  out [n_faces] uint8: 1 for a face with a repeated index or of zero area by the mesh SDF's rule,
+ *                            |ab x ac|^2 <= 1e-14 (longest edge)^4 in fp64 on the fp32 vertices; 0 otherwise
+ *   dsdf_mt_vertex_geometry  corner_order [3 n_faces] int64: the corners 3 f + k stably sorted by their vertex, vstart [n_verts + 1]
+ *                            int64: the start of every vertex's run.  Per vertex, over its corners in that order, in fp64: corner a of
+ *                            face (a, b, c) in cyclic order, e1 = b - a, e2 = c - a, n = e1 x e2:
+ *                              normals  [n_verts][3] (may be NULL): s = sum atan2(|n|, e1 . e2) n / |n| over the faces that are not
+ *                                       zero-area, s / |s| rounded to fp32 once; exactly 0 when s = 0 or the vertex has no corner
+ *                              vol_grad [n_verts][3] (may be NULL): d volume / d vertex = (1 / 6) sum b x c over every corner
+ *                                       (absolute positions, zero-area faces included), rounded to fp32 once
+ *   dsdf_mt_volume           *volume (device double, 8-byte aligned) = (1 / 6) sum_f a . (b x c) in fp64: min(ceil(n_faces / 4096),
+ *                            1024) workgroup sums over contiguous slices, then their sum by one workgroup (dsdf_mean_f64's shape)
+ *   dsdf_mt_project          jac [n_verts][R], axis [n_verts]: dsdf_msd_jacobian's (full = 0), R = ncp * L.  With a = axis[v]:
+ *                            j = jac[v][r] * stretch[a]; if clip > 0 and |j| > clip: j = 0 (the reference's outlier rule, after the
+ *                            stretch); out [n_verts][3][R]: out[v][d][r] = (j * n[a]) * n[d], every product rounded to fp32 on
+ *                            its own.  stretch [host] 3 floats.  n_verts == 0 launches nothing.
+ * Every argument error returns DSDF_E_INVALID before anything is launched. */
+int dsdf_mt_plan(int64_t n_verts, int64_t n_faces, size_t* ws_bytes);                                  /* [host] */
+int dsdf_mt_edge_keys(const int32_t* faces, int64_t n_faces, int64_t n_verts, int64_t* keys, void* stream);
+int dsdf_mt_adjacency(const int32_t* faces, int64_t n_faces, const int64_t* sorted_keys, const int64_t* order, int32_t* mate,
+                      int64_t* stats, void* ws, size_t ws_bytes, void* stream);
+int dsdf_mt_components(const int32_t* mate, int64_t n_faces, int32_t* label, int32_t* size, int32_t* n_rounds /*[host]*/, void* ws,
+                       size_t ws_bytes, void* stream);
+int dsdf_mt_face_degenerate(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, uint8_t* out, void* stream);
+int dsdf_mt_vertex_geometry(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int64_t* corner_order,
+                            const int64_t* vstart, float* normals, float* vol_grad, void* stream);
+int dsdf_mt_volume(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, double* volume, void* ws,
+                   size_t ws_bytes, void* stream);
+int dsdf_mt_project(const float* jac, const int32_t* axis, const float* normals, int64_t n_verts, int64_t R,
+                    const float* stretch /*[host]*/, float clip, float* out, void* stream);
+
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */
 int dsdf_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
