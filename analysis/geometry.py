@@ -60,12 +60,17 @@ class DeepSDFMesh:
         """Mesh and d vertices / d control points for these control points; x stretched by 2; then the reference's clean-up:
         the largest face-adjacency component when ``remove_orphans``, the watertightness test, and degenerate faces dropped when it
         fails.  Sets ``surface_mesh`` (a SurfaceMesh whose vertex ids are those of the derivative) and ``jacobian`` (the
-        MicrostructureMeshDiff: its vjp / jvp / jacobian(), unstretched and unclipped; get_dTheta_surface applies both)."""
+        MicrostructureMeshDiff: its vjp / jvp / jacobian(), unstretched and unclipped; get_dTheta_surface applies both).
+
+        Optional option keys ``sparse_block`` (cells per block edge) and ``sparse_lipschitz`` (default 1.0): decode only the blocks
+        the surface passes through (deepsdf_amd.mesh.follow_surface).  Absent: the dense grid."""
         tiling = self.options["tiling"]
         N = [self.options["N_base_reconstruction"] * t + 1 for t in tiling]
         self.latent_vec_interpolation.control_points = control_points
         self.diff = microstructure_mesh_diff(tiling, self.decoder, self.latent_vec_interpolation, N,
-                                             cap_border_dict=self.options["cap_border_dict"])
+                                             cap_border_dict=self.options["cap_border_dict"],
+                                             block=self.options.get("sparse_block"),
+                                             lipschitz=self.options.get("sparse_lipschitz", 1.0))
         mesh = SurfaceMesh.from_diff(self.diff, STRETCH)
         if self.options["remove_orphans"]:
             self.logger.debug("Removing orphan meshs")

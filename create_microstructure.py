@@ -48,7 +48,7 @@ def parse_caps(items):
 
 
 def main(experiment_directory, checkpoint, tiling, codes, out, degrees=(1, 1, 1), control_points=None, resolution=256,
-         caps=None, max_batch=32, jacobian=None):
+         caps=None, max_batch=32, jacobian=None, block=None, lipschitz=1.0):
     if not torch.cuda.is_available():
         raise RuntimeError("create_microstructure.py (deepsdf_amd) needs an AMD GPU: the HIP path has no CPU fallback")
     decoder = ws.load_trained_model(experiment_directory, checkpoint)
@@ -66,17 +66,19 @@ def main(experiment_directory, checkpoint, tiling, codes, out, degrees=(1, 1, 1)
     cp = torch.stack([latent[c].detach().reshape(-1).cpu() for c in codes]).numpy()
     field = BSplineField(degrees, [uniform_clamped_knots(n, p) for n, p in zip(control_points, degrees)], cp)
     name = out[:-4] if out.endswith(".ply") else out
-    deep_sdf.mesh.create_mesh_microstructure(list(tiling), decoder, field, name, N=resolution, max_batch=int(max_batch ** 3),
-                                             cap_border_dict=caps, save_ply_file=True)
+    with deep_sdf.mesh.sparse_grid(block, lipschitz):
+        deep_sdf.mesh.create_mesh_microstructure(list(tiling), decoder, field, name, N=resolution, max_batch=int(max_batch ** 3),
+                                                 cap_border_dict=caps, save_ply_file=True)
     print(f"wrote {name}.ply")
     if jacobian:
-        d = deep_sdf.mesh.microstructure_mesh_diff(list(tiling), decoder, field, resolution, int(max_batch ** 3), caps)
+        d = deep_sdf.mesh.microstructure_mesh_diff(list(tiling), decoder, field, resolution, int(max_batch ** 3), caps, block=block,
+                                                   lipschitz=lipschitz)
         jac, axis = d.jacobian()
         np.savez(jacobian, verts=d.verts.cpu().numpy(), faces=d.faces.cpu().numpy(), jac=jac.cpu().numpy(), axis=axis.cpu().numpy())
         print(f"wrote {jacobian}")
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser(description="Write the PLY mesh of a tiled microstructure over trained latent codes.")
     parser.add_argument("--experiment_directory", "-e", type=str, required=True)
     parser.add_argument("--checkpoint", "-c", type=str, default="latest")
@@ -90,6 +92,11 @@ if __name__ == "__main__":
     parser.add_argument("--jacobian", type=str, default=None, metavar="FILE.npz",
                         help="also write verts, faces, jac [V, ncp, L] (d vertex / d control points along axis) and axis")
     parser.add_argument("--output", "-o", type=str, required=True)
-    args = parser.parse_args()
+    deep_sdf.mesh.add_sparse_args(parser)
+    return parser
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
     main(args.experiment_directory, args.checkpoint, args.tiling, args.codes, args.output, args.degrees, args.control_points,
-         args.resolution, parse_caps(args.cap), args.max_batch, args.jacobian)
+         args.resolution, parse_caps(args.cap), args.max_batch, args.jacobian, args.block, args.lipschitz)

@@ -37,9 +37,14 @@ def _mesh(decoder, latent_in, fname, N, max_batch):
     return True
 
 
-def main(experiment_directory, checkpoint, max_batch=32, resolution=256):
+def main(experiment_directory, checkpoint, max_batch=32, resolution=256, block=None, lipschitz=1.0):
     if not torch.cuda.is_available():
         raise RuntimeError("create_ply_files_from_latent.py (deepsdf_amd) needs an AMD GPU: the HIP path has no CPU fallback")
+    with deep_sdf.mesh.sparse_grid(block, lipschitz):
+        _main(experiment_directory, checkpoint, max_batch, resolution)
+
+
+def _main(experiment_directory, checkpoint, max_batch, resolution):
     decoder = ws.load_trained_model(experiment_directory, checkpoint)
     decoder.eval()
     latent = ws.load_latent_vectors(experiment_directory, checkpoint)
@@ -71,7 +76,7 @@ def main(experiment_directory, checkpoint, max_batch=32, resolution=256):
             i_sample += 1
 
 
-if __name__ == "__main__":
+def build_parser():
     import argparse
 
     parser = argparse.ArgumentParser(description="Write a PLY mesh for every latent code of a trained experiment.")
@@ -79,5 +84,10 @@ if __name__ == "__main__":
     parser.add_argument("--checkpoint", "-c", type=str, default="latest")
     parser.add_argument("--max_batch", "-b", type=int, default=32, help="decode chunk = max_batch^3 grid points")
     parser.add_argument("--resolution", type=int, default=256, help="grid points per axis (N of create_mesh)")
-    args = parser.parse_args()
-    main(args.experiment_directory, args.checkpoint, args.max_batch, args.resolution)
+    deep_sdf.mesh.add_sparse_args(parser)
+    return parser
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
+    main(args.experiment_directory, args.checkpoint, args.max_batch, args.resolution, args.block, args.lipschitz)

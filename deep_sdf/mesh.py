@@ -3,4 +3,5 @@ meshing of deepsdf_amd/mesh.py (HIP marching cubes, in-house PLY writer, microst
 respect to the spline's control points assembled in HIP)."""
 from deepsdf_amd.mesh import convert_sdf_samples_to_ply, create_mesh  # noqa: F401
 from deepsdf_amd.mesh import (CapBorderDict, CapType, create_mesh_microstructure, create_mesh_microstructure_diff,  # noqa: F401
-                              location_lookup, microstructure_mesh_diff, microstructure_sdf_grid, sdf_struct)
+                              location_lookup, microstructure_mesh_diff, microstructure_sdf_grid, sdf_struct, sparse_grid)
+from deepsdf_amd.mesh import add_sparse_args  # noqa: F401

@@ -80,6 +80,11 @@ class DsdfMsdBand(C.Structure):
                 ("L", C.c_int32)]
 
 
+class DsdfSgPlan(C.Structure):
+    _fields_ = [("blocks", C.c_int32 * 3), ("n_blocks", C.c_int64), ("n_coarse", C.c_int64), ("n_points", C.c_int64),
+                ("ws_bytes", C.c_size_t), ("state_offset", C.c_size_t), ("have_offset", C.c_size_t)]
+
+
 class DsdfWsRegion(C.Structure):      # debug only: one row of dsdf_debug_ws_regions
     _fields_ = [("name", C.c_char * 24), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
@@ -162,6 +167,16 @@ PROTOTYPES = {
     "dsdf_mt_vertex_geometry": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P],
     "dsdf_mt_volume": [_P, _I64, _P, _I64, _P, _P, _SZ, _P],
     "dsdf_mt_project": [_P, _P, _P, _I64, _I64, C.POINTER(_F), _F, _P, _P],
+    "dsdf_sg_plan": [_I32, _I32, _I32, _I32, C.POINTER(DsdfSgPlan)],
+    "dsdf_sg_coarse": [_I32, _I32, _I32, _I32, _P, _P, _SZ, _P],
+    "dsdf_sg_seed": [_P, _I32, _I32, _I32, _I32, _F, _F, _P, _P, _SZ, _P],
+    "dsdf_sg_grow": [_P, _I32, _I32, _I32, _I32, _F, _P, _P, _SZ, _P],
+    "dsdf_sg_points_count": [_I32, _I32, _I32, _I32, _P, _P, _SZ, _P],
+    "dsdf_sg_points_emit": [_I32, _I32, _I32, _I32, _I64, _P, _P, _SZ, _P],
+    "dsdf_sg_fill": [_P, _I32, _I32, _I32, _I32, _P, _SZ, _P],
+    "dsdf_sg_coords": [_I32, _I32, _I32, C.POINTER(_F), C.POINTER(_F), _P, _I64, _P, _P],
+    "dsdf_sg_scatter": [_P, _I64, _P, _P, _I64, _P],
+    "dsdf_sg_caps_at": [C.POINTER(DsdfMsGrid), _P, _I64, C.POINTER(DsdfMsCap), _I32, _P, _P],
 }
 
 _lib = None

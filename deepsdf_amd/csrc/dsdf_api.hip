@@ -28,6 +28,7 @@
 #include "msdiff.hpp"
 #include "pointset.hpp"
 #include "meshtopo.hpp"
+#include "sparsegrid.hpp"
 
 using namespace dsdf;
 
@@ -2878,6 +2879,196 @@ int dsdf_mt_project(const float* jac, const int32_t* axis, const float* normals,
   if (vec) hipLaunchKernelGGL((mt_project_kernel<4>), mt_grid(total), dim3(MT_BLOCK), 0, (hipStream_t)stream, jac, axis, normals, total, Rq, s, clip, out);
   else hipLaunchKernelGGL((mt_project_kernel<1>), mt_grid(total), dim3(MT_BLOCK), 0, (hipStream_t)stream, jac, axis, normals, total, Rq, s, clip, out);
   LAUNCH_OK("mt_project_kernel");
+  return 0;
+}
+
+// ---- surface following on blocks of the dense grid (sparsegrid.hpp) ------------------------------------------
+// The reference builds the coordinates of all N^3 grid points and decodes every one (deep_sdf/mesh.py:42-70 for create_mesh,
+// :262-271 for the microstructure grid); these entries list the points a mesh needs, so that only those are decoded.
+namespace {
+struct SgPlan {
+  SgGrid g;
+  int64_t nparts;
+  size_t state, pend, have, part, offs, total;
+};
+
+int sg_plan(int32_t nx, int32_t ny, int32_t nz, int32_t block, SgPlan* P, WsTable* rec = nullptr) {
+  if (nx < 2 || ny < 2 || nz < 2 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
+    return fail(DSDF_E_INVALID, "sparse grid: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
+  if (block < 2) return fail(DSDF_E_INVALID, "sparse grid: block edge %d < 2 cells", block);
+  SgGrid& g = P->g;
+  g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
+  g.b = std::min<int32_t>(block, MC_MAX_DIM);          // an edge past the grid is one block per axis either way
+  g.npts = g.nblk = g.ncoarse = 1;
+  for (int a = 0; a < 3; ++a) {
+    g.nb[a] = (g.n[a] - 1 + g.b - 1) / g.b;
+    g.nc[a] = g.nb[a] + 1;
+    g.npts *= g.n[a];
+    g.nblk *= g.nb[a];
+    g.ncoarse *= g.nc[a];
+  }
+  P->nparts = (g.npts + SG_BLOCK - 1) / SG_BLOCK;      // a per-block pass has no more workgroups: nblk <= npts
+  WsCarver c(rec);
+  P->state = c.take("sg_state", -1, (size_t)g.nblk);
+  P->pend = c.take("sg_pend", -1, (size_t)g.nblk);
+  P->have = c.take("sg_have", -1, (size_t)g.npts);
+  P->part = c.take("sg_part", -1, (size_t)P->nparts * 4);
+  P->offs = c.take("sg_offs", -1, (size_t)(P->nparts + 1) * 8);
+  P->total = c.finish(c.o);
+  return 0;
+}
+
+int sg_setup(int32_t nx, int32_t ny, int32_t nz, int32_t block, void* ws, size_t ws_bytes, SgPlan* P, SgWs* w) {
+  TRY(sg_plan(nx, ny, nz, block, P, &t_last_plan));
+  if (!ws) return fail(DSDF_E_INVALID, "sparse grid: NULL workspace");
+  if (ws_bytes < P->total) return fail(DSDF_E_WORKSPACE, "sparse grid: workspace %zu < %zu bytes", ws_bytes, P->total);
+  if (((uintptr_t)ws & 255) != 0) return fail(DSDF_E_INVALID, "sparse grid: workspace not 256-byte aligned");
+  char* b = (char*)ws;
+  w->state = (uint8_t*)(b + P->state); w->pend = (uint8_t*)(b + P->pend); w->have = (uint8_t*)(b + P->have);
+  w->part = (int32_t*)(b + P->part); w->offs = (int64_t*)(b + P->offs);
+  w->nparts = P->nparts;
+  return 0;
+}
+
+inline dim3 sg_launch(int64_t n) { return dim3((unsigned)((n + SG_BLOCK - 1) / SG_BLOCK)); }
+}  // namespace
+
+int dsdf_sg_plan(int32_t nx, int32_t ny, int32_t nz, int32_t block, DsdfSgPlan* plan) {
+  SgPlan P;
+  TRY(sg_plan(nx, ny, nz, block, &P, &t_last_plan));
+  if (!plan) return fail(DSDF_E_INVALID, "sparse grid plan: NULL output");
+  for (int a = 0; a < 3; ++a) plan->blocks[a] = P.g.nb[a];
+  plan->n_blocks = P.g.nblk; plan->n_coarse = P.g.ncoarse; plan->n_points = P.g.npts;
+  plan->ws_bytes = P.total;
+  plan->state_offset = P.state;
+  plan->have_offset = P.have;
+  return 0;
+}
+
+int dsdf_sg_coarse(int32_t nx, int32_t ny, int32_t nz, int32_t block, int64_t* indices, void* ws, size_t ws_bytes, void* stream) {
+  SgPlan P; SgWs w;
+  TRY(sg_setup(nx, ny, nz, block, ws, ws_bytes, &P, &w));
+  if (!indices) return fail(DSDF_E_INVALID, "sparse grid coarse: NULL indices");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_OK(hipMemsetAsync(w.have, 0, (size_t)P.g.npts, st));
+  hipLaunchKernelGGL(sg_coarse_kernel, sg_launch(P.g.ncoarse), dim3(SG_BLOCK), 0, st, P.g, indices, w.have);
+  LAUNCH_OK("sg_coarse_kernel");
+  return 0;
+}
+
+int dsdf_sg_seed(const float* sdf, int32_t nx, int32_t ny, int32_t nz, int32_t block, float level, float thr, int64_t* n_new, void* ws,
+                 size_t ws_bytes, void* stream) {
+  SgPlan P; SgWs w;
+  TRY(sg_setup(nx, ny, nz, block, ws, ws_bytes, &P, &w));
+  if (!sdf || !n_new) return fail(DSDF_E_INVALID, "sparse grid seed: NULL sdf or n_new");
+  if (!(thr >= 0.f) || !std::isfinite(thr) || std::isnan(level)) return fail(DSDF_E_INVALID, "sparse grid seed: thr %g must be finite and >= 0, level %g a number", (double)thr, (double)level);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid = sg_launch(P.g.nblk);
+  hipLaunchKernelGGL(sg_seed_kernel, grid, dim3(SG_BLOCK), 0, st, P.g, sdf, level, thr, w.state, w.part);
+  LAUNCH_OK("sg_seed_kernel");
+  hipLaunchKernelGGL(sg_sum_kernel, dim3(1), dim3(SG_BLOCK), 0, st, (const int32_t*)w.part, (int64_t)grid.x, n_new);
+  LAUNCH_OK("sg_sum_kernel");
+  return 0;
+}
+
+int dsdf_sg_grow(const float* sdf, int32_t nx, int32_t ny, int32_t nz, int32_t block, float level, int64_t* n_new, void* ws,
+                 size_t ws_bytes, void* stream) {
+  SgPlan P; SgWs w;
+  TRY(sg_setup(nx, ny, nz, block, ws, ws_bytes, &P, &w));
+  if (!sdf || !n_new) return fail(DSDF_E_INVALID, "sparse grid grow: NULL sdf or n_new");
+  if (std::isnan(level)) return fail(DSDF_E_INVALID, "sparse grid grow: level is NaN");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid = sg_launch(P.g.nblk);
+  hipLaunchKernelGGL(sg_grow_mark_kernel, grid, dim3(SG_BLOCK), 0, st, P.g, sdf, level, (const uint8_t*)w.state, w.pend);
+  LAUNCH_OK("sg_grow_mark_kernel");
+  hipLaunchKernelGGL(sg_grow_apply_kernel, grid, dim3(SG_BLOCK), 0, st, P.g.nblk, w.state, (const uint8_t*)w.pend, w.part);
+  LAUNCH_OK("sg_grow_apply_kernel");
+  hipLaunchKernelGGL(sg_sum_kernel, dim3(1), dim3(SG_BLOCK), 0, st, (const int32_t*)w.part, (int64_t)grid.x, n_new);
+  LAUNCH_OK("sg_sum_kernel");
+  return 0;
+}
+
+int dsdf_sg_points_count(int32_t nx, int32_t ny, int32_t nz, int32_t block, int64_t* n_points, void* ws, size_t ws_bytes, void* stream) {
+  SgPlan P; SgWs w;
+  TRY(sg_setup(nx, ny, nz, block, ws, ws_bytes, &P, &w));
+  if (!n_points) return fail(DSDF_E_INVALID, "sparse grid points: NULL n_points");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(sg_points_count_kernel, sg_launch(P.g.npts), dim3(SG_BLOCK), 0, st, P.g, (const uint8_t*)w.state, (const uint8_t*)w.have, w.part);
+  LAUNCH_OK("sg_points_count_kernel");
+  hipLaunchKernelGGL(sg_scan_kernel, dim3(1), dim3(SG_SCAN_THREADS), 0, st, (const int32_t*)w.part, P.nparts, w.offs, n_points);
+  LAUNCH_OK("sg_scan_kernel");
+  return 0;
+}
+
+int dsdf_sg_points_emit(int32_t nx, int32_t ny, int32_t nz, int32_t block, int64_t n, int64_t* indices, void* ws, size_t ws_bytes,
+                        void* stream) {
+  SgPlan P; SgWs w;
+  TRY(sg_setup(nx, ny, nz, block, ws, ws_bytes, &P, &w));
+  if (n < 0 || n > P.g.npts) return fail(DSDF_E_INVALID, "sparse grid points: %lld indices (0 .. %lld)", (long long)n, (long long)P.g.npts);
+  if (n == 0) return 0;
+  if (!indices) return fail(DSDF_E_INVALID, "sparse grid points: NULL indices");
+  hipLaunchKernelGGL(sg_points_emit_kernel, sg_launch(P.g.npts), dim3(SG_BLOCK), 0, (hipStream_t)stream, P.g, (const uint8_t*)w.state, w.have,
+                     (const int64_t*)w.offs, n, indices);
+  LAUNCH_OK("sg_points_emit_kernel");
+  return 0;
+}
+
+int dsdf_sg_fill(float* sdf, int32_t nx, int32_t ny, int32_t nz, int32_t block, void* ws, size_t ws_bytes, void* stream) {
+  SgPlan P; SgWs w;
+  TRY(sg_setup(nx, ny, nz, block, ws, ws_bytes, &P, &w));
+  if (!sdf) return fail(DSDF_E_INVALID, "sparse grid fill: NULL sdf");
+  hipLaunchKernelGGL(sg_fill_kernel, sg_launch(P.g.npts), dim3(SG_BLOCK), 0, (hipStream_t)stream, P.g, (const uint8_t*)w.have, sdf);
+  LAUNCH_OK("sg_fill_kernel");
+  return 0;
+}
+
+int dsdf_sg_coords(int32_t nx, int32_t ny, int32_t nz, const float* voxel_size, const float* origin, const int64_t* indices, int64_t n,
+                   float* xyz, void* stream) {
+  if (nx < 1 || ny < 1 || nz < 1 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
+    return fail(DSDF_E_INVALID, "sparse grid coords: grid %d x %d x %d outside [1, %d] per axis", nx, ny, nz, MC_MAX_DIM);
+  if (!voxel_size || !origin) return fail(DSDF_E_INVALID, "sparse grid coords: NULL voxel_size or origin");
+  if (n < 0) return fail(DSDF_E_INVALID, "sparse grid coords: %lld indices", (long long)n);
+  if (n == 0) return 0;
+  if (!indices || !xyz) return fail(DSDF_E_INVALID, "sparse grid coords: NULL indices or xyz");
+  SgAxes g;
+  g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
+  for (int a = 0; a < 3; ++a) { g.vs[a] = voxel_size[a]; g.org[a] = origin[a]; }
+  hipLaunchKernelGGL(sg_coords_kernel, sg_launch(n), dim3(SG_BLOCK), 0, (hipStream_t)stream, g, indices, n, xyz);
+  LAUNCH_OK("sg_coords_kernel");
+  return 0;
+}
+
+int dsdf_sg_scatter(const int64_t* indices, int64_t n, const float* values, float* sdf, int64_t n_points, void* stream) {
+  if (n < 0 || n_points < 1) return fail(DSDF_E_INVALID, "sparse grid scatter: %lld values into %lld points", (long long)n, (long long)n_points);
+  if (n == 0) return 0;
+  if (!indices || !values || !sdf) return fail(DSDF_E_INVALID, "sparse grid scatter: NULL indices, values or sdf");
+  hipLaunchKernelGGL(sg_scatter_kernel, sg_launch(n), dim3(SG_BLOCK), 0, (hipStream_t)stream, indices, n, values, sdf, n_points);
+  LAUNCH_OK("sg_scatter_kernel");
+  return 0;
+}
+
+int dsdf_sg_caps_at(const DsdfMsGrid* grid, const int64_t* indices, int64_t n, const DsdfMsCap* caps, int32_t n_caps, float* sdf,
+                    void* stream) {
+  MsGrid g;
+  int64_t npts;
+  TRY(ms_grid(grid, &g, &npts));
+  if (n < 0) return fail(DSDF_E_INVALID, "sparse grid caps: %lld indices", (long long)n);
+  if (n_caps < 0 || n_caps > SG_MAX_CAPS) return fail(DSDF_E_INVALID, "sparse grid caps: %d records (0 .. %d)", n_caps, SG_MAX_CAPS);
+  if (n_caps > 0 && !caps) return fail(DSDF_E_INVALID, "sparse grid caps: NULL records");
+  SgCaps c;
+  c.ncaps = n_caps;
+  for (int a = 0; a < 3; ++a) { c.n[a] = g.n[a]; c.vs[a] = g.vs[a]; c.org[a] = g.org[a]; }
+  for (int r = 0; r < n_caps; ++r) {
+    if (caps[r].dim < 0 || caps[r].dim > 2) return fail(DSDF_E_INVALID, "sparse grid caps: record %d names axis %d", r, caps[r].dim);
+    if (caps[r].cap != -1 && caps[r].cap != 1) return fail(DSDF_E_INVALID, "sparse grid caps: record %d has cap %d (must be -1 or 1)", r, caps[r].cap);
+    if (caps[r].m != -1.f && caps[r].m != 1.f) return fail(DSDF_E_INVALID, "sparse grid caps: record %d has multiplier %g (must be -1 or 1)", r, (double)caps[r].m);
+    if (!std::isfinite(caps[r].c)) return fail(DSDF_E_INVALID, "sparse grid caps: record %d has a non-finite plane", r);
+    c.r[r].dim = caps[r].dim; c.r[r].cap = caps[r].cap; c.r[r].m = caps[r].m; c.r[r].c = caps[r].c;
+  }
+  if (n == 0) return 0;
+  if (!indices || !sdf) return fail(DSDF_E_INVALID, "sparse grid caps: NULL indices or sdf");
+  hipLaunchKernelGGL(sg_caps_kernel, sg_launch(n), dim3(SG_BLOCK), 0, (hipStream_t)stream, c, indices, n, sdf);
+  LAUNCH_OK("sg_caps_kernel");
   return 0;
 }
 

@@ -13,10 +13,18 @@ convert_sdf_samples_to_ply :86-155) with every step on the GPU.
     diff   microstructure_mesh_diff / create_mesh_microstructure_diff (:346-454): d vertices / d control points assembled in closed
                             form (csrc/msdiff.hpp) from one input-gradient pass over the band of grid points that carry a vertex
 
+    sparse follow_surface   surface following on blocks of the same dense grid (csrc/sparsegrid.hpp): the coarse lattice
+                            is decoded, blocks near the surface are seeded and grown across mixed-sign faces, only their points
+                            are decoded, the rest is filled with a coarse value of the right sign.  block= / lipschitz= on
+                            sdf_grid, microstructure_sdf_grid and microstructure_mesh_diff; the reference-named functions honour
+                            the context manager sparse_grid(block, lipschitz).  Off (block=None) by default.
+
 There is no CPU path: the grid and the marching cubes need a HIP device (a grid handed in on the host is moved there).
 """
+import contextlib
 import ctypes as C
 import logging
+import math
 import time
 from typing import TypedDict
 
@@ -151,12 +159,195 @@ def _is_hip_decoder(dec):
     return isinstance(dec, Decoder)
 
 
-def sdf_grid(decoder, latent, N, max_batch=32 ** 3, voxel_origin=(-1, -1, -1), device=None):
+# ---- surface following on blocks of the dense grid (csrc/sparsegrid.hpp, dsdf_sg_*) -------------------------------------
+def _check_sparse(block, lipschitz):
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)):
+        raise ValueError(f"block must be an integer number of cells, got {block!r}")
+    if block < 2:
+        raise ValueError(f"block must be at least 2 cells, got {block}")
+    try:
+        lip = float(lipschitz)
+    except (TypeError, ValueError):
+        raise ValueError(f"lipschitz must be a number, got {lipschitz!r}") from None
+    if not math.isfinite(lip) or lip < 0:
+        raise ValueError(f"lipschitz must be finite and >= 0, got {lipschitz!r}")
+    return int(block), lip
+
+
+def sparse_threshold(block, spacing, lipschitz):
+    """The seeding distance: lipschitz x half the diagonal of a full block, spacing[a] the grid spacing of axis a in the coordinates
+    the decoder sees; computed in double and rounded to fp32 once."""
+    return float(np.float32(float(lipschitz) * 0.5 * math.sqrt(sum((block * float(x)) ** 2 for x in _triple(spacing, "spacing")))))
+
+
+_SPARSE = [(None, 1.0)]
+
+
+@contextlib.contextmanager
+def sparse_grid(block, lipschitz=1.0):
+    """Inside this context create_mesh, create_mesh_microstructure and create_mesh_microstructure_diff (whose signatures are the
+    reference's) decode only the blocks of `block` cells per edge that the surface passes through (follow_surface).  lipschitz: a
+    bound on the field's slope in decoder coordinates; 1.0 is a distance field's, 0 seeds by corner signs alone (fast; a component
+    that flips no block corner is lost), a spline latent field adds slope of its own and is a reason to raise it; values that
+    saturate far from the surface only ever help.  block=None: the dense path.  Contexts nest; the outer setting returns on exit.
+    The setting is the process's, not a thread's."""
+    _SPARSE.append((None, 1.0) if block is None else _check_sparse(block, lipschitz))
+    try:
+        yield
+    finally:
+        _SPARSE.pop()
+
+
+def add_sparse_args(parser):
+    """--block B and --lipschitz X of the meshing command lines: the arguments of sparse_grid (no --block: the dense grid)."""
+    parser.add_argument("--block", type=int, default=None, metavar="B",
+                        help="decode only the blocks of B cells per edge that the surface passes through (default: the whole grid)")
+    parser.add_argument("--lipschitz", type=float, default=1.0, metavar="X",
+                        help="with --block: bound on the field's slope used to seed blocks; 0 seeds by corner signs alone (default 1.0)")
+
+
+def grid_coords_at(dims, voxel_size, origin, indices):
+    """xyz [n, 3] of the listed points (device int64 [n]) of a grid of dims points: fp32 index * voxel_size[a], then + origin[a],
+    each rounded on its own -- bit for bit grid_coords at those indices (dsdf_sg_coords)."""
+    dims = _int_triple(dims, "dims")
+    idx = indices.contiguous()
+    vs, org = (C.c_float * 3)(*_triple(voxel_size, "voxel_size")), (C.c_float * 3)(*_triple(origin, "origin"))
+    with torch.cuda.device(idx.device):
+        xyz = torch.empty(idx.numel(), 3, dtype=torch.float32, device=idx.device)
+        _lib.check(_lib.lib().dsdf_sg_coords(*dims, vs, org, _ptr(idx), idx.numel(), _ptr(xyz), _stream()))
+    return xyz
+
+
+def ms_caps_at(values, N, indices, cap_border_dict=None):
+    """Caps in place on values [n] (contiguous fp32 device tensor), the values of the listed points (device int64 [n]) of the padded
+    grid: bit for bit ms_apply_caps at those points (dsdf_sg_caps_at)."""
+    g, _ = _ms_grid(1, N)
+    recs, n = cap_records(cap_border_dict)
+    idx = indices.contiguous()
+    if values.dtype != torch.float32 or not values.is_contiguous() or values.numel() != idx.numel() or values.device.type != "cuda":
+        raise ValueError("ms_caps_at expects a contiguous fp32 device tensor with one value per index")
+    with torch.cuda.device(values.device):
+        _lib.check(_lib.lib().dsdf_sg_caps_at(C.byref(g), _ptr(idx), idx.numel(), recs, n, _ptr(values), _stream()))
+    return values
+
+
+def _padded_chunks(indices, max_batch, pad):
+    """(start, end, the chunk's indices) over a list of indices in chunks of max_batch; pad > 0: a short chunk is filled up to
+    min(max_batch, pad) rows with its last index, pad being the number of grid points -- the size of the dense path's full chunks,
+    so that every decode call picks their kernel family."""
+    n = indices.numel()
+    full = min(max_batch, pad)
+    for s in range(0, n, max_batch):
+        e = min(n, s + max_batch)
+        chunk = indices[s:e]
+        if e - s < full:
+            chunk = torch.cat([chunk, chunk[-1:].expand(full - (e - s))])
+        yield s, e, chunk
+
+
+def follow_surface(dims, block, thr, level, values_at, caps_at=None, *, device=None, on_step=None):
+    """Surface following on blocks of the dense grid of dims = (nx, ny, nz) points: the grid marching cubes needs, with
+    only the blocks the surface passes through decoded.
+
+    values_at(indices) -> values: the only thing that knows about decoders; indices is a device int64 tensor of distinct linear
+    grid indices (z fastest), ascending; values an fp32 device tensor of as many.  caps_at(indices, values) -> capped values (a new
+    tensor), for grids that are meshed after a cut: states are then decided on the capped values.
+
+    1. the coarse lattice (every block-th point per axis and the last) is decoded; 2. a block is seeded if its 8 corners are not
+    all inside (v < level) or all outside, or if min |v - level| over them is <= thr; 3. per round the points of the new blocks that
+    have no value yet are decoded; 4. an inactive block becomes active if a face-neighbour decoded in this round has mixed inside
+    flags on the shared face; 3 and 4 repeat until a round activates nothing (the host reads two counts per round: one stream
+    wait); 5. every point that never got a value takes the coarse value at the low corner of the lowest block that contains it.
+
+    Returns (grid, capped or None, stats): [nx, ny, nz] fp32 device tensors and stats = {blocks, seeds, active, rounds, points
+    (decoded), total (grid points)}.  The grid holds the field ONLY at decoded points: elsewhere a value of the right sign.  Its
+    marching-cubes mesh is the dense one minus the components that have no cell in a seeded block; none is lost when thr bounds the
+    change of the field over half a block diagonal.
+
+    on_step(name, workspace, plan, indices): called after every step has been put on the stream -- "start", "coarse" (indices: the
+    lattice), "coarse_decode", "seed", "wait" (the host has read the counts), then per round "emit" (indices: the round's points),
+    "decode", "grow", "wait", and last "fill".  workspace is the run's uint8 tensor and plan its DsdfSgPlan (state_offset and
+    have_offset locate the block states and the point map): what the tests compare with the oracle and the benchmarks time."""
+    dims = _int_triple(dims, "dims")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise _lib.DsdfError("follow_surface needs a HIP device (no CPU fallback)")
+    lib = _lib.lib()
+    plan = _lib.DsdfSgPlan()
+    _lib.check(lib.dsdf_sg_plan(*dims, int(block), C.byref(plan)))
+    npts = plan.n_points
+    level, thr = float(level), float(thr)
+    with torch.no_grad(), torch.cuda.device(device):
+        ws = torch.empty(plan.ws_bytes, dtype=torch.uint8, device=device)
+        counts = torch.zeros(2, dtype=torch.int64, device=device)
+        n_new, n_pts = C.c_void_p(counts.data_ptr()), C.c_void_p(counts.data_ptr() + 8)
+        grid = torch.empty(npts, dtype=torch.float32, device=device)
+        capped = torch.empty(npts, dtype=torch.float32, device=device) if caps_at is not None else None
+        seen = grid if capped is None else capped           # the grid that is meshed decides the states
+        at = (*dims, int(block))
+        wsa = (_ptr(ws), ws.numel(), _stream())
+
+        def step(name, indices=None):
+            if on_step is not None:
+                on_step(name, ws, plan, indices)
+
+        def decode_into(idx):
+            vals = values_at(idx).to(torch.float32).reshape(-1).contiguous()
+            if vals.numel() != idx.numel():
+                raise ValueError(f"values_at returned {vals.numel()} values for {idx.numel()} indices")
+            _lib.check(lib.dsdf_sg_scatter(_ptr(idx), idx.numel(), _ptr(vals), _ptr(grid), npts, _stream()))
+            if capped is not None:
+                cv = caps_at(idx, vals).to(torch.float32).reshape(-1).contiguous()
+                _lib.check(lib.dsdf_sg_scatter(_ptr(idx), idx.numel(), _ptr(cv), _ptr(capped), npts, _stream()))
+
+        step("start")
+        idx = torch.empty(plan.n_coarse, dtype=torch.int64, device=device)
+        _lib.check(lib.dsdf_sg_coarse(*at, _ptr(idx), *wsa))
+        step("coarse", idx)
+        decode_into(idx)
+        step("coarse_decode")
+        decoded = plan.n_coarse
+        _lib.check(lib.dsdf_sg_seed(_ptr(seen), *at, level, thr, n_new, *wsa))
+        _lib.check(lib.dsdf_sg_points_count(*at, n_pts, *wsa))
+        step("seed")
+        new, pts = counts.tolist()                          # the one stream wait of a round
+        step("wait")
+        seeds, active, rounds = new, 0, 0
+        while new > 0:
+            rounds += 1
+            active += new
+            idx = torch.empty(pts, dtype=torch.int64, device=device)
+            _lib.check(lib.dsdf_sg_points_emit(*at, pts, _ptr(idx), *wsa))
+            step("emit", idx)
+            if pts > 0:
+                decode_into(idx)
+                decoded += pts
+            step("decode")
+            _lib.check(lib.dsdf_sg_grow(_ptr(seen), *at, level, n_new, *wsa))
+            _lib.check(lib.dsdf_sg_points_count(*at, n_pts, *wsa))
+            step("grow")
+            new, pts = counts.tolist()
+            step("wait")
+        _lib.check(lib.dsdf_sg_fill(_ptr(grid), *at, *wsa))
+        if capped is not None:
+            _lib.check(lib.dsdf_sg_fill(_ptr(capped), *at, *wsa))
+        step("fill")
+    stats = dict(blocks=int(plan.n_blocks), seeds=seeds, active=active, rounds=rounds, points=decoded, total=int(npts))
+    return grid.view(*dims), None if capped is None else capped.view(*dims), stats
+
+
+def sdf_grid(decoder, latent, N, max_batch=32 ** 3, voxel_origin=(-1, -1, -1), device=None, *, block=None, lipschitz=1.0,
+             stats=None, on_step=None):
     """The decoder's SDF on the N^3 grid of create_mesh, as a device tensor [N, N, N] (axis 0 = x).
 
     This package's Decoder decodes through its Engine (decode_latent where the library takes the net, decode on [latent |
     xyz] otherwise: LayerNorm, xyz_in_all, latent_dropout), weights materialised once; any other nn.Module is called on the
-    chunk's [latent | xyz] -- only its decode leaves the library."""
+    chunk's [latent | xyz] -- only its decode leaves the library.
+
+    block: decode only the blocks of `block` cells per edge that the surface {sdf == 0} passes through (follow_surface; lipschitz as
+    in sparse_grid).  The result then holds the SDF only at decoded points -- elsewhere a value of the right sign -- and its mesh is
+    the dense grid's.  A short chunk of a HIP decoder is padded to the dense path's chunk size, min(max_batch, N^3).
+    stats: a dict that receives follow_surface's record; on_step: follow_surface's callback."""
     dec = _unwrap(decoder)
     hip = _is_hip_decoder(dec)
     if hip:
@@ -167,6 +358,34 @@ def sdf_grid(decoder, latent, N, max_batch=32 ** 3, voxel_origin=(-1, -1, -1), d
     if device.type != "cuda":
         raise _lib.DsdfError("sdf_grid needs a HIP device (no CPU fallback)")
     n = N ** 3
+    if block is not None:
+        block, lipschitz = _check_sparse(block, lipschitz)
+        voxel_size = 2.0 / (N - 1)
+        with torch.no_grad():
+            z = latent.detach().to(device, torch.float32).reshape(1, -1)
+            if hip:
+                eng = dec.engine()
+                eng.materialize()
+                single = eng.decode_latent_supported()
+
+            def values_at(indices):
+                vals = torch.empty(indices.numel(), dtype=torch.float32, device=device)
+                for s, e, chunk in _padded_chunks(indices, max_batch, n if hip else 0):
+                    xyz = grid_coords_at(N, voxel_size, voxel_origin, chunk)
+                    if hip and single:
+                        y = eng.decode_latent(z, xyz)
+                    elif hip:
+                        y = eng.decode(torch.cat([z.expand(chunk.numel(), -1), xyz], 1))
+                    else:
+                        y = dec(torch.cat([z.expand(chunk.numel(), -1), xyz], 1))
+                    vals[s:e] = y.reshape(-1)[:e - s]
+                return vals
+
+            grid, _, st = follow_surface(N, block, sparse_threshold(block, voxel_size, lipschitz), 0.0, values_at, device=device,
+                                         on_step=on_step)
+        if stats is not None:
+            stats.update(st)
+        return grid
     out = torch.empty(n, dtype=torch.float32, device=device)
     with torch.no_grad():
         z = latent.detach().to(device, torch.float32).reshape(1, -1)
@@ -195,7 +414,8 @@ def create_mesh(decoder, latent_vec, filename, N=256, max_batch=32 ** 3, offset=
     decoder.eval()
     voxel_origin = [-1, -1, -1]
     voxel_size = 2.0 / (N - 1)
-    grid = sdf_grid(decoder, latent_vec, N, max_batch, voxel_origin, device)
+    block, lipschitz = _SPARSE[-1]                         # sparse_grid(): the signature is the reference's
+    grid = sdf_grid(decoder, latent_vec, N, max_batch, voxel_origin, device, block=block, lipschitz=lipschitz)
     logger.debug("sampling takes: %f", time.time() - start)
     convert_sdf_samples_to_ply(grid, voxel_origin, voxel_size, filename, offset, scale)
 
@@ -342,12 +562,68 @@ def ms_apply_caps(sdf, N, start, end, cap_border_dict=None):
     return sdf
 
 
-def microstructure_sdf_grid(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None, apply_caps=True):
+def _ms_sparse_grids(tiling, decoder, field, N, max_batch, cap_border_dict, device, apply_caps, block, lipschitz, stats=None,
+                     on_step=None):
+    """(raw, capped or None) of microstructure_sdf_grid by surface following: rows at listed points by dsdf_ms_rows_at, caps at
+    listed points by dsdf_sg_caps_at.  The decoder sees folded coordinates, which the fold scales by the tiling: the seeding
+    distance uses voxel_size[a] * tiling[a]."""
+    from .spline import as_field
+    field = as_field(field)
+    block, lipschitz = _check_sparse(block, lipschitz)
+    dec = _unwrap(decoder)
+    hip = _is_hip_decoder(dec)
+    if hip:
+        device = dec._arena.device
+    elif device is None:
+        device = torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DsdfError("microstructure_sdf_grid needs a HIP device (no CPU fallback)")
+    t, n = _int_triple(tiling, "Tiling"), _int_triple(N, "Number of grid points")
+    g, voxel_size = _ms_grid(t, n)
+    npts = g.dims[0] * g.dims[1] * g.dims[2]
+    cap_records(cap_border_dict)                            # validates before anything runs
+    max_batch = int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"max_batch must be positive, got {max_batch}")
+    if hip:
+        eng = dec.engine()
+        eng.materialize()
+
+    def values_at(indices):
+        vals = torch.empty(indices.numel(), dtype=torch.float32, device=device)
+        for s, e, chunk in _padded_chunks(indices, max_batch, npts if hip else 0):
+            rows, _, _ = ms_rows_at(field, t, n, chunk)
+            y = eng.decode(rows) if hip else dec(rows)
+            vals[s:e] = y.reshape(-1)[:e - s]
+        return vals
+
+    def caps_at(indices, values):
+        return ms_caps_at(values.clone(), n, indices, cap_border_dict)
+
+    thr = sparse_threshold(block, [voxel_size[a] * t[a] for a in range(3)], lipschitz)
+    raw, capped, st = follow_surface(list(g.dims), block, thr, 0.0, values_at, caps_at if apply_caps else None, device=device,
+                                     on_step=on_step)
+    if stats is not None:
+        stats.update(st)
+    return raw, capped
+
+
+def microstructure_sdf_grid(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None, apply_caps=True, *,
+                            block=None, lipschitz=1.0, stats=None, on_step=None):
     """The capped SDF of a microstructure on the padded grid, a device tensor [Nx + 2, Ny + 2, Nz + 2] (axis 0 = x).
 
     The design domain [-1, 1]^3 is tiled with tiling[a] mirrored copies of the unit cell per axis; `field` (a BSplineField, or a
     splinepy BSpline) gives every point its latent code.  This package's Decoder decodes through its Engine, weights
-    materialised once; any other nn.Module is called on the rows.  The result does not depend on max_batch."""
+    materialised once; any other nn.Module is called on the rows.  The result does not depend on max_batch.
+
+    block: decode only the blocks the surface passes through (follow_surface; block and lipschitz as in sparse_grid).  The result
+    then holds the SDF only at decoded points -- elsewhere a value of the right sign -- and its mesh is the dense grid's.  stats,
+    on_step: as sdf_grid's."""
+    if block is not None:
+        raw, capped = _ms_sparse_grids(tiling, decoder, field, N, max_batch, cap_border_dict, device, apply_caps, block, lipschitz,
+                                       stats, on_step)
+        return capped if apply_caps else raw
     from .spline import as_field
     field = as_field(field)
     dec = _unwrap(decoder)
@@ -402,7 +678,9 @@ def create_mesh_microstructure(tiling, decoder, latent_vec_interpolation, filena
     decoder.eval()
     _, voxel_size = _ms_grid(tiling, n)
     voxel_origin = [-1 - v for v in voxel_size]
-    grid = microstructure_sdf_grid(tiling, decoder, latent_vec_interpolation, n, max_batch, cap_border_dict, device)
+    block, lipschitz = _SPARSE[-1]                         # sparse_grid(): the signature is the reference's
+    grid = microstructure_sdf_grid(tiling, decoder, latent_vec_interpolation, n, max_batch, cap_border_dict, device, block=block,
+                                   lipschitz=lipschitz)
     logger.debug("sampling takes: %f", time.time() - start)
     if save_ply_file:
         convert_sdf_samples_to_ply(grid, voxel_origin, voxel_size, filename + ".ply", offset, scale)
@@ -519,13 +797,18 @@ class MicrostructureMeshDiff:
         return out
 
 
-def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None):
+def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None, *, block=None,
+                             lipschitz=1.0):
     """The mesh create_mesh_microstructure returns, on the device, with what its derivative needs (MicrostructureMeshDiff).
 
     Forward: the raw grid, its capped copy and marching cubes, as create_mesh_microstructure.  Band: the sorted unique grid points
     {p, p + e_a} of the vertices' edges.  Per chunk of max_batch band points: rows at the band indices (dsdf_ms_rows_at), the
     decoder's forward and its input gradient with d_sdf = 1 (Engine.module_input_grad; torch.autograd.grad for any other
-    nn.Module).  mask = inside and capped value == raw value."""
+    nn.Module).  mask = inside and capped value == raw value.
+
+    block: the raw and the capped grid come from one surface-following run (follow_surface; block and lipschitz as in sparse_grid).
+    Band points are endpoints of vertex edges and so lie in decoded blocks: mask and Jacobian mean what they mean on the dense grid;
+    `grid` holds the SDF only at decoded points."""
     from .spline import as_field
     field = as_field(field)
     tiling, n = _int_triple(tiling, "Tiling"), _int_triple(N, "Number of grid points")
@@ -534,14 +817,19 @@ def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_b
     decoder.eval()
     _, voxel_size = _ms_grid(tiling, n)
     max_batch = int(max_batch)
-    raw = microstructure_sdf_grid(tiling, decoder, field, n, max_batch, cap_border_dict, device, apply_caps=False)
+    if block is None:
+        raw = microstructure_sdf_grid(tiling, decoder, field, n, max_batch, cap_border_dict, device, apply_caps=False)
+        grid = None
+    else:
+        raw, grid = _ms_sparse_grids(tiling, decoder, field, n, max_batch, cap_border_dict, device, True, block, lipschitz)
     device = raw.device
     dims = list(raw.shape)
     npts = raw.numel()
     L = int(field.latent_size)
     with torch.cuda.device(device):
-        grid = raw.clone()
-        ms_apply_caps(grid.view(-1), n, 0, npts, cap_border_dict)
+        if grid is None:
+            grid = raw.clone()
+            ms_apply_caps(grid.view(-1), n, 0, npts, cap_border_dict)
         verts, faces, edge_point, edge_axis = marching_cubes(grid, 0.0, voxel_size, return_edges=True)
         vs = torch.tensor(voxel_size, dtype=torch.float64, device=device)
         verts = (verts.double() - vs) / 2
@@ -588,5 +876,7 @@ def create_mesh_microstructure_diff(tiling, decoder, latent_vec_interpolation, N
         verts, faces = create_mesh_microstructure(tiling, decoder, latent_vec_interpolation, "unused", N=N, max_batch=max_batch,
                                                   cap_border_dict=cap_border_dict, device=device)
         return verts, faces, []
-    d = microstructure_mesh_diff(tiling, decoder, latent_vec_interpolation, N, max_batch, cap_border_dict, device)
+    block, lipschitz = _SPARSE[-1]                         # sparse_grid(): the signature is the reference's
+    d = microstructure_mesh_diff(tiling, decoder, latent_vec_interpolation, N, max_batch, cap_border_dict, device, block=block,
+                                 lipschitz=lipschitz)
     return d.verts.cpu().numpy(), d.faces.cpu().numpy(), d.jacobian(dense=True).cpu().numpy()

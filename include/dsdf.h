@@ -588,6 +588,59 @@ int dsdf_mt_volume(const float* verts, int64_t n_verts, const int32_t* faces, in
 int dsdf_mt_project(const float* jac, const int32_t* axis, const float* normals, int64_t n_verts, int64_t R,
                     const float* stretch /*[host]*/, float clip, float* out, void* stream);
 
+/* ---- surface following on blocks of the dense grid (csrc/sparsegrid.hpp): the reference builds the coordinates of ALL N^3 grid
+ * points and decodes every one of them (deep_sdf/mesh.py:42-70 for create_mesh, :262-271 for the microstructure grid); these
+ * entries find the points a mesh needs, so that only those are decoded.  Nothing here evaluates an SDF: the caller decodes the
+ * listed points with the entries above and hands the values back.  Additions only: DSDF_ABI_VERSION is unchanged.
+ *
+ * Grid [nx][ny][nz] fp32, z fastest, 2 .. 1024 points per axis; block edge `block` >= 2 cells.  Coarse coordinates of axis a:
+ * {0, block, 2 block, ... < n_a - 1} + {n_a - 1}; block (I, J, K), linear (I * nb_y + J) * nb_z + K, owns the closed point box between
+ * consecutive coarse coordinates (the last block of an axis may be short; neighbours share their face points).  Inside: v < level.
+ * One workspace (dsdf_sg_plan, 256-byte aligned, planner conventions: dsdf_debug_ws_redzone / _regions) carries the state of one
+ * surface-following run between the calls: a state byte per block (0 inactive, 1 new, 2 valued) and a byte per grid point
+ * (1: the point holds a decoded value).  The order of a run:
+ *   dsdf_sg_plan          [host] block counts, coarse-lattice size, workspace bytes, and where in it the states and the point map lie
+ *   dsdf_sg_coarse        indices [n_coarse] int64: the coarse lattice's linear indices, ascending; clears the point map and marks them
+ *   (decode, dsdf_sg_scatter)
+ *   dsdf_sg_seed          state = 1 for a block whose 8 corners are not all inside or all outside, or whose
+ *                         min over corners of fabsf(v - level) <= thr (fp32); 0 otherwise.  *n_new (device int64): blocks in state 1
+ *   per round, while *n_new > 0 (the caller reads the two counts on the host: one stream wait per round):
+ *     dsdf_sg_points_count  *n_points (device int64): grid points without a value inside blocks of state 1
+ *     dsdf_sg_points_emit   indices [n] int64, n = that count: those points, ascending; marks them.  Nothing is written past n.
+ *     (decode, dsdf_sg_scatter)
+ *     dsdf_sg_grow          gather form: an inactive block becomes 1 if a face-neighbour in state 1 has mixed inside flags among
+ *                           the points of the shared face; the blocks that were 1 become 2.  *n_new: blocks newly in state 1
+ *   dsdf_sg_fill          every point without a value takes the value at the low corner of the lowest-index block that contains it
+ * and, independent of a run:
+ *   dsdf_sg_coords        xyz [n][3] of listed points: fp32 index * voxel_size[a], then + origin[a], each rounded on its own
+ *                         (voxel_size, origin: [host] 3 floats); nx .. nz >= 1
+ *   dsdf_sg_scatter       sdf[indices[q]] = values[q]; an index outside [0, n_points) writes nothing.  Indices must be distinct.
+ *   dsdf_sg_caps_at       dsdf_ms_caps' arithmetic, bit for bit, in place on sdf [n], the values of the listed points of the padded grid
+ * One thread per block or per point, integer work and plain stores; no atomics: counts are per-workgroup totals summed in a
+ * fixed order, so two identical runs give identical bytes.  Every argument error returns DSDF_E_INVALID before anything is launched. */
+typedef struct DsdfSgPlan {
+  int32_t blocks[3];
+  int64_t n_blocks, n_coarse, n_points;
+  size_t ws_bytes;
+  size_t state_offset, have_offset; /* where the workspace holds the block states [n_blocks] and the point map [n_points], one byte each */
+} DsdfSgPlan;
+
+int dsdf_sg_plan(int32_t nx, int32_t ny, int32_t nz, int32_t block, DsdfSgPlan* plan);                  /* [host] */
+int dsdf_sg_coarse(int32_t nx, int32_t ny, int32_t nz, int32_t block, int64_t* indices, void* ws, size_t ws_bytes, void* stream);
+int dsdf_sg_seed(const float* sdf, int32_t nx, int32_t ny, int32_t nz, int32_t block, float level, float thr, int64_t* n_new, void* ws,
+                 size_t ws_bytes, void* stream);
+int dsdf_sg_grow(const float* sdf, int32_t nx, int32_t ny, int32_t nz, int32_t block, float level, int64_t* n_new, void* ws,
+                 size_t ws_bytes, void* stream);
+int dsdf_sg_points_count(int32_t nx, int32_t ny, int32_t nz, int32_t block, int64_t* n_points, void* ws, size_t ws_bytes, void* stream);
+int dsdf_sg_points_emit(int32_t nx, int32_t ny, int32_t nz, int32_t block, int64_t n, int64_t* indices, void* ws, size_t ws_bytes,
+                        void* stream);
+int dsdf_sg_fill(float* sdf, int32_t nx, int32_t ny, int32_t nz, int32_t block, void* ws, size_t ws_bytes, void* stream);
+int dsdf_sg_coords(int32_t nx, int32_t ny, int32_t nz, const float* voxel_size /*[host]*/, const float* origin /*[host]*/,
+                   const int64_t* indices, int64_t n, float* xyz, void* stream);
+int dsdf_sg_scatter(const int64_t* indices, int64_t n, const float* values, float* sdf, int64_t n_points, void* stream);
+int dsdf_sg_caps_at(const DsdfMsGrid* grid, const int64_t* indices, int64_t n, const DsdfMsCap* caps, int32_t n_caps, float* sdf,
+                    void* stream);
+
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */
 int dsdf_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,

@@ -24,7 +24,8 @@ import deep_sdf.workspace as ws
 from deepsdf_amd.data import DeviceSampleCache, get_instance_filenames
 from deepsdf_amd.reconstruct import reconstruct
 
-if __name__ == "__main__":
+
+def build_parser():
     ap = argparse.ArgumentParser(description="Use a trained DeepSDF decoder to reconstruct shapes given SDF samples.")
     ap.add_argument("--experiment", "-e", dest="experiment_directory", required=True)
     ap.add_argument("--checkpoint", "-c", dest="checkpoint", default="latest")
@@ -36,8 +37,13 @@ if __name__ == "__main__":
     ap.add_argument("--skip", dest="skip", action="store_true", help="skip shapes whose code file already exists")
     ap.add_argument("--mesh", dest="mesh_resolution", nargs="?", const=256, default=None, type=int,
                     help="also write a PLY mesh of every reconstructed code on an N^3 grid (N default 256)")
+    deep_sdf.mesh.add_sparse_args(ap)
     deep_sdf.add_common_args(ap)
-    args = ap.parse_args()
+    return ap
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
     deep_sdf.configure_logging(args)
     if not torch.cuda.is_available():
         raise RuntimeError("reconstruct.py (deepsdf_amd) needs an AMD GPU: the HIP path has no CPU fallback")
@@ -78,4 +84,5 @@ if __name__ == "__main__":
                 ds, cls, inst = f[:-4].split(os.sep)
                 mesh_out = ws.get_reconstructed_mesh_filename(args.experiment_directory, saved_epoch, ds, cls, inst)
                 os.makedirs(os.path.dirname(mesh_out), exist_ok=True)
-                deep_sdf.mesh.create_mesh(decoder, code.view(-1), mesh_out, N=args.mesh_resolution)
+                with deep_sdf.mesh.sparse_grid(args.block, args.lipschitz):
+                    deep_sdf.mesh.create_mesh(decoder, code.view(-1), mesh_out, N=args.mesh_resolution)

@@ -3,6 +3,7 @@ against the same rows composed from torch ops.  One JSON line per (net, L) and o
 
     python tools/ms_bench.py [--nets 8x512 4x64] [--L 16 256] [--N 256] [--tiling 4 4 4] [--max-batch 32768] [--reps 5]
     python tools/ms_bench.py --diff [--nets 8x512 4x64] [--L 16] [--diff-N 64 256]
+    python tools/ms_bench.py --block 4 [--lipschitz 1 0] [--nets 8x512 4x64] [--L 16]
 
 mesh lines   rows_ms / decode_ms / caps_ms: HIP events around each step of every chunk, summed over the grid (the loop of
              microstructure_sdf_grid restated with events between the steps); mc_ms: events around marching_cubes; total_ms: host
@@ -20,6 +21,12 @@ row lines    dsdf_ms_rows on one range of --row-points grid points, 20 launches 
              (deep_sdf/mesh.py:405-422 runs that many double-backward passes, over the whole grid).  HIP events, median of --reps
              after one warm-up, with min and max.  --diff-N gives the grid sizes.
 
+--block B    dense against sparse (microstructure_sdf_grid(block=B): surface following on blocks) in one process, one
+             line per (net, L, lipschitz): a warm-up of both, then --reps alternating pairs; device events around grid + marching
+             cubes; medians; the sparse path's steps from follow_surface's own events (coarse decode, the rounds' decode -- rows,
+             decode and caps at listed points, one figure per round --, index kernels, fill), both marching cubes, its count reads, the
+             fraction decoded and the rounds.
+
 Nets: seeded (nn.Linear init) decoders of bench.py's NetworkSpecs with CodeLength L; the output bias is shifted so that the zero
 level set crosses the structure.  A (net, L) pair for which no net exists (4x64 with L = 256) is reported as skipped.  The field: degree 1, 2 x 2 x 2 seeded codes.
 """
@@ -32,6 +39,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(1, os.path.dirname(os.path.abspath(__file__)))          # mesh_bench's timers (--block)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -202,6 +210,39 @@ def diff_bench(args, dev):
                 del d
 
 
+def sparse_bench(args, dev):
+    from mesh_bench import StepTimer, events_ms, sparse_summary
+    N, tiling = args.N, args.tiling
+    h = 2.0 / (N - 1)
+    mc = lambda g: marching_cubes(g, 0.0, (h, h, h))                                   # noqa: E731
+    for L in args.L:
+        field = make_field(L)
+        for name in args.nets:
+            spec = bench.NETWORKS[name]["net"]
+            if any(spec["dims"][l - 1] <= L + 3 for l in spec["latent_in"]):
+                print(json.dumps(dict(what="sparse", net=name, L=L, skipped=f"no {name} net exists for L = {L}")), flush=True)
+                continue
+            dec = make_decoder(name, L, field, tiling)
+
+            def pair(lip):
+                d_ms, grid = events_ms(lambda: microstructure_sdf_grid(tiling, dec, field, N, args.max_batch))
+                mc_ms, (vd, fd) = events_ms(lambda: mc(grid))
+                del grid
+                stats, timer = {}, StepTimer()
+                s_ms, grid = events_ms(lambda: microstructure_sdf_grid(tiling, dec, field, N, args.max_batch, block=args.block, lipschitz=lip,
+                                                                       stats=stats, on_step=timer))
+                mc2_ms, (vs, fs) = events_ms(lambda: mc(grid))
+                same = vd.shape == vs.shape and fd.shape == fs.shape and bool(torch.equal(vd, vs)) and bool(torch.equal(fd, fs))
+                return dict(dense=d_ms + mc_ms, mc=mc_ms, sparse=s_ms + mc2_ms, mc_sparse=mc2_ms, steps=timer.steps(), waits=timer.waits(),
+                            stats=stats, same=same, F=(fd.shape[0], fs.shape[0]))
+
+            for lip in args.lipschitz:
+                pair(lip)
+                runs = [pair(lip) for _ in range(args.reps)]
+                print(json.dumps(dict(what="sparse", net=name, L=L, N=N, tiling=tiling, block=args.block, lipschitz=lip, max_batch=args.max_batch,
+                                      reps=args.reps, **sparse_summary(runs), device=dev)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nets", nargs="+", default=["8x512", "4x64"], choices=sorted(bench.NETWORKS))
@@ -213,12 +254,16 @@ def main():
     ap.add_argument("--row-points", type=int, default=1 << 21, help="points of the row-kernel measurement")
     ap.add_argument("--diff", action="store_true", help="time the derivative with respect to the control points instead")
     ap.add_argument("--diff-N", nargs="+", type=int, default=[64, 256], help="grid sizes of --diff")
+    ap.add_argument("--block", type=int, default=None, help="compare the dense path with surface following on blocks of this edge")
+    ap.add_argument("--lipschitz", nargs="+", type=float, default=[1.0, 0.0], help="with --block: the seeding slopes to run")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ms_bench.py needs an AMD GPU: nothing here can be timed on a CPU")
     dev = torch.cuda.get_device_name(0)
     if args.diff:
         return diff_bench(args, dev)
+    if args.block:
+        return sparse_bench(args, dev)
     N, tiling = args.N, args.tiling
     for L in args.L:
         field = make_field(L)
