@@ -133,8 +133,13 @@ def disassemble_with_addresses(co, name_part):
         raise AsmHazard(f"expected exactly one function matching {name_part!r} in the code object, found {names}")
     out = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", f"--disassemble-symbols={names[0]}", co],
                          capture_output=True, text=True, check=True).stdout
+    return parse_listing(out)
+
+
+def parse_listing(text):
+    """llvm-objdump -d text of ONE function -> [dict(op, args, addr, target)] (target: the address a branch names, else None)."""
     base, ins = None, []
-    for line in out.splitlines():
+    for line in text.splitlines():
         m = re.match(r"^([0-9a-f]+) <", line)
         if m and base is None:
             base = int(m.group(1), 16)
@@ -220,3 +225,51 @@ def check_mfma_src_reuse(lib, kernel="fused_forward_bf16x8_kernel", min_distance
         raise AsmHazard(f"{kernel}: {len(bad)} load(s) overwrite MFMA source registers after fewer than {min_distance} other MFMAs: "
                         + "; ".join(bad[:4]))
     return worst, len(dist)
+
+
+# ---- third audit: the register ring of dw_item<4> must keep rolling (dwstream.hpp, dw_stream_kernel) ------------------------------
+# The fp32 dW loop prefetches DW_RING k-steps of 2 loads each into a ring of registers.  For four rounds its code object held ONE
+# wait per revolution, ``s_waitcnt vmcnt(0)`` at the loop header: every load sat under a scalar branch, the compiler could not
+# count outstanding loads across the back edge, and the wave drained the whole ring and sat through a memory round trip every
+# DW_RING steps.  Nothing fails when that happens -- the results are the same -- so it is a property held on the code object:
+# inside the steady-state loop of the full-width item every wait that names vmcnt leaves >= 2 (DW_RING - 2) loads in flight.
+def innermost_loops(ins):
+    """[(first, last)] instruction index ranges of the loops that contain no other loop: a backward branch and its target."""
+    by_addr = {x["addr"]: i for i, x in enumerate(ins)}
+    spans = sorted({(by_addr[x["target"]], i) for i, x in enumerate(ins)
+                    if x["op"].startswith(("s_branch", "s_cbranch")) and x["target"] in by_addr and x["target"] <= x["addr"]})
+    return [(a, b) for a, b in spans if not any((c, d) != (a, b) and a <= c and d <= b for c, d in spans)]
+
+
+def dw_ring_waits(ins, ring):
+    """The vmcnt values of every s_waitcnt inside the steady-state loop of dw_item<4>: THE innermost loop with 16 * ring MFMAs and
+    2 * ring buffer loads (one revolution of the ring).  Raises AsmHazard if there is no such loop, or more than one."""
+    found = []
+    for a, b in innermost_loops(ins):
+        body = ins[a:b + 1]
+        if (sum(x["op"].startswith("v_mfma") for x in body) == 16 * ring
+                and sum(x["op"].startswith("buffer_load") for x in body) == 2 * ring):
+            found.append([int(m.group(1)) for x in body if x["op"] == "s_waitcnt" for m in re.finditer(r"vmcnt\((\d+)\)", x["args"])])
+    if len(found) != 1:
+        raise AsmHazard(f"dw ring: expected exactly one innermost loop of {16 * ring} MFMAs and {2 * ring} buffer loads "
+                        f"(one revolution of a ring of {ring}), found {len(found)}; the check would be vacuous")
+    return found[0]
+
+
+def check_dw_ring_waits_ins(ins, ring):
+    waits = dw_ring_waits(ins, ring)
+    need = 2 * (ring - 2)
+    if 0 in waits:
+        raise AsmHazard(f"dw ring: s_waitcnt vmcnt(0) inside the steady-state loop (waits: {waits}): the ring is drained every revolution")
+    if not waits or min(waits) < need:
+        raise AsmHazard(f"dw ring: the steady-state loop's waits {waits} must all leave >= {need} loads in flight "
+                        f"(2 * (DW_RING - 2), DW_RING = {ring})")
+    return waits
+
+
+def check_dw_ring_waits(lib, ring=16, kernel="dw_stream_kernel"):
+    """Raises AsmHazard unless every vmcnt wait in the steady-state loop of `kernel` allows >= 2 (ring - 2) outstanding loads
+    (and none is vmcnt(0)); returns the loop's wait counts in program order."""
+    with tempfile.TemporaryDirectory(prefix="dsdf_asmcheck_") as d:
+        ins = disassemble_with_addresses(extract_code_object(lib, d), kernel)
+    return check_dw_ring_waits_ins(ins, ring)

@@ -38,14 +38,17 @@ def build_library(force=False, verbose=False):
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)
-    # the one inline-asm window that keeps loads in flight across compiler-scheduled code is verified on the code object of
-    # EVERY build, lab flags included (asmcheck.py); a library that violates it -- or that could not be checked -- is removed,
-    # not shipped: left on disk it would pass is_stale() next time and be loaded unverified
+    # the one inline-asm window that keeps loads in flight across compiler-scheduled code, and two properties of compiler-scheduled
+    # loops that no result can show, are verified on the code object of EVERY build, lab flags included (asmcheck.py); a library that
+    # violates one -- or that could not be checked -- is removed, not shipped: left on disk it would pass is_stale() next time and be
+    # loaded unverified
     from . import asmcheck
     if asmcheck.tools_available():
         try:
             asmcheck.check_library(LIB, expect_windows="-DDW_SPLIT_ONE_WAIT=1" not in cmd)
             asmcheck.check_mfma_src_reuse(LIB, min_distance=2)      # fused_bf16x8.hpp: a step is >= 2 MFMAs (one n-tile per wave)
+            ring = [int(f.split("=", 1)[1]) for f in cmd if f.startswith("-DDW_RING_STEPS=")]
+            asmcheck.check_dw_ring_waits(LIB, ring=ring[-1] if ring else 16)   # dwstream.hpp: the fp32 dW ring never drains in its loop
         except BaseException:      # AsmHazard, a failing llvm tool (CalledProcessError), an interrupt: no unverified library stays
             if os.path.exists(LIB):
                 os.remove(LIB)

@@ -6,7 +6,8 @@
 // vector feeds MFMA row-tile i (rows m0 + 4r + i), element j of B feeds column-tile j: 2 loads -> 16 MFMAs.  A wave
 // owns a whole 128x128 output tile (4x4 accumulators = 256 AGPRs) over its own range of points; ONE wave per SIMD,
 // a ring of 16 prefetched k-steps hides the memory latency; the streamed loads go through buffer resources with SCALAR
-// k-step offsets and the wave index is made scalar, so no vector address arithmetic sits between the MFMAs (413 -> 388 us).
+// k-step offsets and the wave index is made scalar, so no vector address arithmetic sits between the MFMAs (413 -> 388 us),
+// and every load is unconditional so that the loop's waits are counted and the ring never drains (388 -> 368 us).
 // Work items (layer, K-split, tile) are laid out so that the tiles of one split run on one XCD and share the streamed
 // rows through its L2.  Output: split-K slabs, summed in fixed order by finalize_row (deterministic).  The workgroups the
 // items leave idle run the post-backward roles of kernels.hpp meanwhile.
@@ -37,9 +38,11 @@ struct DwArgs { int n_layers, n_full, n_narrow, N; DwLayer ly[DSDF_MAX_LAYERS];
 #define DW_RING_STEPS 16
 #endif
 constexpr int DW_RING = DW_RING_STEPS;
-#ifndef DW_BRANCHLESS
-#define DW_BRANCHLESS 0      // measured: no difference (388 us both ways); the per-step overhead is not the branch
-#endif
+// Every load of the ring is UNCONDITIONAL (step indices are clamped, never branched on): a load under a scalar branch makes the
+// compiler's wait-count pass give up counting across the loop's back edge and put s_waitcnt vmcnt(0) at the loop header -- the
+// whole ring drained once per revolution, one exposed memory round trip per DW_RING k-steps.  (An earlier switch made only the
+// steady state branch-free, measured "no difference" and blamed the per-step overhead elsewhere: the prologue's loads were
+// still conditional, so the header kept its vmcnt(0).)  deepsdf_amd/asmcheck.py check_dw_ring_waits holds every build to it.
 
 template <int NJ> struct DwVec;
 template <> struct DwVec<1> { typedef float type; };
@@ -49,16 +52,19 @@ template <> struct DwVec<4> { typedef float4 type; };
 
 // one work item: a 128 x (32 NJ) tile over points [kbeg, kend)
 template <int NJ>
-__device__ __forceinline__ void dw_item(const DwLayer& L, int split, int m0, int n0, int kbeg, int kend, int fr, int fh) {
+__device__ __forceinline__ void dw_item(const DwLayer& L, int N, int split, int m0, int n0, int kbeg, int kend, int fr, int fh) {
   typedef typename DwVec<NJ>::type bvec;
   const int nsteps = (kend - kbeg) >> 1;                    // full k-steps of 2 points
   const float* bq = L.act + (size_t)(kbeg + fh) * L.ld_act + n0 + NJ * fr;   // narrow tiles (NJ < 4): plain loads
   const size_t bstep = (size_t)2 * L.ld_act;
   // the streamed loads go through buffer resources based at the item's first row: the address of k-step q is a SCALAR
-  // offset (q * step bytes, < 2^31) plus a per-lane constant -- no vector address arithmetic between the MFMAs
+  // offset (q * step bytes, < 2^31) plus a per-lane constant -- no vector address arithmetic between the MFMAs.  A resource ends
+  // where its operand array ends (N rows): a request past the batch's last point reads zeros, not foreign memory
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(L.dp + (size_t)kbeg * L.ld_dp), 0, 0x7FFFFFFF, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(L.act + (size_t)kbeg * L.ld_act), 0, 0x7FFFFFFF, 0x00020000);
+  const size_t rows_left = (size_t)(N - kbeg);
+  const int ra_bytes = (int)min(rows_left * L.ld_dp * 4, (size_t)0x7FFFFFFF), rb_bytes = (int)min(rows_left * L.ld_act * 4, (size_t)0x7FFFFFFF);
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(L.dp + (size_t)kbeg * L.ld_dp), 0, ra_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(L.act + (size_t)kbeg * L.ld_act), 0, rb_bytes, 0x00020000);
   const int voa = (fh * L.ld_dp + m0 + 4 * fr) * 4, vob = (fh * L.ld_act + n0 + NJ * fr) * 4;
   const int astepb = 8 * L.ld_dp, bstepb = 8 * L.ld_act;
   auto lda = [&](int q) -> float4 {
@@ -96,36 +102,36 @@ __device__ __forceinline__ void dw_item(const DwLayer& L, int split, int m0, int
 #pragma unroll
       for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
   };
-  // prologue: fill the ring (steps beyond nsteps are simply not loaded)
+  // An item without a full k-step (0 or 1 points) skips the ring: there is no step to clamp to.  Otherwise steps past the end
+  // re-request the LAST step (in bounds, never used): a scalar min instead of a compare + branch in front of a load
+  if (nsteps > 0) {
+    const int last = nsteps - 1;
 #pragma unroll
-  for (int q = 0; q < DW_RING - 1; ++q) {
-    if (q < nsteps) {
-      rga[q] = lda(q);
-      rgb[q] = ldbq(q);
+    for (int q = 0; q < DW_RING - 1; ++q) {                    // prologue: fill the ring
+      rga[q] = lda(min(q, last));
+      rgb[q] = ldbq(min(q, last));
     }
-  }
-  int s = 0;
-  for (; s + DW_RING <= nsteps; s += DW_RING) {   // steady state: static ring slots, one new step in flight per MMA group
+    int s = 0;
+    for (; s + DW_RING <= nsteps; s += DW_RING) {   // steady state: static ring slots, one new step in flight per MMA group
 #pragma unroll
-    for (int q = 0; q < DW_RING; ++q) {
-#if DW_BRANCHLESS
-      const int nxt = min(s + q + DW_RING - 1, nsteps - 1);   // past the end: re-request the last step (in bounds, never used) --
-      rga[(q + DW_RING - 1) % DW_RING] = lda(nxt);            // a scalar min instead of a compare + branch per k-step
-      rgb[(q + DW_RING - 1) % DW_RING] = ldbq(nxt);
-#else
-      const int nxt = s + q + DW_RING - 1;
-      if (nxt < nsteps) {
-        rga[(q + DW_RING - 1) % DW_RING] = lda(nxt);
+      for (int q = 0; q < DW_RING; ++q) {
+        const int nxt = min(s + q + DW_RING - 1, last);
+        rga[(q + DW_RING - 1) % DW_RING] = lda(nxt);             // into the slot the PREVIOUS group's MFMAs read
         rgb[(q + DW_RING - 1) % DW_RING] = ldbq(nxt);
+        mma(rga[q], rgb[q]);
+        if constexpr (NJ == 4) {     // pin the interleave (fused.hpp fused_kloop): left alone the compiler bunches a revolution's loads
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+          __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);   // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+        }
       }
-#endif
-      mma(rga[q], rgb[q]);
     }
-  }
-  // tail: the remaining (< DW_RING) full steps are already in ring slots 0..rem-1
+    // tail: the remaining (< DW_RING) full steps are already in ring slots 0..rem-1
 #pragma unroll
-  for (int q = 0; q < DW_RING - 1; ++q)
-    if (s + q < nsteps) mma(rga[q], rgb[q]);
+    for (int q = 0; q < DW_RING - 1; ++q)
+      if (s + q < nsteps) mma(rga[q], rgb[q]);
+  }
   if ((kend - kbeg) & 1) {                                   // odd last point: lanes of the second half contribute zero
     const int k = kend - 1;
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -589,7 +595,7 @@ __device__ __forceinline__ void dw_stream_body(const DwArgs& p, const PostBwdArg
       tm = 2 * (b / nbn) + (i >> 1);
       tn = 2 * (b % nbn) + (i & 1);
     }
-    dw_item<4>(L, split, tm * 128, tn * 128, kbeg, min(p.N, kbeg + L.kchunk), fr, fh);
+    dw_item<4>(L, p.N, split, tm * 128, tn * 128, kbeg, min(p.N, kbeg + L.kchunk), fr, fh);
   }
   if (p.n_narrow > 0) {
     const int used = p.n_full % nwaves;                 // waves busy in the last round of full items
@@ -605,9 +611,9 @@ __device__ __forceinline__ void dw_stream_body(const DwArgs& p, const PostBwdArg
         const int kbeg = split * L.kchunk, kend = min(p.N, kbeg + L.kchunk);
         const int m0 = tm * 128, n0 = (L.tiles_n - 1) * 128;
         switch (L.last_nj) {
-          case 1: dw_item<1>(L, split, m0, n0, kbeg, kend, fr, fh); break;
-          case 2: dw_item<2>(L, split, m0, n0, kbeg, kend, fr, fh); break;
-          default: dw_item<3>(L, split, m0, n0, kbeg, kend, fr, fh); break;
+          case 1: dw_item<1>(L, p.N, split, m0, n0, kbeg, kend, fr, fh); break;
+          case 2: dw_item<2>(L, p.N, split, m0, n0, kbeg, kend, fr, fh); break;
+          default: dw_item<3>(L, p.N, split, m0, n0, kbeg, kend, fr, fh); break;
         }
       }
     }
