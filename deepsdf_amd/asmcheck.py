@@ -1,15 +1,17 @@
 """Build-time check of the one place where inline asm leaves loads in flight across C++ code (dwstream.hpp dw_block_split).
 
-The first asm statement there issues 16 ``ds_read_b128`` and ends in ``s_waitcnt lgkmcnt(8)``: the eight A fragments have
-landed, the eight B reads are still in flight while the A terms are cut; a second statement (``s_waitcnt lgkmcnt(0)``) ends the
-window.  The compiler cannot see loads inside asm, so BETWEEN the two statements it believes the B registers hold data: a copy,
-an AGPR move or a spill of one of them placed there would read stale registers.  Whether it does that is a register-allocation
-outcome -- so every build of the library (lab flags included) is checked on the gfx950 code object itself:
+The first asm statement of a step there issues 16 ``ds_read_b128`` (the raw A and B rows of the NEXT step) and ends without a
+wait: all sixteen reads are in flight while four groups of MFMAs and cut instructions run; a second statement
+(``s_waitcnt lgkmcnt(0)``) ends the window.  The compiler cannot see loads inside asm, so BETWEEN the two statements it believes
+the 64 destination registers hold data: a copy, an AGPR move or a spill of one of them placed there would read stale registers.
+Whether it does that is a register-allocation outcome -- so every build of the library (lab flags included) is checked on the
+gfx950 code object itself:
 
   for each run of 16 ds_read_b128 whose statement leaves reads in flight: no instruction up to the next ``s_waitcnt lgkmcnt(0)``
   may name a destination VGPR of those reads, and none may touch scratch (a spill in the window).
 
 Tooling only (no GPU, no torch): ``python -m deepsdf_amd.asmcheck [lib]``; deepsdf_amd.build runs it after every compile.
+``python -m deepsdf_amd.asmcheck --same A B`` compares the instruction streams of two libraries, function by function (same_code).
 """
 import os
 import re
@@ -65,8 +67,8 @@ def vgprs(operands):
 def check_split_wait_windows(ins):
     """Returns the number of windows checked; raises AsmHazard on a violation.  A window opens behind a run of 16 ds_read_b128
     (the fragment reads of dwstream.hpp) that is not closed by an ``s_waitcnt lgkmcnt(0)`` at once, and extends to the next
-    ``s_waitcnt lgkmcnt(0)``: directly behind the reads either ``lgkmcnt(8)`` (dw_block_split_v1: the first eight have landed, the
-    last eight are in flight) or nothing (dw_block_split: all sixteen are in flight)."""
+    ``s_waitcnt lgkmcnt(0)``: directly behind the reads either nothing (dw_block_split: all sixteen are in flight) or
+    ``lgkmcnt(8)`` (the first eight have landed, the last eight are in flight: the first form of that block)."""
     windows = 0
     for i, (op, args) in enumerate(ins):
         if i < 16 or ins[i - 1][0] != "ds_read_b128" or op == "ds_read_b128":
@@ -103,20 +105,15 @@ def check_split_wait_windows(ins):
     return windows
 
 
-def check_library(lib, expect_windows=True):
-    """Raises AsmHazard if the library's dw_stream_split_kernel violates the rule; returns the number of windows found
-    (0 is an error unless the build was made with the single-wait variant, expect_windows=False)."""
+def check_library(lib):
+    """Raises AsmHazard if the library's dw_stream_split_kernel violates the rule or has no window at all; returns the number of
+    windows found."""
     with tempfile.TemporaryDirectory(prefix="dsdf_asmcheck_") as d:
         ins = disassemble(extract_code_object(lib, d), KERNEL)
     n = check_split_wait_windows(ins)
-    if expect_windows and n == 0:
+    if n == 0:
         raise AsmHazard(f"{KERNEL}: no split-wait window found (16 ds_read_b128 left in flight); the check would be vacuous")
     return n
-
-
-if __name__ == "__main__":
-    lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdsdf_hip.so")
-    print(f"{KERNEL}: {check_library(lib, expect_windows='--allow-none' not in sys.argv)} split-wait window(s) clean")
 
 
 # ---- second audit: MFMA source registers overwritten by a later load (fused_bf16x8.hpp, two waves per SIMD) -----------------
@@ -273,3 +270,68 @@ def check_dw_ring_waits(lib, ring=16, kernel="dw_stream_kernel"):
     with tempfile.TemporaryDirectory(prefix="dsdf_asmcheck_") as d:
         ins = disassemble_with_addresses(extract_code_object(lib, d), kernel)
     return check_dw_ring_waits_ins(ins, ring)
+
+
+# ---- comparing two libraries: has a source change moved any instruction? ---------------------------------------------------------
+# A refactor of the kernel sources that must not change what the GPU executes is proved here, without a GPU: every function of
+# the two gfx950 code objects is disassembled and compared as text, mnemonic and operands, in order.  ONE thing is masked: the
+# literal of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64.  That is the PC-relative distance to data, and it moves in
+# kernels nobody touched when code elsewhere in the translation unit changes size.
+def function_streams(lib):
+    """{name: [(mnemonic, operands)]} for every FUNC symbol of the library's gfx950 code object."""
+    with tempfile.TemporaryDirectory(prefix="dsdf_asmcheck_") as d:
+        co = extract_code_object(lib, d)
+        syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-sW", co], capture_output=True, text=True, check=True).stdout
+        text = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", co], capture_output=True, text=True, check=True).stdout
+    funcs = {f.split()[7]: [] for f in syms.splitlines() if len(f.split()) >= 8 and f.split()[3] == "FUNC"}
+    cur = None
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
+        if m:
+            cur = funcs.get(m.group(1))
+            continue
+        m = re.match(r"^\s+([a-z_0-9]+)\s*(.*?)\s*//", line)
+        if m and cur is not None:
+            cur.append((m.group(1), m.group(2)))
+    return funcs
+
+
+def mask_pc_relative(ins):
+    out = list(ins)
+    for i in range(len(out) - 2):
+        if out[i][0] == "s_getpc_b64" and out[i + 1][0] == "s_add_u32" and out[i + 2][0] == "s_addc_u32":
+            for j in (i + 1, i + 2):
+                out[j] = (out[j][0], out[j][1].rsplit(",", 1)[0] + ", <pc-relative>")
+    return out
+
+
+def same_streams(a, b):
+    """a, b: {function: [(mnemonic, operands)]}.  Returns ({function in both: (instructions in a, instructions in b, index of the
+    first difference or None)}, names only in a, names only in b)."""
+    per = {}
+    for name in sorted(set(a) & set(b)):
+        x, y = mask_pc_relative(a[name]), mask_pc_relative(b[name])
+        diff = next((i for i, (p, q) in enumerate(zip(x, y)) if p != q), None)
+        if diff is None and len(x) != len(y):
+            diff = min(len(x), len(y))
+        per[name] = (len(x), len(y), diff)
+    return per, sorted(set(a) - set(b)), sorted(set(b) - set(a))
+
+
+def same_code(lib_a, lib_b):
+    """same_streams of the gfx950 code objects of two builds of the library."""
+    return same_streams(function_streams(lib_a), function_streams(lib_b))
+
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["--same"]:
+        per, only_a, only_b = same_code(sys.argv[2], sys.argv[3])
+        for name, (na, nb, diff) in per.items():
+            print(f"{name} {na} " + ("equal" if diff is None else f"DIFFERENT at instruction {diff} ({na} / {nb} instructions)"))
+        for name in only_a + only_b:
+            print(f"{name} - ONLY IN {'A' if name in only_a else 'B'}")
+        bad = sum(d is not None for _, _, d in per.values()) + len(only_a) + len(only_b)
+        print(f"# {len(per)} functions compared, {bad} different or missing")
+        sys.exit(1 if bad else 0)
+    lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdsdf_hip.so")
+    print(f"{KERNEL}: {check_library(lib)} split-wait window(s) clean")

@@ -45,7 +45,7 @@ def build_library(force=False, verbose=False):
     from . import asmcheck
     if asmcheck.tools_available():
         try:
-            asmcheck.check_library(LIB, expect_windows="-DDW_SPLIT_ONE_WAIT=1" not in cmd)
+            asmcheck.check_library(LIB)
             asmcheck.check_mfma_src_reuse(LIB, min_distance=2)      # fused_bf16x8.hpp: a step is >= 2 MFMAs (one n-tile per wave)
             ring = [int(f.split("=", 1)[1]) for f in cmd if f.startswith("-DDW_RING_STEPS=")]
             asmcheck.check_dw_ring_waits(LIB, ring=ring[-1] if ring else 16)   # dwstream.hpp: the fp32 dW ring never drains in its loop

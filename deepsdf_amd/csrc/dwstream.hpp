@@ -177,9 +177,6 @@ __device__ __forceinline__ void dw_item(const DwLayer& L, int N, int split, int 
 // TWO 128-column panels of each operand, and stream them with direct-to-LDS loads (buffer_load_dwordx4 ... lds: no registers in flight)
 // into a ring of DWS_RING steps of 32 KB; one barrier per step publishes a step and frees the slot of the previous one.  Rows past the
 // item's last point read as zero through the buffer bounds check (row offset in the VECTOR offset).  Accumulators as in dw_item<4>.
-#ifndef DW_SPLIT_ONE_WAIT
-#define DW_SPLIT_ONE_WAIT 0     // 1: the fragment reads end in ONE wait (no loads in flight across C++ code); measured in DESIGN.md 4.3
-#endif
 constexpr int DWS_RING = 4;
 constexpr int DWS_SLOT = 2 * 16 * 256;      // floats per ring slot: A panel [16 points][256 columns], then the B panel
 
@@ -195,116 +192,9 @@ __device__ __forceinline__ Split3 split8v(const float (&x)[8]) {
   return s;
 }
 
-// the workgroup's block: row tiles tmb, tmb + 1 and column tiles tnb, tnb + 1 of `split`; wave w takes (tmb + (w >> 1), tnb + (w & 1))
-__device__ __forceinline__ void dw_block_split_v1(const DwLayer& L, int split, int tmb, int tnb, int kbeg, int kend, int w, int lane, float* ring) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int npts = kend - kbeg, nsteps = (npts + 15) >> 4;      // steps of 16 points (uniform over the workgroup)
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(L.dp + (size_t)kbeg * L.ld_dp), 0, npts * L.ld_dp * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(L.act + (size_t)kbeg * L.ld_act), 0, npts * L.ld_act * 4, 0x00020000);
-  // producer side: this wave brings rows 4w .. 4w+3 of every step, one load instruction = one 256-column row of a panel (lane l:
-  // columns 4l .. 4l+3 -> the row lands contiguously at the LDS pointer)
-  const int pva = (tmb * 128 + 4 * lane) * 4, pvb = (tnb * 128 + 4 * lane) * 4;
-  auto issue = [&](int st) __attribute__((always_inline)) {
-    float* slot = ring + (st % DWS_RING) * DWS_SLOT;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int row = 4 * w + rr, pt = 16 * st + row;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(slot + row * 256), 16, pt * L.ld_dp * 4 + pva, 0, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr)(slot + 4096 + row * 256), 16, pt * L.ld_act * 4 + pvb, 0, 0, 0);
-    }
-  };
-  f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#pragma unroll
-  for (int st = 0; st < DWS_RING - 1; ++st) issue(st);      // (steps past the end: every row out of range, zeros land in LDS)
-  const int ca = (w >> 1) * 128 + 4 * fr, cb = 4096 + (w & 1) * 128 + 4 * fr;
-  for (int st = 0; st < nsteps; ++st) {
-    // this wave's loads of step st are the oldest 8 of the 8 (DWS_RING - 1) in flight
-    __builtin_amdgcn_s_waitcnt(0x0F70 | (((8 * (DWS_RING - 2)) & 15)) | ((((8 * (DWS_RING - 2)) >> 4) & 3) << 14));   // vmcnt(16), nothing else
-    __builtin_amdgcn_s_barrier();          // step st is complete in LDS; everybody is done reading step st - 1  (the bare barrier:
-                                           // __syncthreads()' fence makes the compiler wait for ALL loads in flight, vmcnt(0))
-    issue(st + DWS_RING - 1);              // ... whose slot takes step st + DWS_RING - 1
-    // The fragment reads are inline asm ON PURPOSE: the compiler's wait-count pass cannot tell the ring slots apart and puts
-    // s_waitcnt vmcnt(0) in front of any ds_read it sees -- i.e. it waits for the loads just issued, and the ring is worth nothing.
-    // (Inline asm hides hazards from it as well, cf. fused_bf16x8's history: the lgkmcnt wait is part of the asm.)
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    f32x4 a[8], b[8];
-    {
-      typedef __attribute__((address_space(3))) const float* lds_cf;
-      const float* slot = ring + (st % DWS_RING) * DWS_SLOT;
-      const uint32_t aa = (uint32_t)(uintptr_t)(lds_cf)(slot + 8 * fh * 256 + ca), ab = (uint32_t)(uintptr_t)(lds_cf)(slot + 8 * fh * 256 + cb);
-      asm volatile(
-          "ds_read_b128 %0, %16\n ds_read_b128 %1, %16 offset:1024\n ds_read_b128 %2, %16 offset:2048\n ds_read_b128 %3, %16 offset:3072\n"
-          "ds_read_b128 %4, %16 offset:4096\n ds_read_b128 %5, %16 offset:5120\n ds_read_b128 %6, %16 offset:6144\n ds_read_b128 %7, %16 offset:7168\n"
-          "ds_read_b128 %8, %17\n ds_read_b128 %9, %17 offset:1024\n ds_read_b128 %10, %17 offset:2048\n ds_read_b128 %11, %17 offset:3072\n"
-          "ds_read_b128 %12, %17 offset:4096\n ds_read_b128 %13, %17 offset:5120\n ds_read_b128 %14, %17 offset:6144\n ds_read_b128 %15, %17 offset:7168\n"
-#if DW_SPLIT_ONE_WAIT
-          "s_waitcnt lgkmcnt(0)"     // A/B switch (tools/lab_split.sh): everything has landed when the statement ends
-#else
-          "s_waitcnt lgkmcnt(8)"     // the A fragments are there; the B reads stay in flight while A is cut (second wait below)
-#endif
-          : "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]), "=&v"(a[3]), "=&v"(a[4]), "=&v"(a[5]), "=&v"(a[6]), "=&v"(a[7]),
-            "=&v"(b[0]), "=&v"(b[1]), "=&v"(b[2]), "=&v"(b[3]), "=&v"(b[4]), "=&v"(b[5]), "=&v"(b[6]), "=&v"(b[7])
-          : "v"(aa), "v"(ab)
-          : "memory");
-    }
-    Split3 sa[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float x[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) x[k] = i == 0 ? a[k].x : (i == 1 ? a[k].y : (i == 2 ? a[k].z : a[k].w));
-      sa[i] = split8v(x);
-    }
-#if !DW_SPLIT_ONE_WAIT
-    // (the operands tie the B registers to this wait: nothing that READS them can be scheduled in front of it.  What the operands
-    // cannot express is that b[] is not yet valid between the two statements: a copy / AGPR move / spill of a B register placed
-    // there by the register allocator would read stale data.  deepsdf_amd/asmcheck.py checks every build's code object for exactly
-    // that -- no instruction in the window names a B destination, no scratch traffic -- and deepsdf_amd/build.py refuses the
-    // library otherwise; -DDW_SPLIT_ONE_WAIT=1 is the variant without a window.)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]));
-#endif
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float x[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) x[k] = j == 0 ? b[k].x : (j == 1 ? b[k].y : (j == 2 ? b[k].z : b[k].w));
-      const Split3 sb = split8v(x);
-#define DW_PASS(AX, BX)                                                                                                     \
-      _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                          \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[i].AX, sb.BX, acc[i][j], 0, 0, 0);
-      DW_PASS(l, h) DW_PASS(h, l) DW_PASS(m, m) DW_PASS(m, h) DW_PASS(h, m) DW_PASS(h, h)
-#undef DW_PASS
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the loads issued past the last step have landed ...
-  __syncthreads();                         // ... before anybody reuses the ring
-  // epilogue: acc[i][j][reg] = dW[m0 + 4 (crow(reg) + 4 fh) + i][n0 + 4 fr + j]  ->  one 16-byte store per (i, reg)
-  const int m0 = (tmb + (w >> 1)) * 128, n0 = (tnb + (w & 1)) * 128;
-  float* slab = L.slabs + (size_t)split * L.slab;
-  __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)slab, 0, L.M * L.ldc * 4, 0x00020000);
-  const int n = n0 + 4 * fr;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int rg = 0; rg < 16; ++rg) {
-      const int m = m0 + 4 * (crow(rg) + 4 * fh) + i;       // rows >= M fall outside the descriptor and are dropped
-      const uint32_t voff = n < L.ldc ? (uint32_t)((m * L.ldc + n) * 4) : 0x7FFFFFFFu;   // ldc % 4 == 0
-      u32x4 v = {__float_as_uint(acc[i][0][rg]), __float_as_uint(acc[i][1][rg]), __float_as_uint(acc[i][2][rg]),
-                 __float_as_uint(acc[i][3][rg])};
-      __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, 0, 0);
-    }
-}
-
-// ---- the same block with the cut woven between the MFMAs (DW_SPLIT_WEAVE, default) ----------------------------------------------------
-// dw_block_split_v1 above runs a step as  [16 LDS reads] [cut A: 176 VALU] [per column: cut B, 24 MFMAs]: a lone in-order wave overlaps
+// ---- the workgroup's block, the cut woven between the MFMAs -------------------------------------------------------------------------
+// Row tiles tmb, tmb + 1 and column tiles tnb, tnb + 1 of `split`; wave w takes (tmb + (w >> 1), tnb + (w & 1)).
+// Run as  [16 LDS reads] [cut A: 176 VALU] [per column: cut B, 24 MFMAs]  (the first form of this block) a lone in-order wave overlaps
 // none of the cut with its MFMAs (tools/lab/split_weave.hip: 11 VALU in front of 3 MFMAs = 140 cycles, woven between them 101-112), the
 // kernel sat at 60 % MFMA-busy.  Here the step is software-pipelined by one step and written as 32 asm groups (fused.hpp SPLIT_GROUP_P:
 // MFMA, 4 VALU, MFMA, 4 VALU, MFMA, 3 VALU), the MFMAs of step st woven with the cut of what comes next:
@@ -312,12 +202,15 @@ __device__ __forceinline__ void dw_block_split_v1(const DwLayer& L, int split, i
 //                                          groups 4-7 cut row tile j of the A operand of step st + 1
 // so every term is cut one block / one step before its first MFMA.  Registers: two sets of A terms (this step's / the next's, 2 x 48),
 // two of one B column (2 x 12), the raw A rows of the next step (32) and the raw B rows of this and the next step (2 x 32).
+// The fragment reads are inline asm ON PURPOSE: the compiler's wait-count pass cannot tell the ring slots apart and puts
+// s_waitcnt vmcnt(0) in front of any ds_read it sees -- i.e. it waits for the loads just issued, and the ring is worth nothing.
+// (Inline asm hides hazards from it as well, cf. fused_bf16x8's history: the lgkmcnt wait is asm too.)
 // The raw rows of step st + 1 are read from the LDS ring at the top of step st (16 ds_read_b128 in one asm statement); their first use
-// is group 4, which opens with the s_waitcnt lgkmcnt(0) -- groups 0-3 run in that window and name none of the 64 destination
-// registers (deepsdf_amd/asmcheck.py checks exactly that on every build's code object).
-#ifndef DW_SPLIT_WEAVE
-#define DW_SPLIT_WEAVE 1
-#endif
+// is group 4, which opens with the s_waitcnt lgkmcnt(0) -- groups 0-3 run in that window.  The wait's "+v" operands tie the 64
+// destination registers to it: nothing that READS them can be scheduled in front of it.  What the operands cannot express is that
+// the registers are not yet valid between the two statements: a copy / AGPR move / spill of one of them placed there by the register
+// allocator would read stale data.  deepsdf_amd/asmcheck.py checks every build's code object for exactly that -- no instruction in
+// the window names a destination of the reads, no scratch traffic -- and deepsdf_amd/build.py refuses the library otherwise.
 typedef float dw_f32x4 __attribute__((ext_vector_type(4)));
 template <int J> __device__ __forceinline__ float dw_comp(const dw_f32x4& v) { return J == 0 ? v.x : (J == 1 ? v.y : (J == 2 ? v.z : v.w)); }
 struct DwRaw { dw_f32x4 v[8]; };                 // 8 points x 4 consecutive columns of one operand panel
@@ -331,7 +224,9 @@ __device__ __forceinline__ void dw_block_split(const DwLayer& L, int split, int 
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(L.dp + (size_t)kbeg * L.ld_dp), 0, npts * L.ld_dp * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(L.act + (size_t)kbeg * L.ld_act), 0, npts * L.ld_act * 4, 0x00020000);
   const int pva = (tmb * 128 + 4 * lane) * 4, pvb = (tnb * 128 + 4 * lane) * 4;
-  auto issue = [&](int st) __attribute__((always_inline)) {     // this wave brings rows 4w .. 4w+3 of step st's two panels (see v1)
+  // producer side: this wave brings rows 4w .. 4w+3 of step st's two panels, one load instruction = one 256-column row of a panel
+  // (lane l: columns 4l .. 4l+3 -> the row lands contiguously at the LDS pointer)
+  auto issue = [&](int st) __attribute__((always_inline)) {
     float* slot = ring + (st % DWS_RING) * DWS_SLOT;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
@@ -391,7 +286,8 @@ __device__ __forceinline__ void dw_block_split(const DwLayer& L, int split, int 
   Split3 sa0[4], sa1[4], sb0, sb1;     // A terms of the even / odd steps; one B column's terms, alternating
   // prologue = "step -1": the raw rows of step 0, their A terms and the terms of B column 0, cut by compiler-scheduled code
   __builtin_amdgcn_s_waitcnt(0x0F70 | (((8 * (DWS_RING - 2)) & 15)) | ((((8 * (DWS_RING - 2)) >> 4) & 3) << 14));   // vmcnt(16): step 0 has landed
-  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_s_barrier();        // (this wave's loads of a step are the oldest 8 of the 8 (DWS_RING - 1) in flight.  The bare barrier:
+                                       // __syncthreads()' fence makes the compiler wait for ALL loads in flight, vmcnt(0))
   issue(DWS_RING - 1);
   DW_READ_RAW(0, an, b0, "s_waitcnt lgkmcnt(0)")
 #pragma unroll
@@ -571,11 +467,7 @@ __device__ __forceinline__ void dw_stream_body(const DwArgs& p, const PostBwdArg
       if (block) {
         const int split = local0 / tf0, b = (local0 - split * tf0) >> 2, nbn = L0.nfull_n >> 1;
         const int kbeg = split * L0.kchunk;
-#if DW_SPLIT_WEAVE
         dw_block_split(L0, split, 2 * (b / nbn), 2 * (b % nbn), kbeg, min(p.N, kbeg + L0.kchunk), w, lane, ring);
-#else
-        dw_block_split_v1(L0, split, 2 * (b / nbn), 2 * (b % nbn), kbeg, min(p.N, kbeg + L0.kchunk), w, lane, ring);
-#endif
         continue;
       }
     }

@@ -97,6 +97,14 @@ struct FusedFwdArgs {
   float* y_out; float* u_out;
   unsigned long long* dbg;   // lab builds (-DDSDF_LAB): per-workgroup s_memtime stamps, else unused
 };
+// one stamp of a lab build into slot SLOT of the workgroup's 64 (forward: 0, then 3 per layer; backward: FusedBwdArgs).
+// (fused_forward_body spells its seven stamps out: stamped through the macro, the epilogues of the two fp32 split kernels of a
+// lab build come out in another order -- same instructions, other schedule -- and lab timings would no longer compare.)
+#ifdef DSDF_LAB
+#define FUSED_STAMP(P, SLOT) do { if ((P).dbg && threadIdx.x == 0) (P).dbg[blockIdx.x * 64 + (SLOT)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define FUSED_STAMP(P, SLOT) do { } while (0)
+#endif
 
 // rows of x0 into slab columns [col0, col0 + W0).  All 16-byte loads of a pass are issued back-to-back BEFORE the
 // first LDS write: a load-use-load-use loop would pay the HBM latency dozens of times in a row.
@@ -234,7 +242,9 @@ __device__ __forceinline__ void fused_fwd_epilogue(const f32x16 (&acc)[MT][NT], 
 }
 
 // Optional (lab: -DFUSED_ROTATE=1): every workgroup walks the k-units of a layer in its own rotated order, so that the CUs
-// of an XCD do not all stream the same weight lines at the same moment (one L2 channel at a time).
+// of an XCD do not all stream the same weight lines at the same moment (one L2 channel at a time).  Measured 1 % slower
+// (DESIGN.md 4.1).  The switch outlived the other retired variants: without fused_rot / fused_unit the fp32 k-loops of seven
+// kernels come out with another register allocation (profiles/retire_variants_same_code.log), which wants a GPU A/B.
 #ifndef FUSED_ROTATE
 #define FUSED_ROTATE 0
 #endif
@@ -278,26 +288,6 @@ __device__ __forceinline__ void fused_prefetch_b(FusedBSetsT<NT>& B, const float
 // Weights come through a buffer resource: the address of k-unit u of n-tile t is scalar ((t U + u) * 2 KiB, an SGPR
 // soffset) plus a per-lane constant, so the loads need NO vector address arithmetic (a lone wave pays for every VALU
 // instruction it issues between its MFMAs).
-#ifndef FUSED_RSRC4
-#define FUSED_RSRC4 0      // lab: 1 = one buffer resource per n-tile, ONE scalar offset per k-unit instead of one per load (measured: no difference -- the scalar instructions are not what the k-loop waits for)
-#endif
-#if FUSED_RSRC4
-struct FusedBView { __amdgpu_buffer_rsrc_t rsrc[4]; int voff; };   // rsrc[ni] based at n-tile (w + 4 ni); voff = lane * 16
-__device__ __forceinline__ FusedBView fused_bview(const float* wf, int U, int w, int lane, int nws = 4) {
-  FusedBView v;
-  const int ws = __builtin_amdgcn_readfirstlane(w);
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni)
-    v.rsrc[ni] = __builtin_amdgcn_make_buffer_rsrc((void*)(wf + (size_t)(ws + nws * ni) * U * 512), 0, 0x7FFFFFFF, 0x00020000);
-  v.voff = lane * 16;
-  return v;
-}
-__device__ __forceinline__ float4 fused_bload(const FusedBView& B, int ni, int u, int half) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(B.rsrc[ni], B.voff + 1024 * half, u * 2048, 0);
-  return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
-}
-#else
 struct FusedBView { __amdgpu_buffer_rsrc_t rsrc; int tbase[4]; int voff; };   // tbase[ni] = (w + 4 ni) * U; voff = lane * 16
 __device__ __forceinline__ FusedBView fused_bview(const float* wf, int U, int w, int lane, int nws = 4) {
   FusedBView v;
@@ -313,7 +303,6 @@ __device__ __forceinline__ float4 fused_bload(const FusedBView& B, int ni, int u
   const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(B.rsrc, B.voff + 1024 * half, (B.tbase[ni] + u) * 2048, 0);
   return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
 }
-#endif
 
 template <int NACT, int MT = 2, int NT = 4, int LDSW = FLD>
 __device__ __forceinline__ void fused_kloop(f32x16 (&acc)[MT][NT], const float* ap, const FusedBView& bv, int nu,
@@ -469,18 +458,13 @@ __device__ __forceinline__ SplitBView split_bview(const float* ws, int plane, co
   v.voff = lane * 16;
   return v;
 }
-#ifndef SPLIT_LAB_U0
-#define SPLIT_LAB_U0 0     // lab (wrong results, timing only): every weight load reads k-unit 0 -- takes the L2 stream out of the k-loop
-#endif
 __device__ __forceinline__ bf16x8 split_bload(const SplitBView& B, int ni, int u, int pl) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  if (SPLIT_LAB_U0) u = 0;
   const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(B.rsrc, B.voff, pl * B.plane + ((B.tbase[ni] + u) << 10), 0);
   return __builtin_bit_cast(bf16x8, r);
 }
 __device__ __forceinline__ float4 split_bload32(const SplitBView& B, int ni, int u, int half) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  if (SPLIT_LAB_U0) u = 0;
   const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(B.rsrc32, B.voff + 1024 * half, (B.tbase[ni] + u) * 2048, 0);
   return make_float4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w));
 }
@@ -511,11 +495,9 @@ __device__ __forceinline__ void split_prefetch_b(SplitBSet& P, const float* ws, 
 }
 
 // Software pipeline: while the 12 NACT MFMAs of k-unit u run, the operands of unit u+1 (loaded one step earlier) are cut into their bf16
-// terms and the loads of unit u+2 go out; sched_group_barrier pins the interleave (a lone in-order wave that does its ~180 VALU
-// instructions in one block lets the MFMA pipe run dry meanwhile: 49 % MFMA-busy before).
-#ifndef SPLIT_SCHED
-#define SPLIT_SCHED 0      // lab: 1 = pin the MFMA / VALU / load interleave with sched_group_barrier (measured slower: 544 against 505 us), 2 = MFMA / VALU groups only (530)
-#endif
+// terms and the loads of unit u+2 go out (a lone in-order wave that does its ~180 VALU instructions in one block lets the MFMA pipe
+// run dry meanwhile: 49 % MFMA-busy before).  The interleave is the compiler's: pinning it with sched_group_barrier
+// measured slower (544 us, MFMA / VALU groups only 530, against 505) and the requested pattern is not what comes out.
 template <int NACT>
 __device__ __forceinline__ void fused_kloop_split(f32x16 (&acc)[2][4], const float* ap, const SplitBView& bv, int nu, SplitBSet& PB) {
   struct Raw { float4 a[4]; bf16x8 b[4][3]; float4 f[4][2]; };       // one k-unit as it comes from LDS / L2
@@ -550,19 +532,6 @@ __device__ __forceinline__ void fused_kloop_split(f32x16 (&acc)[2][4], const flo
     SPLIT_PASS(l, h) SPLIT_PASS(h, l) SPLIT_PASS(m, m) SPLIT_PASS(m, h) SPLIT_PASS(h, m) SPLIT_PASS(h, h)
 #undef SPLIT_PASS
   };
-  auto interleave = [&]() __attribute__((always_inline)) {
-#if SPLIT_SCHED
-    constexpr int NM = 12 * NACT, NVM = 3 * NPL + 2 * (NACT - NPL), NVAL = 44 * (2 + NACT - NPL);   // MFMAs, loads, cut instructions per step
-    constexpr int VPM = (NVAL + NM - 1) / NM;
-#pragma unroll
-    for (int q = 0; q < NM; ++q) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);     // VALU
-      if (SPLIT_SCHED == 1 && q % 4 == 1 && q / 4 < NVM) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);    // VMEM read
-      if (SPLIT_SCHED == 1 && q % 4 == 3 && q / 4 < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
-    }
-#endif
-  };
 #pragma unroll
   for (int ni = 0; ni < NACT; ++ni) {     // the weights of unit 0 came with the cross-layer prefetch
 #pragma unroll
@@ -579,12 +548,10 @@ __device__ __forceinline__ void fused_kloop_split(f32x16 (&acc)[2][4], const flo
     load(r0, min(u + 2, ulast));     // unit u+2 -> the raw set unit u came from
     cut(c1, r1);                     // unit u+1
     mma(c0);                         // unit u
-    interleave();
     if (u + 1 >= nu) break;
     load(r1, min(u + 3, ulast));
     cut(c0, r0);                     // unit u+2
     mma(c1);                         // unit u+1
-    interleave();
   }
 }
 
@@ -598,9 +565,6 @@ __device__ __forceinline__ void fused_kloop_split(f32x16 (&acc)[2][4], const flo
 // leaves free (MI355X_MICROARCH.md: issue costs summing to <= 24 cycles per gap hide).  Loads stay compiler-issued builtins (it
 // counts them and waits before the first group that reads their registers).  No hazard needs padding inside a group: the VALU
 // results are MFMA operands only one half-step later, the three MFMAs write three different accumulators.
-#ifndef SPLIT_ASM
-#define SPLIT_ASM 1        // 0: the compiler-scheduled loop above for every NACT (A/B switch)
-#endif
 // One group: three MFMAs and 11 VALU instructions of the cut chain, SOFTWARE-PIPELINED over three groups: stage 1 (h and the residual
 // r = x - h) of pair g, stage 2 (m, and r -> t = r - m in place) of pair g - 1, stage 3 (l) of pair g - 2.  Written as one dependent chain
 // per group (the first version) every instruction depends on the one or two in front of it; here no instruction reads a result of the
@@ -696,12 +660,12 @@ __device__ __forceinline__ void fused_kloop_split_asm4(f32x16 (&acc)[2][4], cons
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     if (i < 6) {
       const int ni = i % 2, pl = i / 2;      // both tiles' h terms first (operands of the next half-step's very first MFMAs), then m, then l
-      int so = pl * bv.plane + ((bv.tbase[ni] + (SPLIT_LAB_U0 ? 0 : up)) << 10);
+      int so = pl * bv.plane + ((bv.tbase[ni] + up) << 10);
       asm volatile("" : "+s"(so));
       pn.b[ni][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(bv.rsrc, bv.voff, so, 0));
     } else if (i < 10) {
       const int ni = (i - 6) / 2, half = (i - 6) % 2;
-      int so = (bv.tbase[2 + ni] + (SPLIT_LAB_U0 ? 0 : ur)) * 2048;
+      int so = (bv.tbase[2 + ni] + ur) * 2048;
       asm volatile("" : "+s"(so));
       const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(bv.rsrc32, bv.voff + 1024 * half, so, 0);
       rn.f[ni][half] = make_float4(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z), __uint_as_float(q.w));
@@ -831,11 +795,7 @@ __device__ __forceinline__ void fused_kloop_dispatch(f32x16 (&acc)[MT][NT], cons
   if constexpr (SPLIT) {
     const SplitBView bv = split_bview(wf, wplane, wf32, U, w, lane);
     switch (nact) {
-#if SPLIT_ASM
       case 4: fused_kloop_split_asm4(acc, ap, bv, nu, PB); break;
-#else
-      case 4: fused_kloop_split<4>(acc, ap, bv, nu, PB); break;
-#endif
       case 3: fused_kloop_split<3>(acc, ap, bv, nu, PB); break;
       case 2: fused_kloop_split<2>(acc, ap, bv, nu, PB); break;
       case 1: fused_kloop_split<1>(acc, ap, bv, nu, PB); break;
@@ -1181,15 +1141,8 @@ struct Bf16Pre { bf16x8 b[BF_PRE][4]; };
 // stream the same weights in the same order at the same pace keep hitting ONE L2 channel at a time.  A rotation of the
 // contraction order only permutes the fp32 summation; it is a fixed function of the workgroup index, so results stay
 // run-to-run bit-identical.
-#ifndef BF_ROTATE
-#define BF_ROTATE 1
-#endif
 __device__ __forceinline__ int bf16_rot(int nu) {
-#if BF_ROTATE
   return nu > 0 ? (int)(((blockIdx.x >> 3) * (unsigned)nu) >> 5) % nu : 0;   // blocks b, b+8, ... share an XCD (common.hpp)
-#else
-  return 0;
-#endif
 }
 
 // Weights come through a buffer resource with SCALAR offsets (as in the fp32 kernel's FusedBView): the first version built a
@@ -1347,9 +1300,7 @@ __device__ __forceinline__ void fused_forward_bf16_body(const FusedFwdArgs& p, f
     fused_load_x0_h(SH, p.x0, p.ldx0, p.W0, row0, p.N, 0);
   }
   __syncthreads();
-#ifdef DSDF_LAB
-  if (p.dbg && tid == 0) p.dbg[blockIdx.x * 64 + 0] = __builtin_amdgcn_s_memtime();
-#endif
+  FUSED_STAMP(p, 0);
   for (int l = 0; l < p.n_hidden; ++l) {
     const FusedLayer& L = p.ly[l];
     const int nu = (L.in + 15) >> 4, nact = fused_nact(L.out_dim, w);
@@ -1379,13 +1330,9 @@ __device__ __forceinline__ void fused_forward_bf16_body(const FusedFwdArgs& p, f
         bf16_prefetch(R, reinterpret_cast<const __bf16*>(Ln.wf), Ln.U, w, lane, fused_nact(Ln.out_dim, w), (Ln.in + 15) >> 4);
       }
     }
-#ifdef DSDF_LAB
-    if (p.dbg && tid == 0) p.dbg[blockIdx.x * 64 + 1 + 3 * l] = __builtin_amdgcn_s_memtime();
-#endif
+    FUSED_STAMP(p, 1 + 3 * l);
     __syncthreads();   // every wave has finished reading the slab: it may be overwritten in place
-#ifdef DSDF_LAB
-    if (p.dbg && tid == 0) p.dbg[blockIdx.x * 64 + 2 + 3 * l] = __builtin_amdgcn_s_memtime();
-#endif
+    FUSED_STAMP(p, 2 + 3 * l);
     const bool last_hidden = l + 1 == p.n_hidden;
     if (L.x0_col >= 0) fused_load_x0_h(SH, p.x0, p.ldx0, p.W0, row0, p.N, L.x0_col);
     {
@@ -1406,9 +1353,7 @@ __device__ __forceinline__ void fused_forward_bf16_body(const FusedFwdArgs& p, f
       for (int i = tid; i < FROWS * zc; i += 256) SH[(i / zc) * FLDH + L.out_dim + (i % zc)] = (__bf16)0.f;
     }
     __syncthreads();
-#ifdef DSDF_LAB
-    if (p.dbg && tid == 0) p.dbg[blockIdx.x * 64 + 3 + 3 * l] = __builtin_amdgcn_s_memtime();
-#endif
+    FUSED_STAMP(p, 3 + 3 * l);
   }
   if (p.y_out == nullptr && p.u_out == nullptr) return;   // training: the backward head recomputes the output layer from the slab
   float4 qv[2];
@@ -1492,11 +1437,6 @@ struct FusedBwdArgs {
   FusedBwdLayer ly[DSDF_MAX_LAYERS];
   unsigned long long* dbg;   // lab builds (-DDSDF_LAB): per-workgroup s_memtime stamps (slots 32..: head, then 3 per layer), else unused
 };
-#ifdef DSDF_LAB
-#define FUSED_STAMP(P, SLOT) do { if ((P).dbg && threadIdx.x == 0) (P).dbg[blockIdx.x * 64 + (SLOT)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define FUSED_STAMP(P, SLOT) do { } while (0)
-#endif
 
 template <bool XS, int MT = 2, int NT = 4, int LDSW = FLD>
 __device__ __forceinline__ void fused_bwd_epilogue(const f32x16 (&acc)[MT][NT], float* S, const FusedBwdLayer& L, int w, int fr,

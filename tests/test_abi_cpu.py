@@ -227,8 +227,8 @@ def test_warm_own_code_bound_is_inside_the_text_section(tmp_path):
 
 
 def test_split_wait_window_of_the_dw_split_kernel_is_clean():
-    """dwstream.hpp dw_block_split keeps eight ds_read_b128 in flight across compiler-scheduled code (asm statement 1 ends in
-    lgkmcnt(8), statement 2 is the lgkmcnt(0)).  Correct only if nothing in between touches their destination registers -- a
+    """dwstream.hpp dw_block_split keeps all sixteen ds_read_b128 of a step in flight across compiler-scheduled code (asm statement
+    1 ends without a wait, statement 2 is the lgkmcnt(0)).  Correct only if nothing in between touches their destination registers -- a
     register-allocation outcome, so it is checked on the gfx950 code object of the library that was just built (the build does the
     same and refuses a violating library), and the checker itself is checked on hand-made instruction streams."""
     from deepsdf_amd import asmcheck
@@ -284,6 +284,34 @@ def test_bf16x8_kloop_never_reloads_the_sources_of_the_mfma_in_front():
         pytest.skip("ROCm LLVM tools or the built library are not available")
     worst, pairs = asmcheck.check_mfma_src_reuse(LIB, min_distance=2)
     assert worst is not None and worst >= 2 and pairs > 20
+
+
+def test_same_code_tells_equal_instruction_streams_from_changed_ones():
+    """asmcheck.same_code is how a refactor of the kernel sources is shown to leave the GPU's code alone: per function, mnemonic and
+    operand text in order, with one mask -- the literal of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 (the PC-relative
+    distance to data, which moves when code elsewhere changes size).  The comparison itself is checked on hand-made streams."""
+    from deepsdf_amd import asmcheck
+    from deepsdf_amd.build import LIB
+    pc = lambda lo, hi: [("s_getpc_b64", "s[4:5]"), ("s_add_u32", f"s4, s4, {lo}"), ("s_addc_u32", f"s5, s5, {hi}")]   # noqa: E731
+    body = [("s_load_dwordx2", "s[0:1], s[4:5], 0x0"), ("s_add_u32", "s6, s6, 0x1f38"), ("v_mov_b32_e32", "v3, v48"), ("s_endpgm", "")]
+    a = {"k1": pc("0x1f38", "0") + body, "k2": body}
+    assert asmcheck.same_streams(a, {n: list(x) for n, x in a.items()}) == ({"k1": (7, 7, None), "k2": (4, 4, None)}, [], [])
+    moved = {"k1": pc("0x2a40", "1") + body, "k2": body}                         # only the masked literal differs
+    assert asmcheck.same_streams(a, moved) == ({"k1": (7, 7, None), "k2": (4, 4, None)}, [], [])
+    other_base = {"k1": [("s_getpc_b64", "s[4:5]"), ("s_add_u32", "s4, s6, 0x1f38"), ("s_addc_u32", "s5, s5, 0")] + body, "k2": body}
+    assert asmcheck.same_streams(a, other_base)[0]["k1"] == (7, 7, 1)            # the mask covers the literal, not the registers
+    bare = {"k1": pc("0x1f38", "0") + body, "k2": [body[0], ("s_add_u32", "s6, s6, 0x2a40")] + body[2:]}
+    assert asmcheck.same_streams(a, bare)[0]["k2"] == (4, 4, 1)                  # ... and no s_add_u32 without the s_getpc_b64
+    renamed = {"k1": pc("0x1f38", "0") + body[:2] + [("v_mov_b32_e32", "v3, v49")] + body[3:], "k2": body}
+    assert asmcheck.same_streams(a, renamed) == ({"k1": (7, 7, 5), "k2": (4, 4, None)}, [], [])
+    longer = {"k1": pc("0x1f38", "0") + body, "k2": body[:3] + [("s_nop", "0")] + body[3:]}
+    assert asmcheck.same_streams(a, longer)[0]["k2"] == (4, 5, 3)
+    assert asmcheck.same_streams(a, {"k1": a["k1"], "k2": body + [("s_nop", "0")]})[0]["k2"] == (4, 5, 4)   # a longer tail alone
+    assert asmcheck.same_streams(a, {"k1": a["k1"], "k3": body}) == ({"k1": (7, 7, None)}, ["k2"], ["k3"])
+    if asmcheck.tools_available() and os.path.exists(LIB):
+        per, only_a, only_b = asmcheck.same_code(LIB, LIB)
+        assert len(per) > 100 and not only_a and not only_b
+        assert all(na == nb and na > 0 and diff is None for na, nb, diff in per.values())
 
 
 # ---- workspace planners: red zones and the region table (dsdf_debug_ws_*; host code, no device) ------------------------------------
