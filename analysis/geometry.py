@@ -2,8 +2,9 @@
 
 ``DeepSDFMesh`` takes the reference's option dictionary and gives the optimiser what it needs from the surface alone: a clean,
 closed surface (deepsdf_amd.surface.SurfaceMesh), its vertex normals, the normal-projected shape derivative (``get_dTheta_surface``)
-and the enclosed volume with its derivative with respect to the control points.  The tetrahedral half (tetgenpy, gustaf, MFEM) is
-not part of this package: ``tetrahedralize_surface`` and ``export_volume_mesh`` raise NotImplementedError."""
+and the enclosed volume with its derivative with respect to the control points.  The volume mesh comes from the grid the surface
+came from (``generate_volume_mesh``, ``export_mfem_mesh``: deepsdf_amd.tetmesh); the reference's route through tetgenpy and gustaf
+is not part of this package: ``tetrahedralize_surface`` and ``export_volume_mesh`` raise NotImplementedError."""
 import logging
 import os
 import pathlib
@@ -15,6 +16,7 @@ from deepsdf_amd import workspace as ws
 from deepsdf_amd.mesh import microstructure_mesh_diff, sdf_struct  # noqa: F401  (sdf_struct: re-exported)
 from deepsdf_amd.spline import BSplineField
 from deepsdf_amd.surface import SurfaceMesh
+from deepsdf_amd.tetmesh import tetrahedralize
 
 STRETCH = (2.0, 1.0, 1.0)      # the reference's "freeform deformation": x is doubled
 CLIP = 1.0                     # its outlier rule: Jacobian entries outside [-1, 1] are zeroed
@@ -46,7 +48,7 @@ class DeepSDFMesh:
         field = BSplineField(degrees, knots, np.zeros((n_initial, self.latent.shape[1])))      # zero codes at every control point
         field.uniform_refine(self.options["refinement"])
         self.latent_vec_interpolation = field
-        self.surface_mesh = self.jacobian = self.diff = None
+        self.surface_mesh = self.jacobian = self.diff = self.volume_mesh = None
         self.logger = logging.getLogger(__name__)
         self.logger.debug(f"Initialied latent vector with {field.control_mesh_resolutions} control points")
 
@@ -105,11 +107,35 @@ class DeepSDFMesh:
         """d volume / d control points [ncp, L] on the device."""
         return self._mesh().volume_gradient()
 
+    def generate_volume_mesh(self, t_clamp=0.0):
+        """The tetrahedral mesh of the solid the surface bounds, after generate_surface_mesh: the capped grid the surface came from
+        (``diff.grid``) meshed at the voxel size, in the surface's coordinates ((v - voxel_size) / 2 in float64, x stretched by 2);
+        only the largest solid component when ``remove_orphans``.  Sets and returns ``volume_mesh`` (a TetMesh); its axis-class
+        boundary vertices are the surface's vertices bit for bit.  t_clamp: deepsdf_amd.tetmesh.tetrahedralize."""
+        self._mesh()
+        vs = self.diff.voxel_size
+        m = tetrahedralize(self.diff.grid, 0.0, vs, t_clamp=t_clamp, keep_largest=bool(self.options["remove_orphans"]),
+                           return_edges=True)
+        dev = m.verts.device
+        verts = (m.verts.double() - torch.tensor(vs, dtype=torch.float64, device=dev)) / 2      # microstructure_mesh_diff's transform
+        m.verts = verts * torch.tensor(STRETCH, dtype=torch.float64, device=dev)                 # SurfaceMesh.from_diff's stretch
+        self.volume_mesh = m
+        return m
+
+    def export_mfem_mesh(self, filename):
+        """Write ``volume_mesh`` as an MFEM mesh v1.0 file with the reference's boundary attributes (1: x = 0, 2: the top in z,
+        3: the rest; TetMesh.boundary_attributes)."""
+        if self.volume_mesh is None:
+            raise RuntimeError("call generate_volume_mesh() first")
+        self.volume_mesh.write_mfem(filename)
+
     def tetrahedralize_surface(self):
+        """Not implemented (tetgenpy): generate_volume_mesh meshes the solid from the grid instead."""
         raise NotImplementedError("tetrahedralize_surface needs tetgenpy, which this package does not carry: only the surface stage "
                                   "(normals, volume, shape derivative) is implemented")
 
     def export_volume_mesh(self, filename, show_mesh=False, export_abaqus=False):
+        """Not implemented (gustaf): export_mfem_mesh writes generate_volume_mesh's mesh."""
         raise NotImplementedError("export_volume_mesh needs a tetrahedral mesh (tetgenpy) and gustaf, which this package does not "
                                   "carry")
 

@@ -7,13 +7,18 @@ domain is tiled with mirrored unit cells, the borders are capped and the zero le
 deep_sdf.mesh.create_mesh_microstructure: rows, decode, caps and marching cubes on the GPU.
 
     python create_microstructure.py -e <experiment_dir> -c latest --tiling 4 4 2 --codes 0 3 1 2 5 5 7 8 \\
-        [--degrees 1 1 1] [--resolution 256] [--cap x1=1:0.1 z0=-1:0] [-b 32] [--jacobian out.npz] -o out.ply
+        [--degrees 1 1 1] [--resolution 256] [--cap x1=1:0.1 z0=-1:0] [-b 32] [--jacobian out.npz] \\
+        [--tetmesh out.mesh [--t-clamp 0.05]] -o out.ply
 
 With degrees p the number of codes must be a product nx * ny * nz of control points per axis, each > p; the split is taken
 from --control-points, or for 8 codes 2 x 2 x 2.  Knot vectors are uniform and clamped.
 
 --jacobian FILE.npz also writes the mesh with its derivative with respect to the control points: verts [V, 3], faces [F, 3],
 jac [V, ncp, L] = d verts[v, axis[v]] / d control points, axis [V] (the other two coordinates of a vertex do not depend on them).
+
+--tetmesh FILE.mesh also writes the solid as a tetrahedral mesh in MFEM mesh v1.0 format, in the PLY's coordinates
+(deep_sdf.mesh.tetrahedralize of the same capped grid, which is decoded once for both files); --t-clamp bounds how thin a cut
+element can get.  --jacobian decodes the structure once more (microstructure_mesh_diff keeps the raw and the capped grid).
 """
 import argparse
 
@@ -48,7 +53,7 @@ def parse_caps(items):
 
 
 def main(experiment_directory, checkpoint, tiling, codes, out, degrees=(1, 1, 1), control_points=None, resolution=256,
-         caps=None, max_batch=32, jacobian=None, block=None, lipschitz=1.0):
+         caps=None, max_batch=32, jacobian=None, block=None, lipschitz=1.0, tetmesh=None, t_clamp=0.0):
     if not torch.cuda.is_available():
         raise RuntimeError("create_microstructure.py (deepsdf_amd) needs an AMD GPU: the HIP path has no CPU fallback")
     decoder = ws.load_trained_model(experiment_directory, checkpoint)
@@ -66,9 +71,15 @@ def main(experiment_directory, checkpoint, tiling, codes, out, degrees=(1, 1, 1)
     cp = torch.stack([latent[c].detach().reshape(-1).cpu() for c in codes]).numpy()
     field = BSplineField(degrees, [uniform_clamped_knots(n, p) for n, p in zip(control_points, degrees)], cp)
     name = out[:-4] if out.endswith(".ply") else out
-    with deep_sdf.mesh.sparse_grid(block, lipschitz):
-        deep_sdf.mesh.create_mesh_microstructure(list(tiling), decoder, field, name, N=resolution, max_batch=int(max_batch ** 3),
-                                                 cap_border_dict=caps, save_ply_file=True)
+    if tetmesh:                                   # one decode of the structure for the surface and the volume mesh
+        m = deep_sdf.mesh.microstructure_tetmesh(list(tiling), decoder, field, resolution, int(max_batch ** 3), caps, t_clamp=t_clamp,
+                                                 block=block, lipschitz=lipschitz, ply_filename=name + ".ply")
+        m.write_mfem(tetmesh)
+        print(f"wrote {tetmesh}: {m.n_verts} vertices, {m.n_tets} elements, {m.n_bfaces} boundary triangles")
+    else:
+        with deep_sdf.mesh.sparse_grid(block, lipschitz):
+            deep_sdf.mesh.create_mesh_microstructure(list(tiling), decoder, field, name, N=resolution, max_batch=int(max_batch ** 3),
+                                                     cap_border_dict=caps, save_ply_file=True)
     print(f"wrote {name}.ply")
     if jacobian:
         d = deep_sdf.mesh.microstructure_mesh_diff(list(tiling), decoder, field, resolution, int(max_batch ** 3), caps, block=block,
@@ -90,7 +101,12 @@ def build_parser():
     parser.add_argument("--cap", type=str, nargs="*", default=None, help="<face>=<cap>:<measure>, e.g. x1=1:0.1; in order")
     parser.add_argument("--max_batch", "-b", type=int, default=32, help="decode chunk = max_batch^3 grid points")
     parser.add_argument("--jacobian", type=str, default=None, metavar="FILE.npz",
-                        help="also write verts, faces, jac [V, ncp, L] (d vertex / d control points along axis) and axis")
+                        help="also write verts, faces, jac [V, ncp, L] (d vertex / d control points along axis) and axis; decodes the "
+                             "structure a second time")
+    parser.add_argument("--tetmesh", type=str, default=None, metavar="FILE.mesh",
+                        help="also write the solid as a tetrahedral MFEM mesh v1.0 file, in the PLY's coordinates (from the PLY's grid: no "
+                             "second decode)")
+    parser.add_argument("--t-clamp", type=float, default=0.0, help="clamp of the edge parameter in [0, 0.5) (--tetmesh)")
     parser.add_argument("--output", "-o", type=str, required=True)
     deep_sdf.mesh.add_sparse_args(parser)
     return parser
@@ -99,4 +115,4 @@ def build_parser():
 if __name__ == "__main__":
     args = build_parser().parse_args()
     main(args.experiment_directory, args.checkpoint, args.tiling, args.codes, args.output, args.degrees, args.control_points,
-         args.resolution, parse_caps(args.cap), args.max_batch, args.jacobian, args.block, args.lipschitz)
+         args.resolution, parse_caps(args.cap), args.max_batch, args.jacobian, args.block, args.lipschitz, args.tetmesh, args.t_clamp)

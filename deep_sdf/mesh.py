@@ -5,3 +5,4 @@ from deepsdf_amd.mesh import convert_sdf_samples_to_ply, create_mesh  # noqa: F4
 from deepsdf_amd.mesh import (CapBorderDict, CapType, create_mesh_microstructure, create_mesh_microstructure_diff,  # noqa: F401
                               location_lookup, microstructure_mesh_diff, microstructure_sdf_grid, sdf_struct, sparse_grid)
 from deepsdf_amd.mesh import add_sparse_args  # noqa: F401
+from deepsdf_amd.mesh import TetMesh, microstructure_tetmesh, solid_components, tetrahedralize  # noqa: F401

@@ -177,6 +177,11 @@ PROTOTYPES = {
     "dsdf_sg_coords": [_I32, _I32, _I32, C.POINTER(_F), C.POINTER(_F), _P, _I64, _P, _P],
     "dsdf_sg_scatter": [_P, _I64, _P, _P, _I64, _P],
     "dsdf_sg_caps_at": [C.POINTER(DsdfMsGrid), _P, _I64, C.POINTER(DsdfMsCap), _I32, _P, _P],
+    "dsdf_tet_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_SZ)],
+    "dsdf_tet_count": [_P, _I32, _I32, _I32, _F, _P, _P, _SZ, _P],
+    "dsdf_tet_emit": [_P, _I32, _I32, _I32, _F, C.POINTER(_F), C.POINTER(_F), _F, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                      _P],
+    "dsdf_tet_components": [_P, _I32, _I32, _I32, _F, _P, _P, C.POINTER(_I32), _P, _SZ, _P],
 }
 
 _lib = None

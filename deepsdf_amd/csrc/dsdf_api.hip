@@ -29,6 +29,7 @@
 #include "pointset.hpp"
 #include "meshtopo.hpp"
 #include "sparsegrid.hpp"
+#include "tetmesh.hpp"
 
 using namespace dsdf;
 
@@ -3069,6 +3070,139 @@ int dsdf_sg_caps_at(const DsdfMsGrid* grid, const int64_t* indices, int64_t n, c
   if (!indices || !sdf) return fail(DSDF_E_INVALID, "sparse grid caps: NULL indices or sdf");
   hipLaunchKernelGGL(sg_caps_kernel, sg_launch(n), dim3(SG_BLOCK), 0, (hipStream_t)stream, c, indices, n, sdf);
   LAUNCH_OK("sg_caps_kernel");
+  return 0;
+}
+
+// ---- tetrahedral volume mesh (tetmesh.hpp) ---------------------------------------------------------------------
+namespace {
+struct TetPlan {
+  int64_t npts, nblocks;
+  size_t rec, ne, nb, vbase, bcount[3], boff[3], gf, flags, total;
+};
+
+int tet_plan(int32_t nx, int32_t ny, int32_t nz, TetPlan* P, WsTable* rec = nullptr) {
+  if (nx < 2 || ny < 2 || nz < 2 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
+    return fail(DSDF_E_INVALID, "tet mesh: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
+  P->npts = (int64_t)nx * ny * nz;
+  P->nblocks = (P->npts + TET_BLOCK - 1) / TET_BLOCK;
+  WsCarver c(rec);
+  P->rec = c.take("tet_rec", -1, (size_t)P->npts);
+  P->ne = c.take("tet_ne", -1, (size_t)P->npts);
+  P->nb = c.take("tet_nb", -1, (size_t)P->npts);
+  P->vbase = c.take("tet_vbase", -1, (size_t)P->npts * 4);
+  static const char* const cnt_name[3] = {"tet_bv", "tet_bt", "tet_bb"};
+  static const char* const off_name[3] = {"tet_ov", "tet_ot", "tet_ob"};
+  for (int s = 0; s < 3; ++s) P->bcount[s] = c.take(cnt_name[s], -1, (size_t)P->nblocks * 4);
+  for (int s = 0; s < 3; ++s) P->boff[s] = c.take(off_name[s], -1, (size_t)(P->nblocks + 1) * 8);
+  P->gf = c.take("tet_cc_gf", -1, (size_t)P->npts * 4);
+  P->flags = c.take("tet_cc_flags", -1, (size_t)TET_CC_GROUP * 4);
+  P->total = c.finish(c.o);
+  return 0;
+}
+
+int tet_setup(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, void* ws, size_t ws_bytes, McGrid* g, TetWs* w,
+              TetPlan* P) {
+  TRY(tet_plan(nx, ny, nz, P, &t_last_plan));
+  if (!sdf || !ws) return fail(DSDF_E_INVALID, "tet mesh: NULL sdf or workspace");
+  if (ws_bytes < P->total) return fail(DSDF_E_WORKSPACE, "tet mesh: workspace %zu < %zu bytes", ws_bytes, P->total);
+  g->sdf = sdf; g->nx = nx; g->ny = ny; g->nz = nz; g->level = level; g->npts = P->npts;
+  char* b = (char*)ws;
+  w->rec = (uint8_t*)(b + P->rec); w->ne = (uint8_t*)(b + P->ne); w->nb = (uint8_t*)(b + P->nb);
+  w->vbase = (int32_t*)(b + P->vbase);
+  for (int s = 0; s < 3; ++s) { w->bcount[s] = (int32_t*)(b + P->bcount[s]); w->boff[s] = (int64_t*)(b + P->boff[s]); }
+  w->nblocks = P->nblocks;
+  return 0;
+}
+}  // namespace
+
+int dsdf_tet_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes) {
+  TetPlan P;
+  TRY(tet_plan(nx, ny, nz, &P, &t_last_plan));
+  if (!bytes) return fail(DSDF_E_INVALID, "NULL bytes");
+  *bytes = P.total;
+  return 0;
+}
+
+int dsdf_tet_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* totals, void* ws, size_t ws_bytes,
+                   void* stream) {
+  McGrid g; TetWs w; TetPlan P;
+  TRY(tet_setup(sdf, nx, ny, nz, level, ws, ws_bytes, &g, &w, &P));
+  if (!totals) return fail(DSDF_E_INVALID, "tet mesh: NULL totals");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(tet_classify_kernel, dim3((unsigned)P.nblocks), dim3(TET_BLOCK), 0, st, g, w);
+  LAUNCH_OK("tet_classify_kernel");
+  hipLaunchKernelGGL(tet_scan_kernel, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w, totals);
+  LAUNCH_OK("tet_scan_kernel");
+  return 0;
+}
+
+int dsdf_tet_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing, const float* origin,
+                  float t_clamp, int64_t n_verts, int64_t n_tets, int64_t n_bfaces, float* verts, int32_t* tets, int32_t* bfaces,
+                  int8_t* bface_kind, int64_t* vert_point, int32_t* vert_class, void* ws, size_t ws_bytes, void* stream) {
+  McGrid g; TetWs w; TetPlan P;
+  TRY(tet_setup(sdf, nx, ny, nz, level, ws, ws_bytes, &g, &w, &P));
+  if (!(t_clamp >= 0.f && t_clamp < 0.5f)) return fail(DSDF_E_INVALID, "tet mesh: t_clamp %g outside [0, 0.5)", (double)t_clamp);
+  if (n_verts < 0 || n_tets < 0 || n_bfaces < 0 || n_verts > INT32_MAX || n_tets > INT32_MAX || n_bfaces > INT32_MAX)
+    return fail(DSDF_E_INVALID, "tet mesh: %lld vertices / %lld elements / %lld boundary triangles (int32 indices hold at most %d)",
+                (long long)n_verts, (long long)n_tets, (long long)n_bfaces, INT32_MAX);
+  if (!spacing || !origin) return fail(DSDF_E_INVALID, "tet mesh: NULL spacing or origin");
+  if ((n_verts > 0 && !verts) || (n_tets > 0 && !tets) || (n_bfaces > 0 && (!bfaces || !bface_kind)))
+    return fail(DSDF_E_INVALID, "tet mesh: NULL verts, tets, bfaces or bface_kind");
+  if (((uintptr_t)tets & 15) != 0) return fail(DSDF_E_INVALID, "tet mesh: tets not 16-byte aligned (an element is stored as one int4)");
+  if (n_verts == 0 && n_tets == 0 && n_bfaces == 0) return 0;
+  TetOut o;
+  for (int a = 0; a < 3; ++a) { o.spacing[a] = spacing[a]; o.origin[a] = origin[a]; }
+  o.t_clamp = t_clamp;
+  o.verts = verts; o.tets = tets; o.bfaces = bfaces; o.bface_kind = bface_kind; o.vert_point = vert_point; o.vert_class = vert_class;
+  o.nv = n_verts; o.nt = n_tets; o.nb = n_bfaces;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(tet_vertex_kernel, dim3((unsigned)P.nblocks), dim3(TET_BLOCK), 0, st, g, w, o);
+  LAUNCH_OK("tet_vertex_kernel");
+  if (n_tets > 0 || n_bfaces > 0) {
+    hipLaunchKernelGGL(tet_element_kernel, dim3((unsigned)P.nblocks), dim3(TET_BLOCK), 0, st, g, w, o);
+    LAUNCH_OK("tet_element_kernel");
+  }
+  return 0;
+}
+
+// Waits for the stream: the change flags of every TET_CC_GROUP rounds are read on the host (as dsdf_mt_components does).
+int dsdf_tet_components(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int32_t* label, int32_t* size,
+                        int32_t* n_rounds, void* ws, size_t ws_bytes, void* stream) {
+  McGrid g; TetWs w; TetPlan P;
+  if (n_rounds) *n_rounds = 0;
+  TRY(tet_setup(sdf, nx, ny, nz, level, ws, ws_bytes, &g, &w, &P));
+  if (!label) return fail(DSDF_E_INVALID, "tet mesh components: NULL label");
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* gf = (int32_t*)((char*)ws + P.gf);
+  int32_t* flags = (int32_t*)((char*)ws + P.flags);
+  const dim3 grid((unsigned)P.nblocks);
+  hipLaunchKernelGGL(tet_cc_init_kernel, grid, dim3(TET_BLOCK), 0, st, g, label);
+  LAUNCH_OK("tet_cc_init_kernel");
+  int rounds = 0;
+  for (bool done = false; !done;) {                          // no cap: f only decreases, so a round without a change comes
+    hipLaunchKernelGGL(mt_cc_flags_kernel, dim3(1), dim3(MT_BLOCK), 0, st, flags);
+    LAUNCH_OK("mt_cc_flags_kernel");
+    for (int r = 0; r < TET_CC_GROUP; ++r) {
+      hipLaunchKernelGGL(tet_cc_grand_kernel, grid, dim3(TET_BLOCK), 0, st, (const int32_t*)label, P.npts, gf);
+      LAUNCH_OK("tet_cc_grand_kernel");
+      hipLaunchKernelGGL(tet_cc_hook_kernel, grid, dim3(TET_BLOCK), 0, st, g, label, (const int32_t*)gf, flags + r);
+      LAUNCH_OK("tet_cc_hook_kernel");
+    }
+    int32_t host[TET_CC_GROUP];
+    HIP_OK(hipMemcpyAsync(host, flags, sizeof(host), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int r = 0; r < TET_CC_GROUP && !done; ++r) {
+      ++rounds;
+      done = host[r] == 0;
+    }
+  }
+  if (n_rounds) *n_rounds = rounds;
+  if (size) {
+    hipLaunchKernelGGL(tet_cc_zero_kernel, grid, dim3(TET_BLOCK), 0, st, size, P.npts);
+    LAUNCH_OK("tet_cc_zero_kernel");
+    hipLaunchKernelGGL(tet_cc_size_kernel, grid, dim3(TET_BLOCK), 0, st, (const int32_t*)label, P.npts, size);
+    LAUNCH_OK("tet_cc_size_kernel");
+  }
   return 0;
 }
 

@@ -12,6 +12,8 @@ convert_sdf_samples_to_ply :86-155) with every step on the GPU.
                             (create_mesh_microstructure :157-342): rows and caps by csrc/msgrid.hpp around the same decode
     diff   microstructure_mesh_diff / create_mesh_microstructure_diff (:346-454): d vertices / d control points assembled in closed
                             form (csrc/msdiff.hpp) from one input-gradient pass over the band of grid points that carry a vertex
+    volume tetrahedralize / solid_components / TetMesh (deepsdf_amd/tetmesh.py, re-exported here): the solid {sdf < level} of the
+                            same grid as a conforming tetrahedral mesh with its boundary triangles (csrc/tetmesh.hpp)
 
     sparse follow_surface   surface following on blocks of the same dense grid (csrc/sparsegrid.hpp): the coarse lattice
                             is decoded, blocks near the surface are seeded and grown across mixed-sign faces, only their points
@@ -722,8 +724,10 @@ class MicrostructureMeshDiff:
     verts [V, 3] float64 and faces [F, 3] int32 (device) are create_mesh_microstructure's; edge_point [V] int64 / edge_axis [V] int32
     name the padded-grid edge of every vertex.  Only coordinate edge_axis[v] of vertex v depends on the control points."""
 
-    def __init__(self, verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale):
+    def __init__(self, verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale,
+                 voxel_size=None):
         self.verts, self.faces, self.edge_point, self.edge_axis = verts, faces, edge_point, edge_axis
+        self.voxel_size = None if voxel_size is None else [float(v) for v in voxel_size]      # the grid's spacing before (v - vs) / 2
         self.grid, self.band, self.band_of = grid, band, band_of
         self.G, self.weights, self.base, self.mask = G, weights, base, mask
         self.n_control_points, self.latent_size = int(field.control_points.shape[0]), int(field.latent_size)
@@ -860,7 +864,8 @@ def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_b
         flat_raw, flat = raw.view(-1), grid.view(-1)
         mask = ((base >= 0) & (flat[band] == flat_raw[band])).to(torch.uint8)
     scale = [float(np.float32(v / 2)) for v in voxel_size]
-    return MicrostructureMeshDiff(verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale)
+    return MicrostructureMeshDiff(verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale,
+                                  voxel_size)
 
 
 def create_mesh_microstructure_diff(tiling, decoder, latent_vec_interpolation, N=256, max_batch=32 ** 3, offset=None, scale=None,
@@ -880,3 +885,24 @@ def create_mesh_microstructure_diff(tiling, decoder, latent_vec_interpolation, N
     d = microstructure_mesh_diff(tiling, decoder, latent_vec_interpolation, N, max_batch, cap_border_dict, device, block=block,
                                  lipschitz=lipschitz)
     return d.verts.cpu().numpy(), d.faces.cpu().numpy(), d.jacobian(dense=True).cpu().numpy()
+
+
+# ---- volume meshes ----------------------------------------------------------------------------------------------------------------
+def microstructure_tetmesh(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None, *, t_clamp=0.0,
+                           keep_largest=False, block=None, lipschitz=1.0, ply_filename=None):
+    """The solid of the tiled, capped structure as a TetMesh (tetmesh.tetrahedralize of the grid create_mesh_microstructure meshes),
+    in the coordinates of its PLY file: voxel origin + index * voxel size.  Its axis-class vertices are the PLY's vertices.
+
+    ply_filename: also write the surface of the SAME grid there, byte for byte the file create_mesh_microstructure(...,
+    save_ply_file=True) writes: the structure is decoded once for both meshes."""
+    tiling, n = _int_triple(tiling, "Tiling"), _int_triple(N, "Number of grid points")
+    decoder.eval()
+    _, voxel_size = _ms_grid(tiling, n)
+    voxel_origin = [-1 - v for v in voxel_size]
+    grid = microstructure_sdf_grid(tiling, decoder, field, n, max_batch, cap_border_dict, device, block=block, lipschitz=lipschitz)
+    if ply_filename is not None:
+        convert_sdf_samples_to_ply(grid, voxel_origin, voxel_size, ply_filename)
+    return tetrahedralize(grid, 0.0, voxel_size, voxel_origin, t_clamp=t_clamp, keep_largest=keep_largest)
+
+
+from .tetmesh import TetMesh, solid_components, tetrahedralize  # noqa: E402,F401  (re-exports; tetmesh.py does not import this module)

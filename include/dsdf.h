@@ -641,6 +641,66 @@ int dsdf_sg_scatter(const int64_t* indices, int64_t n, const float* values, floa
 int dsdf_sg_caps_at(const DsdfMsGrid* grid, const int64_t* indices, int64_t n, const DsdfMsCap* caps, int32_t n_caps, float* sdf,
                     void* stream);
 
+/* ---- tetrahedral volume mesh of the solid {sdf < level} (csrc/tetmesh.hpp; numpy restatement: tests/tet_numpy.py) ------------
+ * The grid, level, spacing and origin are dsdf_mc_*'s: sdf [nx][ny][nz] fp32, z fastest, 2 <= n <= 1024 per axis, a grid point
+ * is inside iff v < level (strictly); spacing > 0.  Additions only: DSDF_ABI_VERSION is unchanged.
+ *
+ * Kuhn tetrahedra.  Every cell is cut into six tetrahedra around its diagonal (0,0,0)-(1,1,1): for the permutation pi of the axes
+ *   (the six of them in lexicographic order) the corners are q0 = cell origin, q1 = q0 + e_pi0, q2 = q1 + e_pi1, q3 = q2 + e_pi2,
+ *   and det(q1 - q0, q2 - q0, q3 - q0) = sign(pi): the orientation of everything emitted follows from the permutation's parity
+ *   and from integer relabellings, never from a floating-point test.  The triangulation is translation invariant and conforming
+ *   across cells.
+ * Edges.  A tetrahedron edge is (p, c): its lower grid point p and a class c in 1..7 with direction d = (c & 1, (c >> 1) & 1,
+ *   (c >> 2) & 1) -- three axis classes (1, 2, 4), three face diagonals, one body diagonal.  It crosses iff exactly one end is inside.
+ * Vertices, in output order: for every grid point in linear order the grid point itself if it is inside (class 0), at
+ *   origin + idx * spacing, then its crossing edges in increasing c, at t = (level - v_p) / (v_q - v_p): coordinate b is
+ *   origin[b] + (idx[b] + t) * spacing[b] where d[b] = 1 and origin[b] + idx[b] * spacing[b] elsewhere, fp32, every operation
+ *   rounded on its own, in dsdf_mc_emit's sequence: the class-1/2/4 vertices are, in order and bit for bit, dsdf_mc_emit's vertices.
+ *   t_clamp = tau in [0, 0.5): when tau > 0, t is clamped to [tau, 1 - tau] (1 - tau in fp32) before it is used; tau = 0 does not
+ *   touch t.  The clamp bounds how thin a cut element can get and moves the surface by at most tau of an edge.
+ * Elements of a Kuhn tetrahedron by its inside corners (corner numbers in increasing order within "inside" and within "outside";
+ *   XY is the vertex on edge XY): none: nothing; all four: (q0, q1, q2, q3); one, A: (A, AB, AC, AD); three, D outside: the prism
+ *   (A, B, C | AD, BD, CD); two, A and B: the prism (A, AC, AD | B, BC, BD).  A prism (a0, a1, a2 | b0, b1, b2) with vertical edges
+ *   ai-bi is relabelled -- the triangles exchanged if the lowest of its six output ids is a b, then both rotated -- so that a0 is that
+ *   lowest id; it gives (a0, b0, b1, b2) and then, if the lowest id of the quadrilateral (a1, a2, b2, b1) is a1 or b2, (a0, a1, a2, b2)
+ *   and (a0, a1, b2, b1), else (a0, a1, a2, b1) and (a0, a2, b2, b1): on every quadrilateral the diagonal leaves from the lowest id,
+ *   and ids are a global total order, so neighbours agree.  Every element is stored positively oriented (its last two ids exchanged
+ *   where the parity says it is negative).  At most 3 elements per Kuhn tetrahedron, 18 per cell.
+ * Boundary triangles, outward: the cut faces -- one inside corner (AB, AC, AD), three (AD, BD, CD), two the quadrilateral
+ *   (AC, AD, BD, BC), rotated to its lowest id and cut from there -- which face increasing sdf as dsdf_mc_emit's do, kind 0; and
+ *   the inside part of every Kuhn face lying in one of the six outer planes of the grid (walk round the outward-ordered face, keep
+ *   inside corners and crossing vertices; a quadrilateral is cut as above), kind 1..6 = -x, +x, -y, +y, -z, +z.
+ * Order, without atomics (two runs give identical bytes): elements by cell (linear index of its lower corner), permutation, then
+ *   the order above; boundary triangles by cell, permutation, cut faces, then the low-plane face (q0, q1, q2), then the high-plane
+ *   face (q1, q2, q3).
+ * Degenerate input: a value equal to level is outside, so t can be exactly 0 or 1; the elements touching that point then have zero
+ *   volume and are still emitted (the topology stays conforming).  With tau > 0 there are none.
+ * Use: dsdf_tet_count (writes {n_verts, n_tets, n_bfaces} as int64 to device memory), read the totals, allocate, dsdf_tet_emit with
+ * the SAME grid, level and workspace.  Totals above INT32_MAX and a t_clamp outside [0, 0.5) are refused (DSDF_E_INVALID) before
+ * anything is launched; nothing is written past n_verts / n_tets / n_bfaces entries.  The workspace (about 11 bytes per grid point,
+ * regions tet_* of dsdf_debug_ws_regions) also serves dsdf_tet_components, which overwrites none of what dsdf_tet_count left. */
+int dsdf_tet_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, size_t* bytes);                    /* [host] */
+int dsdf_tet_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int64_t* totals /*[3], device*/, void* ws,
+                   size_t ws_bytes, void* stream);
+/* verts [n_verts][3] fp32, tets [n_tets][4] int32, bfaces [n_bfaces][3] int32, bface_kind [n_bfaces] int8; vert_point [n_verts]
+ * int64 / vert_class [n_verts] int32 (each may be NULL): the grid point p and the class c (0: a grid vertex) of every vertex id;
+ * spacing, origin [host] 3 floats each.  tets must be 16-byte aligned (an element is stored as one 16-byte vector; a misaligned
+ * pointer is refused with DSDF_E_INVALID); the other arrays need their element's alignment only.
+ * n_verts / n_tets / n_bfaces are the counted totals, or fewer to receive only the first entries.  The INT32_MAX check is made on
+ * these arguments: the library cannot read the device totals on the host.  A caller who passes FEWER than the counted totals must
+ * have checked that the counted totals themselves fit int32 -- beyond that the ids wrap and the entries written are meaningless
+ * (still none outside the buffers).  deepsdf_amd.tetmesh.tetrahedralize always passes the counted totals. */
+int dsdf_tet_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, const float* spacing, const float* origin,
+                  float t_clamp, int64_t n_verts, int64_t n_tets, int64_t n_bfaces, float* verts, int32_t* tets, int32_t* bfaces,
+                  int8_t* bface_kind, int64_t* vert_point, int32_t* vert_class, void* ws, size_t ws_bytes, void* stream);
+/* Connected components of the solid: two inside grid points joined by a Kuhn edge (p, p + d(c)) are connected (14 neighbours; two
+ * inside corners of a Kuhn tetrahedron are always joined by one, and every element holds an inside corner, so these are exactly the
+ * components of the mesh).  dsdf_mt_components' conventions: label [npts] int32, the lowest linear index of the point's component,
+ * -1 outside; size [npts] int32 (may be NULL), the component's inside-point count at its root, 0 elsewhere; *n_rounds [host] the
+ * hooking rounds run.  The result is unique; waits for the stream. */
+int dsdf_tet_components(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int32_t* label, int32_t* size,
+                        int32_t* n_rounds /*[host]*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */
 int dsdf_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
