@@ -89,6 +89,13 @@ class DsdfWsRegion(C.Structure):      # debug only: one row of dsdf_debug_ws_reg
     _fields_ = [("name", C.c_char * 24), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
 
+class DsdfPackedLayout(C.Structure):  # debug only: dsdf_debug_packed_layout
+    _fields_ = [("total", C.c_int64), ("scale_off", C.c_int64)] + \
+               [(k, C.c_int64 * MAX_LAYERS) for k in ("w_off", "wt_off", "wf_off", "wtf_off", "wfb_off", "ws_off", "wts_off",
+                                                      "ws_plane", "wts_plane")] + \
+               [(k, C.c_int32 * MAX_LAYERS) for k in ("ldw", "ldwt", "uf", "utf")]
+
+
 WS_MAX_REGIONS = 192
 WS_MAX_REDZONE = 4096
 WS_PLAN_TRAIN, WS_PLAN_DECODE, WS_PLAN_DECODE_LATENT = 0, 1, 2
@@ -145,6 +152,7 @@ PROTOTYPES = {
     "dsdf_debug_ws_redzone": [_I32],
     "dsdf_debug_ws_regions": [C.POINTER(DsdfWsRegion), _I32, C.POINTER(_I32), C.POINTER(_SZ)],
     "dsdf_debug_ws_plan": [_NET, _I64, _I64, _I32, _I32, _I32, _I32],
+    "dsdf_debug_packed_layout": [_NET, C.POINTER(DsdfPackedLayout)],
     "dsdf_msdf_query": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P],
     "dsdf_module_input_grad": [_NET, _P, _P, _P, _I64, _P, _I64, _P, _SZ, _P],
     "dsdf_mc_edges": [_I32, _I32, _I32, _I64, _P, _P, _P, _SZ, _P],

@@ -1547,6 +1547,24 @@ int dsdf_debug_ws_plan(const DsdfNet* net, int64_t n_points, int64_t n_segments,
   }
 }
 
+int dsdf_debug_packed_layout(const DsdfNet* net, DsdfPackedLayout* out) {
+  TRY(validate(net));
+  if (!out) return fail(DSDF_E_INVALID, "out is NULL");
+  const Packed pk = packed_layout(net);
+  out->total = pk.total; out->scale_off = pk.scale_off;
+  for (int l = 0; l < DSDF_MAX_LAYERS; ++l) {
+    const bool in = l < net->n_layers;
+    out->w_off[l] = in ? pk.w_off[l] : -1;     out->wt_off[l] = in ? pk.wt_off[l] : -1;
+    out->wf_off[l] = in ? pk.wf_off[l] : -1;   out->wtf_off[l] = in ? pk.wtf_off[l] : -1;
+    out->wfb_off[l] = in ? pk.wfb_off[l] : -1;
+    out->ws_off[l] = in ? pk.ws_off[l] : -1;   out->wts_off[l] = in ? pk.wts_off[l] : -1;
+    out->ws_plane[l] = in ? pk.ws_plane[l] : 0; out->wts_plane[l] = in ? pk.wts_plane[l] : 0;
+    out->ldw[l] = in ? pk.ldw[l] : 0; out->ldwt[l] = in ? pk.ldwt[l] : 0;
+    out->uf[l] = in ? pk.uf[l] : 0;   out->utf[l] = in ? pk.utf[l] : 0;
+  }
+  return 0;
+}
+
 int dsdf_module_forward(const DsdfNet* net, const float* packed, const float* params, const float* input,
                         int64_t ld_in, int64_t n, int32_t training, const uint32_t* dropout_key, float* sdf_out,
                         void* ws, size_t ws_bytes, void* stream) {

@@ -171,6 +171,32 @@ int dsdf_debug_ws_regions(DsdfWsRegion* table, int32_t capacity, int32_t* n_regi
 int dsdf_debug_ws_plan(const DsdfNet* net, int64_t n_points, int64_t n_segments, int32_t kind, int32_t segmode, int32_t n_buckets,
                        int32_t frows);
 
+/* ---- debug only: where everything lies inside the packed-weight buffer ----------------------------------------------
+ * dsdf_debug_packed_layout [host] the layout dsdf_materialize_weights / dsdf_adam_step / dsdf_train_step write `packed` with, so
+ * that a TEST can state what every byte of the buffer must be.  No kernel takes part; production callers never call it.
+ * Offsets are in floats from the start of `packed`; entries of layers >= n_layers are -1 (offsets) or 0.  Per layer l
+ * (out x in = out_dim[l] x in_dim[l]; W = v * scale[row], scale = g / ||v_row|| or 1):
+ *   w_off / ldw     W   [out][ldw]  row-major, ldw  = in  rounded up to 32
+ *   wt_off / ldwt   W^T [in][ldwt]  row-major, ldwt = out rounded up to 32           (not written for the last layer)
+ *   wf_off / uf     fragment order of B = W   (n = out, k = in ), uf  k-units of 16 per 32-row n-tile:
+ *   wtf_off / utf   fragment order of B = W^T (n = in,  k = out), utf k-units:
+ *                     Bf[((nt * U + u) * 2 + i) * 256 + lane * 4 + e] = B[32 nt + (lane & 31)][16 u + 8 (lane >> 5) + 4 i + e]
+ *   wfb_off         fwd_bf16: bf16(W), round to nearest even, 32 k-unit slots of 512 bf16 per n-tile, unit u in slot
+ *                     16 ((u >> 1) & 1) + 2 (u >> 2) + (u & 1); element ((nt * 32 + slot) * 64 + lane) * 8 + j (j = 4 i + e)
+ *   ws_off / ws_plane, wts_off / wts_plane   gemm_split: W / W^T as three bf16 planes of `plane` bf16 elements each (x = h + m + l,
+ *                     every term the top 16 bits of what is left), element ((nt * U + u) * 64 + lane) * 8 + j inside a plane
+ * The fragment copies exist for every layer but the last; entries of an absent copy (last layer, flag not set) still carry the
+ * offset the layout reserves for them.  Everything the kernels never write (leading-dimension padding, rows and k-units past the
+ * matrix, n-tiles of the rounding to 4, unused slots) stays as the caller initialised it: the kernels rely on zeros there.
+ * scale_off: one float per output row of every layer, layers in order.  total == dsdf_packed_floats. */
+typedef struct DsdfPackedLayout {
+  int64_t total, scale_off;
+  int64_t w_off[DSDF_MAX_LAYERS], wt_off[DSDF_MAX_LAYERS], wf_off[DSDF_MAX_LAYERS], wtf_off[DSDF_MAX_LAYERS], wfb_off[DSDF_MAX_LAYERS];
+  int64_t ws_off[DSDF_MAX_LAYERS], wts_off[DSDF_MAX_LAYERS], ws_plane[DSDF_MAX_LAYERS], wts_plane[DSDF_MAX_LAYERS];
+  int32_t ldw[DSDF_MAX_LAYERS], ldwt[DSDF_MAX_LAYERS], uf[DSDF_MAX_LAYERS], utf[DSDF_MAX_LAYERS];
+} DsdfPackedLayout;
+int dsdf_debug_packed_layout(const DsdfNet* net, DsdfPackedLayout* out);
+
 /* [host] 1 if this net's training step can run its backward in phases (the fused kernels take it; in this process: the
  * DSDF_NO_FUSED switch counts), 0 if not (a caller then exchanges the gradient in ONE piece), < 0 for an invalid net. */
 int dsdf_dw_phase_supported(const DsdfNet* net);

@@ -591,6 +591,17 @@ def test_debug_entries_check_their_arguments(lib, redzone):
     assert names[0] == "in0" and "part" in names and "hoistU" in names and "dwslab3" in names and exact[-1].offset + exact[-1].bytes <= total.value
     rows, tot = _lib.ws_regions()
     assert [r[0] for r in rows] == names and tot == total.value
+    # dsdf_debug_packed_layout: NULL arguments and an invalid net are refused and write nothing; a valid net's total is dsdf_packed_floats'
+    lay = _lib.DsdfPackedLayout()
+    lay.total = 77
+    assert lib.dsdf_debug_packed_layout(None, C.byref(lay)) == -1 and lib.dsdf_debug_packed_layout(C.byref(net), None) == -1
+    bad = NetSpec(8, [32] * 4, 3, latent_in=[2]).c_struct()
+    bad.in_dim[2] += 1
+    assert lib.dsdf_debug_packed_layout(C.byref(bad), C.byref(lay)) == -1 and b"in_dim" in lib.dsdf_last_error() and lay.total == 77
+    nf = C.c_int64()
+    assert lib.dsdf_debug_packed_layout(C.byref(net), C.byref(lay)) == 0 and lib.dsdf_packed_floats(C.byref(net), C.byref(nf)) == 0
+    assert lay.total == nf.value and lay.w_off[0] == 0 and lay.ldw[0] == 32 and lay.w_off[net.n_layers] == -1
+    assert lay.scale_off + sum(net.out_dim[l] for l in range(net.n_layers)) <= lay.wf_off[0] < lay.total
 
 
 def test_latent_size_zero_never_reaches_segment_mode(lib):
