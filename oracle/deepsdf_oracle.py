@@ -203,8 +203,9 @@ def dropout_masks(net: Net, seed: int, step: int, n_rows: int, row_offset: int =
 
 
 def renorm_rows_(table: torch.Tensor, indices: torch.Tensor, max_norm: Optional[float]) -> None:
-    """In place, no grad: every looked-up row with ||row||_2 > max_norm is scaled by max_norm/(norm+1e-7)."""
-    if max_norm is None:
+    """In place, no grad: every looked-up row with ||row||_2 > max_norm is scaled by max_norm/(norm+1e-7).  None, and the C ABI's
+    spelling of it, a bound <= 0 (include/dsdf.h: "<= 0 disables the renorm"), leave the table as it is."""
+    if max_norm is None or max_norm <= 0:
         return
     for j in torch.unique(indices).tolist():
         nu = table[j].norm(2)
@@ -503,8 +504,11 @@ def step_gradients(net: Net, params, latents, indices, xyz, sdf_gt, *, delta, co
 
 def train_step(net: Net, st: TrainState, indices, xyz, sdf_gt, *, delta, code_bound, code_reg=True,
                code_reg_lambda=1e-4, epoch=1, lr_decoder=5e-4, lr_latent=1e-3, batch_split=1,
-               grad_clip=None, training=True, seed=0, masks_per_chunk=None):
-    """Full optimiser step incl. --batch_split accumulation.  Returns dict(loss, grads, dlat, grad_norm, y [N, 1])."""
+               grad_clip=None, training=True, seed=0, masks_per_chunk=None, betas=(0.9, 0.999), eps=1e-8, n_norm=None):
+    """Full optimiser step incl. --batch_split accumulation.  Returns dict(loss, grads, dlat, grad_norm, y [N, 1], grads_unclipped: the
+    gradients before grad_clip scaled them, None without clipping).
+    betas / eps: torch.optim.Adam's (its defaults); n_norm: the loss's divisor where it is not this batch's point count (a
+    data-parallel rank's share of a larger step)."""
     N = xyz.shape[0]
     ys = []
     xs, is_, ts = torch.chunk(xyz, batch_split), torch.chunk(indices, batch_split), torch.chunk(sdf_gt, batch_split)
@@ -523,7 +527,7 @@ def train_step(net: Net, st: TrainState, indices, xyz, sdf_gt, *, delta, code_bo
         lmask = latent_dropout_mask(net, seed, st.step, n, row_offset=row0) if (training and net.latent_dropout) else None
         r = step_gradients(net, st.params, st.latents, is_[ci], xs[ci], ts[ci], delta=delta,
                            code_bound=code_bound, code_reg=code_reg, code_reg_lambda=code_reg_lambda,
-                           epoch=epoch, n_norm=N, training=training, masks=masks, latent_mask=lmask)
+                           epoch=epoch, n_norm=N if n_norm is None else n_norm, training=training, masks=masks, latent_mask=lmask)
         loss += float(r["loss"])
         ys.append(r["y"])
         tot_dlat += r["dlat"]
@@ -533,14 +537,15 @@ def train_step(net: Net, st: TrainState, indices, xyz, sdf_gt, *, delta, code_bo
             for k in tot_g:
                 tot_g[k] = tot_g[k] + r["grads"][k]
         row0 += n
-    gnorm = None
+    gnorm, raw = None, None
     if grad_clip is not None:
+        raw = {k: g.clone() for k, g in tot_g.items()}      # what the backward pass produced: clipping scales tot_g in place
         gnorm = clip_grad_norm_(tot_g, grad_clip)
     st.step += 1
     for k in st.params:
-        adam_update_(st.params[k], tot_g[k].reshape(st.params[k].shape), st.m[k], st.v[k], st.step, lr_decoder)
-    adam_update_(st.latents, tot_dlat, st.m_lat, st.v_lat, st.step, lr_latent)
-    return dict(loss=loss, grads=tot_g, dlat=tot_dlat, grad_norm=gnorm, y=torch.cat(ys))
+        adam_update_(st.params[k], tot_g[k].reshape(st.params[k].shape), st.m[k], st.v[k], st.step, lr_decoder, betas[0], betas[1], eps)
+    adam_update_(st.latents, tot_dlat, st.m_lat, st.v_lat, st.step, lr_latent, betas[0], betas[1], eps)
+    return dict(loss=loss, grads=tot_g, dlat=tot_dlat, grad_norm=gnorm, y=torch.cat(ys), grads_unclipped=raw)
 
 
 # --------------------------------------------------------------------------------------------

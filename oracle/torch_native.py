@@ -23,14 +23,14 @@ class NativeStep:
     with the two parameter groups (train_deep_sdf.py:400-411)."""
 
     def __init__(self, net: Net, params: Dict[str, torch.Tensor], latents: torch.Tensor, *, code_bound: Optional[float],
-                 lr_decoder: float = 5e-4, lr_latent: float = 1e-3):
+                 lr_decoder: float = 5e-4, lr_latent: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
         self.net = net
         self.params = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
         self.lat = torch.nn.Embedding(latents.shape[0], latents.shape[1], max_norm=code_bound, dtype=latents.dtype)
         with torch.no_grad():
             self.lat.weight.copy_(latents)
         self.opt = torch.optim.Adam([{"params": list(self.params.values()), "lr": lr_decoder},
-                                     {"params": self.lat.parameters(), "lr": lr_latent}])
+                                     {"params": self.lat.parameters(), "lr": lr_latent}], betas=tuple(betas), eps=eps)
         self.step_count = 0
 
     def forward(self, x0, training: bool, masks: Optional[Sequence[Optional[torch.Tensor]]] = None):
@@ -56,11 +56,15 @@ class NativeStep:
         return torch.tanh(x)
 
     def step(self, indices, xyz, sdf_gt, *, delta: float, code_reg: bool = True, code_reg_lambda: float = 1e-4, epoch: int = 1,
-             training: bool = True, seed: int = 0, masks: Optional[List[Optional[torch.Tensor]]] = None) -> float:
-        """One optimiser step (no --batch_split).  Returns the loss."""
+             training: bool = True, seed: int = 0, masks: Optional[List[Optional[torch.Tensor]]] = None,
+             n_norm: Optional[int] = None, grad_clip: Optional[float] = None) -> float:
+        """One optimiser step (no --batch_split).  Returns the loss.  n_norm: the loss's divisor where it is not this batch's point
+        count; grad_clip: torch.nn.utils.clip_grad_norm_ on the decoder's parameters (train_deep_sdf.py:541-543)."""
         n = xyz.shape[0]
+        masks_n = n
+        n = n if n_norm is None else n_norm
         if masks is None and training and self.net.dropout_prob > 0.0:
-            masks = dropout_masks(self.net, seed, self.step_count, n)
+            masks = dropout_masks(self.net, seed, self.step_count, masks_n)
         self.opt.zero_grad()
         z = self.lat(indices)                                     # in-place max-norm renorm of the looked-up rows, then gather
         pred = torch.clamp(self.forward(torch.cat([z, xyz], 1), training, masks), -delta, delta)
@@ -69,6 +73,8 @@ class NativeStep:
         if code_reg:
             loss = loss + code_reg_lambda * min(1.0, epoch / 100) * torch.sum(torch.norm(z, dim=1)) / n
         loss.backward()
+        if grad_clip is not None:
+            torch.nn.utils.clip_grad_norm_(list(self.params.values()), grad_clip)
         self.opt.step()
         self.step_count += 1
         return float(loss.detach())

@@ -159,8 +159,9 @@ def margins_ok(dec_net, params, x0, gt, delta, masks=None, training=False, tol=2
 
 def case_train(Decoder, name, *, L, net_specs, S_tot, scenes_steps, S, seed, delta=0.1, lam=1e-4,
                epoch=37, code_bound=1.0, code_reg=True, lr=(5e-4, 1e-3), batch_split=1, dropout_train=False,
-               drop_seed=0, grad_clip=None, store="full", oversize_row=None):
-    """Run len(scenes_steps) optimiser steps on the reference; store inputs + expected outputs."""
+               drop_seed=0, grad_clip=None, store="full", oversize_row=None, betas=(0.9, 0.999), eps=1e-8):
+    """Run len(scenes_steps) optimiser steps on the reference; store inputs + expected outputs.  betas / eps go to torch.optim.Adam
+    and into meta (the goldens written before they were arguments carry neither key: torch's defaults)."""
     net = orc.make_net(L, **net_specs)
     params = orc.init_params(net, seed)
     gen = torch.Generator().manual_seed(seed + 1)
@@ -170,12 +171,13 @@ def case_train(Decoder, name, *, L, net_specs, S_tot, scenes_steps, S, seed, del
     dec = build_ref(Decoder, L, net_specs, params)
     lat = torch.nn.Embedding(S_tot, L, max_norm=code_bound)
     lat.weight.data.copy_(lat0)
-    opt = torch.optim.Adam([{"params": dec.parameters(), "lr": lr[0]}, {"params": lat.parameters(), "lr": lr[1]}])
+    opt = torch.optim.Adam([{"params": dec.parameters(), "lr": lr[0]}, {"params": lat.parameters(), "lr": lr[1]}],
+                           betas=tuple(betas), eps=eps)
     out = {"meta": np.frombuffer(json.dumps(dict(
         L=L, net_specs=net_specs, S_tot=S_tot, S=S, seed=seed, delta=delta, lam=lam, epoch=epoch,
         code_bound=code_bound, code_reg=code_reg, lr=list(lr), batch_split=batch_split,
         dropout_train=dropout_train, drop_seed=drop_seed, grad_clip=grad_clip, store=store,
-        n_steps=len(scenes_steps))).encode(), dtype=np.uint8)}
+        n_steps=len(scenes_steps), betas=list(betas), eps=eps)).encode(), dtype=np.uint8)}
     out.update(pack("lat0", {"w": lat0}))
     if store == "full":
         out.update(pack("params0", params))
@@ -514,6 +516,21 @@ def case_sample_counts(name):
     print("wrote", name)
 
 
+def off_point_cases(Decoder):
+    """G14: three steps each, at the size of g1a, AWAY from the one set of constants every other golden runs at (CodeBound 1.0,
+    ClampingDistance 0.1, lambda 1e-4, torch's Adam defaults)."""
+    wn4d = dict(dims=[64] * 4, dropout=[0, 1, 2, 3], dropout_prob=0.2, norm_layers=[0, 1, 2, 3], latent_in=[2],
+                xyz_in_all=False, use_tanh=False, latent_dropout=False, weight_norm=True, geom_dimension=3)
+    # a tight code bound (every row of norm ~1 is scaled at every step, row 1 starts at norm 3), a narrow clamp, a regulariser that
+    # carries weight at ramp 0.37, dropout in training mode; step 1 omits scene 2
+    case_train(Decoder, "g14a_off_point_tight", L=4, net_specs=wn4d, S_tot=3, scenes_steps=[[0, 1, 2], [0, 1], [2, 1, 0]], S=32,
+               seed=131, code_bound=0.6, delta=0.03, lam=1e-2, epoch=37, dropout_train=True, drop_seed=55, oversize_row=1)
+    # a loose code bound (only the oversize row is scaled), a wide clamp, no regulariser, non-default Adam constants, clipping
+    case_train(Decoder, "g14b_off_point_loose", L=4, net_specs=dict(wn4d, dropout_prob=0.0), S_tot=3,
+               scenes_steps=[[0, 1, 2], [1, 2], [2, 0, 1]], S=32, seed=132, code_bound=2.5, delta=0.4, code_reg=False,
+               betas=(0.8, 0.95), eps=1e-5, grad_clip=0.05, oversize_row=2)
+
+
 def main():
     torch.set_num_threads(4)
     Decoder = ref_decoder_cls()
@@ -552,6 +569,7 @@ def main():
                scenes_steps=[[0, 1, 2], [2, 1, 0]], S=32, seed=112, dropout_train=True, drop_seed=22, batch_split=2)
     case_train(Decoder, "g11c_layer_norm", L=4, net_specs=dict(wn4d, weight_norm=False, norm_layers=[0, 1, 2, 3, 4], dims=[56] * 4),
                S_tot=3, scenes_steps=[[0, 1, 2], [0, 2, 1]], S=32, seed=113, dropout_train=True, drop_seed=23)
+    off_point_cases(Decoder)
     case_lr("g5_lr_schedules")
     case_real_weights("g6_real_weights")
     case_latent_only(Decoder, "g7_latent_only", L=8, net_specs=dict(wn4, latent_in=[2]), N=96, iters=5, seed=71)
@@ -582,6 +600,9 @@ if __name__ == "__main__":
         torch.set_num_threads(4)                      # as main(): the run is bit-reproducible for a fixed thread count
         case_lr("g5_lr_schedules")
         case_reference_run("g10_reference_run")
+    elif "--off-point-only" in sys.argv:              # writes the two G14 files only; no committed golden is regenerated
+        torch.set_num_threads(4)
+        off_point_cases(ref_decoder_cls())
     elif "--sample-counts-only" in sys.argv:
         case_sample_counts("g12_sample_counts")
     else:

@@ -23,8 +23,8 @@ class HipTrainer:
         self.dev = device
 
     def step(self, idx, xyz, gt, *, delta, code_bound, code_reg, lam, epoch, lr, batch_split=1, grad_clip=None,
-             seed=0, training=True, want_y=False, do_adam=True, force_ragged=False):
-        N = xyz.shape[0]
+             seed=0, training=True, want_y=False, do_adam=True, force_ragged=False, betas=(0.9, 0.999), eps=1e-8, n_norm=None):
+        N = xyz.shape[0] if n_norm is None else n_norm
         idx, xyz, gt = idx.to(self.dev), xyz.to(self.dev).contiguous(), gt.to(self.dev).reshape(-1).contiguous()
         reg = lam * min(1, epoch / 100) if code_reg else 0.0
         ys, row0 = [], 0
@@ -45,7 +45,7 @@ class HipTrainer:
         if grad_clip is not None:
             out["grad_norm"] = float(self.eng.grad_norm(grad_clip)[0].item())
         if do_adam:
-            self.eng.adam_step(self.lat, self.dlat, self.lat_m, self.lat_v, lr[0], lr[1], clip=grad_clip is not None)
+            self.eng.adam_step(self.lat, self.dlat, self.lat_m, self.lat_v, lr[0], lr[1], clip=grad_clip is not None, betas=betas, eps=eps)
         return out
 
     def params(self):

@@ -170,6 +170,70 @@ def test_trainer_end_to_end_and_resume(tmp_path):
         train.main_function(exp, "latest", 1)
 
 
+OFF_POINT_SPECS = {"CodeBound": 0.6, "ClampingDistance": 0.03, "CodeRegularizationLambda": 1e-2, "NumEpochs": 2, "SnapshotFrequency": 2,
+                   "AdditionalSnapshots": [], "LogFrequency": 2}
+
+
+@pytest.mark.parametrize("clip", [None, 0.02], ids=["one_call_step", "GradientClipNorm"])
+def test_trainer_off_the_reference_point_follows_the_oracle(tmp_path, monkeypatch, clip):
+    """The tiny experiment with a specs.json AWAY from CodeBound 1.0 / ClampingDistance 0.1 / lambda 1e-4, without and
+    with GradientClipNorm (the one-call step, and the two-call path with dsdf_grad_norm).  Every step the trainer takes is recorded
+    -- the state it starts from, the batch it drew -- and replayed through the float64 oracle AT THE FILE'S VALUES: loss 1e-5, the table
+    the forward leaves and the post-step parameters and table PARAM_TOL, the gradient norm GRAD_TOL.  The values reach the kernels from
+    the file, or the replay does not agree: in these first epochs (ramp epoch / 100) a lambda of 1e-2 is 0.2 % of the loss, two hundred
+    times its bound, and a band of 0.03 leaves between a seventh and two fifths of the predictions outside."""
+    from deepsdf_amd import train
+    over = dict(OFF_POINT_SPECS, **({"GradientClipNorm": clip} if clip is not None else {}))
+    exp = _make_experiment(str(tmp_path), 4, specs_over=over)
+    specs = json.load(open(os.path.join(exp, "specs.json")))
+    rec, true_call = [], train.FusedTrainStep.__call__
+
+    def recording(self, scene_rows, sps, xyz, sdf_gt, epoch, lr0, lr1, **kw):
+        eng = self.eng
+        before = dict(p={k: v.clone().cpu() for k, v in eng.named_views().items()}, m={k: v.clone().cpu() for k, v in eng.named_views(eng.exp_avg).items()},
+                      v={k: v.clone().cpu() for k, v in eng.named_views(eng.exp_avg_sq).items()}, lat=self.lat.cpu().clone(),
+                      lat_m=self.lat_m.cpu().clone(), lat_v=self.lat_v.cpu().clone(), step=eng.step)
+        true_call(self, scene_rows, sps, xyz, sdf_gt, epoch, lr0, lr1, **kw)
+        rec.append(dict(before=before, rows=scene_rows.cpu().clone(), sps=sps, xyz=xyz.cpu().clone(), gt=sdf_gt.cpu().clone(), epoch=epoch,
+                        lr=(lr0, lr1), n_norm=kw["n_norm"], seed=self.seed, loss=float(kw["loss_out"].item()),
+                        p={k: v.clone().cpu() for k, v in eng.named_views().items()}, lat=self.lat.cpu().clone(),
+                        norm=float(eng.clip[0].item()), cfg=(self.clamp_dist, self.code_bound, self.lam, self.grad_clip)))
+
+    monkeypatch.setattr(train.FusedTrainStep, "__call__", recording)
+    torch.manual_seed(0)
+    train.main_function(exp, None, 1)
+    assert len(rec) == 2 * 2                                        # 2 epochs x (4 scenes / 2 per batch)
+    net = orc.make_net(specs["CodeLength"], **specs["NetworkSpecs"])
+    oversize = 0
+    for i, r in enumerate(rec):
+        assert r["cfg"] == (0.03, 0.6, 1e-2, clip) and r["n_norm"] == r["xyz"].shape[0] == 2 * 4096
+        b = r["before"]
+        st = orc.TrainState(params={k: v.double() for k, v in b["p"].items()}, latents=b["lat"].double(),
+                            m={k: v.double() for k, v in b["m"].items()}, v={k: v.double() for k, v in b["v"].items()},
+                            m_lat=b["lat_m"].double(), v_lat=b["lat_v"].double(), step=b["step"])
+        idx = r["rows"].repeat_interleave(r["sps"])
+        ren = st.latents.clone()
+        orc.renorm_rows_(ren, idx, 0.6)
+        oversize += int((b["lat"][r["rows"]].norm(dim=1) > 0.6 + 1e-4).sum())
+        o = orc.train_step(net, st, idx, r["xyz"].double(), r["gt"].double().reshape(-1, 1), delta=float(np.float32(0.03)),
+                           code_bound=float(np.float32(0.6)), code_reg=True, code_reg_lambda=1e-2, epoch=r["epoch"], lr_decoder=r["lr"][0],
+                           lr_latent=r["lr"][1], grad_clip=clip, seed=r["seed"])
+        z = ren[idx]
+        share = float(orc.code_regulariser(z, 1e-2, r["epoch"], idx.numel())[0]) / o["loss"]
+        inside = float((o["y"].abs() <= 0.03).double().mean())
+        print(f"step {i}: loss {r['loss']:.6f} (oracle {o['loss']:.6f}), regulariser's share {share:.3f}, inside the band {inside:.2f}")
+        assert abs(r["loss"] - o["loss"]) <= 1e-5 * abs(o["loss"]), (i, r["loss"], o["loss"])
+        assert share > 1e-3 and 0.02 < inside < 0.98
+        for k in st.params:
+            assert rel_err(r["p"][k], st.params[k]) <= PARAM_TOL, (i, k)
+        assert rel_err(r["lat"], st.latents) <= PARAM_TOL, i
+        assert float(r["lat"][r["rows"]].norm(dim=1).max()) <= 0.6 + 2 * max(r["lr"]) * math.sqrt(specs["CodeLength"])      # bound + one Adam step
+        if clip is not None:
+            assert abs(r["norm"] - float(o["grad_norm"])) <= GRAD_TOL * float(o["grad_norm"]), (i, r["norm"], float(o["grad_norm"]))
+            assert (float(o["grad_norm"]) > clip) or i > 0, "the clip should fire on the first step"
+    assert oversize >= 2                                            # the renorm had rows to scale
+
+
 def test_latent_only_reconstruction_vs_golden():
     """Config 4: frozen decoder, Adam on the code only -- golden g7 = reference Decoder.eval() + torch Adam."""
     from deepsdf_amd.engine import Engine

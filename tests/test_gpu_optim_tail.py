@@ -85,17 +85,25 @@ def tiny_engine():
 def test_flat_adam_forms_hold_the_spec_at_every_step(n, tiny_engine):
     """dsdf_adam_latent_only, dsdf_adam_latent_sched (one schedule row holding step t's scalars) and the ride, from the same aged and
     fresh states at steps 1 .. 100000.  (|g| >= 1e-12 keeps g^2 and (1 - b2) g^2 normal fp32 numbers: the bounds stay relative.)"""
+    flat_adam_forms(n, tiny_engine)
+
+
+def flat_adam_forms(n, tiny_engine, betas=(0.9, 0.999), eps=1e-8, steps=STEPS):
+    """The three flat forms at Adam constants of the caller's choice (tests/test_gpu_operating_points.py: away from torch's defaults);
+    the spec is evaluated at their float32 images, as the ABI carries them."""
     lib = _lib.lib()
+    b1, b2, ep = O.f32(betas[0]), O.f32(betas[1]), O.f32(eps)
+    assert 1.0 - b1 <= 0.5                                         # m_bound's condition
     blocks = min(2048, -(-n // 256))
     assert (n > blocks * 256) == (n > CAP)                       # sizes past the cap take a second pass; the last one has a tail
     for aged in (True, False):
         p0, g0, m0, v0 = O.make_state(n, 1000 + n % 997, aged=aged)
         O.check_state(p0, g0, m0, v0, aged=aged)
         g = _dev(g0)
-        for t in STEPS:
+        for t in steps:
             tag = f"n{n} {'aged' if aged else 'fresh'} t{t}"
-            r = O.adam_ref(p0, g0, m0, v0, lr=LR_LAT, t=t)
-            cfg = _lib.DsdfAdamCfg(t, 0.0, LR_LAT, 0.9, 0.999, 1e-8, None)
+            r = O.adam_ref(p0, g0, m0, v0, lr=LR_LAT, t=t, b1=b1, b2=b2, eps=ep)
+            cfg = _lib.DsdfAdamCfg(t, 0.0, LR_LAT, betas[0], betas[1], eps, None)
             # adam_kernel
             p, m, v = _dev(p0), _dev(m0), _dev(v0)
             _lib.check(lib.dsdf_adam_latent_only(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, C.byref(cfg), _stream()))
@@ -108,12 +116,12 @@ def test_flat_adam_forms_hold_the_spec_at_every_step(n, tiny_engine):
                                           _ptr(g), _ptr(m), _ptr(v), n, C.byref(cfg), _ptr(e.packed), _stream()))
             hold_adam(tag + " ride", p, m, v, r, m0)
             # adam_sched_kernel: the two scalars as the device schedule carries them (fp32), the regulariser folded in
-            ss, bq = (O.f32(x) for x in O.step_scalars(LR_LAT, O.B1, O.B2, t))
-            rs = O.adam_ref(p0, g0, m0, v0, lr=None, t=None, l2=L2, step_size=ss, bc2_sqrt=bq)
+            ss, bq = (O.f32(x) for x in O.step_scalars(LR_LAT, b1, b2, t))
+            rs = O.adam_ref(p0, g0, m0, v0, lr=None, t=None, b1=b1, b2=b2, eps=ep, l2=L2, step_size=ss, bc2_sqrt=bq)
             p, m, v = _dev(p0), _dev(m0), _dev(v0)
             sched = torch.tensor([[ss, bq]], dtype=torch.float64).to(torch.float32).cuda()
             counter = torch.zeros(1, dtype=torch.int64, device="cuda")
-            _lib.check(lib.dsdf_adam_latent_sched(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(sched), 1, _ptr(counter), 0.9, 0.999, 1e-8,
+            _lib.check(lib.dsdf_adam_latent_sched(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(sched), 1, _ptr(counter), betas[0], betas[1], eps,
                                                   L2, _stream()))
             hold_adam(tag + " sched", p, m, v, rs, m0, scaled=True)
             assert int(counter.item()) == 1
@@ -209,6 +217,12 @@ def test_decoder_arena_adam_holds_the_spec(name, clip):
     to a fresh dsdf_materialize_weights of the new parameters (padding included: the fresh engine's buffer starts zeroed, too).
     With clipping the spec's grad_scale is the fp32 coefficient Engine.grad_norm left on the device (its own value is
     test_grad_norm_and_clip_coefficient_hold_the_spec's subject): below 1, and exactly 1."""
+    decoder_arena_adam(name, clip)
+
+
+def decoder_arena_adam(name, clip, betas=(0.9, 0.999), eps=1e-8, steps=STEPS):
+    """adam_rows_kernel (and adam_kernel on bn parameters) at Adam constants of the caller's choice."""
+    b1, b2, ep = O.f32(betas[0]), O.f32(betas[1]), O.f32(eps)
     spec = arena_spec(name)
     rows = sum(spec.out_dim)
     if name.startswith("wn_"):
@@ -218,7 +232,7 @@ def test_decoder_arena_adam_holds_the_spec(name, clip):
     for aged in (True, False):
         p0, g0, m0, v0 = O.make_state(spec.n_params, 31 + len(name), aged=aged)
         O.check_state(p0, g0, m0, v0, aged=aged)
-        for t in STEPS:
+        for t in steps:
             eng = Engine(spec, "cuda")
             eng.params.copy_(_dev(p0)); eng.grads.copy_(_dev(g0)); eng.exp_avg.copy_(_dev(m0)); eng.exp_avg_sq.copy_(_dev(v0))
             eng.step = t - 1
@@ -227,9 +241,9 @@ def test_decoder_arena_adam_holds_the_spec(name, clip):
                 norm = float(np.sqrt((g0.astype(np.float64) ** 2).sum()))
                 gs = float(eng.grad_norm(O.f32(norm * (0.37 if clip == "coef<1" else 2.0)))[1].item())
                 assert (0.36 < gs < 0.38) if clip == "coef<1" else gs == 1.0, gs
-            eng.adam_step(None, None, None, None, LR_DEC, LR_LAT, clip=clip != "noclip")
+            eng.adam_step(None, None, None, None, LR_DEC, LR_LAT, clip=clip != "noclip", betas=betas, eps=eps)
             assert eng.step == t
-            r = O.adam_ref(p0, g0, m0, v0, lr=LR_DEC, t=t, grad_scale=gs)
+            r = O.adam_ref(p0, g0, m0, v0, lr=LR_DEC, t=t, grad_scale=gs, b1=b1, b2=b2, eps=ep)
             tag = f"{name} {clip} {'aged' if aged else 'fresh'} t{t}"
             hold_adam(tag, eng.params, eng.exp_avg, eng.exp_avg_sq, r, m0, scaled=clip != "noclip")
             assert torch.equal(eng.grads.cpu(), torch.from_numpy(g0))
@@ -352,6 +366,12 @@ def test_fused_finalize_adam_holds_the_spec_of_its_own_gradient(name, mode):
     moments are held to it at the spec's bounds -- both paths form every gradient entry with the same expressions (the finalize pass
     computes d once and either stores it or hands it to adam_elem), so nothing looser is needed.  The sentinel B's gradient arena is
     filled with tells the paths apart: the fused finalize never writes the arena; a net that falls back to dsdf_adam_step does."""
+    fused_finalize_adam(name, mode)
+
+
+def fused_finalize_adam(name, mode, betas=(0.9, 0.999), eps=1e-8):
+    """finalize_row_wave<K> + Adam, the ride and the latent Adam of dsdf_train_step at Adam constants of the caller's choice."""
+    b1, b2, ep = O.f32(betas[0]), O.f32(betas[1]), O.f32(eps)
     spec = fused_spec(name)
     fused = FUSED_NETS[name][2] and os.environ.get("DSDF_NO_FUSED") != "1"      # (the switch sends every net down the fallback)
     sc, so, xyz, gt, seg_len = tail_batch(mode)
@@ -366,7 +386,7 @@ def test_fused_finalize_adam_holds_the_spec_of_its_own_gradient(name, mode):
     assert ("hoistU" in names) == (mode == "segment" and fused), names      # segment mode (hoisted x0 columns) exactly where expected
     B.grads.fill_(SENTINEL)
     B.train_step(latB, dlatB, lmB, lvB, sc, so, xyz, gt, n_norm=n, lr_decoder=LR_DEC, lr_latent=LR_LAT, training=True, seg_len=seg_len,
-                 **STEP_KW)
+                 betas=betas, eps=eps, **STEP_KW)
     assert A.step == STEP0 and B.step == STEP0 + 1
     survived = bool((B.grads == SENTINEL).all())
     assert survived == fused, f"{name}: expected the {'fused finalize' if fused else 'two-call fallback'} path"
@@ -376,12 +396,12 @@ def test_fused_finalize_adam_holds_the_spec_of_its_own_gradient(name, mode):
     g = A.grads.cpu().numpy()
     assert np.isfinite(g).all() and (g != 0).mean() > 0.5
     tag = f"{name} {mode}"
-    r = O.adam_ref(p0, g, m0, v0, lr=LR_DEC, t=STEP0 + 1)
+    r = O.adam_ref(p0, g, m0, v0, lr=LR_DEC, t=STEP0 + 1, b1=b1, b2=b2, eps=ep)
     hold_adam(tag + " decoder", B.params, B.exp_avg, B.exp_avg_sq, r, m0)
     dl = dlatA.cpu().numpy().reshape(-1)
     absent = [s for s in range(latA.shape[0]) if s not in sc.cpu().tolist()]
     assert absent and not dlatA[absent].any()                                 # latent rows absent from the batch: zero gradient rows
-    rl = O.adam_ref(latA.cpu().numpy().reshape(-1), dl, lm0, lv0, lr=LR_LAT, t=STEP0 + 1)     # (A's table: renormed by the forward, as B's)
+    rl = O.adam_ref(latA.cpu().numpy().reshape(-1), dl, lm0, lv0, lr=LR_LAT, t=STEP0 + 1, b1=b1, b2=b2, eps=ep)     # (A's table: renormed by the forward, as B's)
     hold_adam(tag + " latent", latB, lmB, lvB, rl, lm0)
     from tests.packed_numpy import layout_of
     so_ = layout_of(spec)["scale_off"]

@@ -18,7 +18,9 @@ TRAIN_CASES = ["g1a_tiny_full", "g1b_lastnorm_tanh", "g1c_plain_clip", "g2_8x512
                "g3b_dropout_8x512", "g4_batch_split2",
                # the Decoder variants no shipped spec uses: xyz_in_all, latent_dropout (+ batch_split 2), LayerNorm (incl. the
                # bn module of the last Linear, which forward never calls: zero gradient, no Adam movement)
-               "g11a_xyz_in_all", "g11b_latent_dropout", "g11c_layer_norm"]
+               "g11a_xyz_in_all", "g11b_latent_dropout", "g11c_layer_norm",
+               # away from CodeBound 1.0 / ClampingDistance 0.1 / lambda 1e-4 / torch's Adam defaults
+               "g14a_off_point_tight", "g14b_off_point_loose"]
 
 
 def run_case(name):
@@ -33,7 +35,8 @@ def run_case(name):
         r = orc.train_step(net, st, i["idx"], i["xyz"], i["gt"], delta=m["delta"], code_bound=m["code_bound"],
                            code_reg=m["code_reg"], code_reg_lambda=m["lam"], epoch=m["epoch"],
                            lr_decoder=m["lr"][0], lr_latent=m["lr"][1], batch_split=m["batch_split"],
-                           grad_clip=m["grad_clip"], training=True, seed=m["drop_seed"])
+                           grad_clip=m["grad_clip"], training=True, seed=m["drop_seed"],
+                           betas=tuple(m.get("betas", (0.9, 0.999))), eps=m.get("eps", 1e-8))     # (older goldens: torch's defaults)
         res.append(r)
         o = g.group(f"step{si}/out")
         assert abs(r["loss"] - float(o["loss"])) <= 1e-5 * abs(float(o["loss"])) + 1e-9, (name, si)
