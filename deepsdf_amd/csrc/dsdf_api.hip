@@ -470,9 +470,6 @@ Plan make_plan(const DsdfNet* n, int64_t N, int64_t R, bool inference, bool segm
   return P;
 }
 
-template <typename T>
-inline T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
-
 // ---- launch helpers -------------------------------------------------------------------------------
 template <int EPI>
 int launch_nt(const NtArgs& a, hipStream_t st) {
@@ -574,32 +571,8 @@ inline uint32_t latent_drop_thr() { return (uint32_t)lround((double)LATENT_DROPO
 inline bool net_variant(const DsdfNet* n) { return n->latent_dropout || n->xyz_in_all || n->ln_param_mask != 0; }
 inline bool ln_applied(const DsdfNet* n, int l) { return ((n->ln_param_mask >> l) & 1) && l < n->n_layers - 1; }   // hidden layers only
 
-
-// x0 (+ skip copies, + the xyz columns of every layer of an xyz_in_all net) from either the latent table + segments or an
-// explicit input; keys != nullptr && training: latent_dropout nets drop layer 0's latent columns on the way
-int run_gather(const DsdfNet* net, const Plan& P, void* ws, const float* table, const DsdfBatch* b, const float* input,
-               int64_t ld_in, int64_t n, hipStream_t st, int training = 0, const uint32_t* keys = nullptr, uint32_t row_offset = 0) {
-  GatherArgs g;
-  memset(&g, 0, sizeof(g));
-  g.table = table; g.L = net->latent_size; g.G = net->geom_dim;
-  if (b) { g.xyz = b->xyz; g.seg_scene = b->seg_scene; g.seg_offset = b->seg_offset; g.R = (int)b->n_segments; }
-  g.input = input; g.ld_in = ld_in; g.n = (int)n;
-  const int W0 = net->latent_size + net->geom_dim;
-  const bool drop = net->latent_dropout && training && keys != nullptr && net->latent_size > 0;
-  if (drop) { g.drop_key = keys[LATENT_DROPOUT_KEY]; g.drop_thr = latent_drop_thr(); g.drop_scale = 1.0f / (1.0f - LATENT_DROPOUT_P); g.row_offset = row_offset; }
-  g.ndst = 0;
-  g.dst[g.ndst++] = GatherDst{at<float>(ws, P.in_off[0]), P.ld_in[0], 0, 0, W0, drop ? 1 : 0};
-  for (int l = 1; l < net->n_layers; ++l) {
-    if ((net->skip_mask >> l) & 1) g.dst[g.ndst++] = GatherDst{at<float>(ws, P.in_off[l]), P.ld_in[l], net->out_dim[l - 1], 0, W0, 0};
-    else if (net->xyz_in_all) g.dst[g.ndst++] = GatherDst{at<float>(ws, P.in_off[l]), P.ld_in[l], net->out_dim[l - 1], net->latent_size, net->geom_dim, 0};
-  }
-  hipLaunchKernelGGL(gather_concat_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, g);
-  LAUNCH_OK("gather_concat_kernel");
-  return 0;
-}
-
 // ---- the kernel path of one call --------------------------------------------------------------------
-// A/B and test switches.  Read ONCE per call, by the entry point (the tests flip them inside one process); nothing below an entry
+// A/B and test switches.  Read ONCE per call, by open_call (the tests flip them inside one process); nothing below an entry
 // point reads the environment (lab builds and the per-process DSDF_NO_RIDE of plan_roles excepted).
 struct Switches {
   bool no_fused, no_narrow, frows64, no_w32, no_w32x2, no_merge;
@@ -718,6 +691,49 @@ Drop drop_of(const DsdfNet* net, int layer, int training) {
 }
 float mask_scale_of(const DsdfNet* net, int layer, int training) { return drop_of(net, layer, training).scale; }
 
+// The state of one call: everything the launch code below an entry point works on, filled ONCE, by open_call.  The helpers take it
+// whole and add only what is their own.  No behaviour: fields, and the typed view of a workspace region.
+struct Call {
+  const DsdfNet* net;
+  Switches sw;
+  Path path;
+  Plan P;
+  DsdfParamLayout L;   // where each layer's parameters sit in params / grads
+  Packed pk;           // ... and its materialized copies in packed
+  void* ws;
+  const float* packed;
+  const float* params;
+  int64_t n;
+  hipStream_t st;
+  int training;           // these three: zero behind open_call, the training / module entries set them
+  const uint32_t* keys;   // dropout keys of the layers (+ LATENT_DROPOUT_KEY)
+  uint32_t row_offset;    // of this call's first point in the dropout hash (data-parallel ranks)
+  template <typename T>
+  T* at(size_t off) const { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
+};
+
+// x0 (+ skip copies, + the xyz columns of every layer of an xyz_in_all net) from either the latent table + segments or an
+// explicit input; keys != nullptr && training: latent_dropout nets drop layer 0's latent columns on the way
+int run_gather(const Call& c, const float* table, const DsdfBatch* b, const float* input, int64_t ld_in) {
+  GatherArgs g;
+  memset(&g, 0, sizeof(g));
+  g.table = table; g.L = c.net->latent_size; g.G = c.net->geom_dim;
+  if (b) { g.xyz = b->xyz; g.seg_scene = b->seg_scene; g.seg_offset = b->seg_offset; g.R = (int)b->n_segments; }
+  g.input = input; g.ld_in = ld_in; g.n = (int)c.n;
+  const int W0 = c.net->latent_size + c.net->geom_dim;
+  const bool drop = c.net->latent_dropout && c.training && c.keys != nullptr && c.net->latent_size > 0;
+  if (drop) { g.drop_key = c.keys[LATENT_DROPOUT_KEY]; g.drop_thr = latent_drop_thr(); g.drop_scale = 1.0f / (1.0f - LATENT_DROPOUT_P); g.row_offset = c.row_offset; }
+  g.ndst = 0;
+  g.dst[g.ndst++] = GatherDst{c.at<float>(c.P.in_off[0]), c.P.ld_in[0], 0, 0, W0, drop ? 1 : 0};
+  for (int l = 1; l < c.net->n_layers; ++l) {
+    if ((c.net->skip_mask >> l) & 1) g.dst[g.ndst++] = GatherDst{c.at<float>(c.P.in_off[l]), c.P.ld_in[l], c.net->out_dim[l - 1], 0, W0, 0};
+    else if (c.net->xyz_in_all) g.dst[g.ndst++] = GatherDst{c.at<float>(c.P.in_off[l]), c.P.ld_in[l], c.net->out_dim[l - 1], c.net->latent_size, c.net->geom_dim, 0};
+  }
+  hipLaunchKernelGGL(gather_concat_kernel, dim3((unsigned)((c.n + 3) / 4)), dim3(256), 0, c.st, g);
+  LAUNCH_OK("gather_concat_kernel");
+  return 0;
+}
+
 #ifdef DSDF_LAB
 // lab builds: device buffers of per-wave clock stamps.  One static LabStamps per launch site (allocated once, when the environment
 // names a dump file); a LabScope around the launch zeroes it on the stream (sites that ask for it) and, when the scope ends,
@@ -747,262 +763,242 @@ struct LabScope {
 // renorm != nullptr (training steps): the launch also does the max-norm renorm of the looked-up rows into zr (max_norm <= 0: a plain
 // copy) and zeroes the dense latent gradient (nzero floats of dlat; 0: leaves it) -- no latent_renorm_kernel launch in segment mode
 struct HoistRenorm { float max_norm; float* dlat; long long nzero; };
-int run_hoist(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* table, const DsdfBatch* b,
-              FusedSeg* seg, hipStream_t st, const HoistRenorm* renorm = nullptr) {
+int run_hoist(const Call& c, const float* table, const DsdfBatch* b, FusedSeg* seg, const HoistRenorm* renorm = nullptr) {
   // (seg_hoist_kernel clamps its loads to column latent_size - 1: there must be one.  Both callers exclude the case before they
   // get here -- the segment-mode condition and decode_latent_ok -- so this is the guard of a third one)
-  if (net->latent_size < 1 || net->latent_size > HOIST_MAXL)
-    return fail(DSDF_E_INVALID, "segment mode needs 1 <= latent_size <= %d (got %d)", HOIST_MAXL, net->latent_size);
-  const Packed pk = packed_layout(net);
-  const int ks = skip_layer(net);
+  if (c.net->latent_size < 1 || c.net->latent_size > HOIST_MAXL)
+    return fail(DSDF_E_INVALID, "segment mode needs 1 <= latent_size <= %d (got %d)", HOIST_MAXL, c.net->latent_size);
+  const int ks = skip_layer(c.net);
   HoistArgs h;
   memset(&h, 0, sizeof(h));
   memset(seg, 0, sizeof(*seg));
   h.nh = ks > 0 ? 2 : 1;
-  h.W[0] = packed + pk.w_off[0]; h.ldw[0] = pk.ldw[0]; h.c0[0] = 0; h.out[0] = net->out_dim[0];
-  seg->h[0].layer = 0; seg->h[0].wx = h.W[0] + net->latent_size; seg->h[0].ldw = pk.ldw[0];
+  h.W[0] = c.packed + c.pk.w_off[0]; h.ldw[0] = c.pk.ldw[0]; h.c0[0] = 0; h.out[0] = c.net->out_dim[0];
+  seg->h[0].layer = 0; seg->h[0].wx = h.W[0] + c.net->latent_size; seg->h[0].ldw = c.pk.ldw[0];
   seg->h[1].layer = -1;
   if (ks > 0) {
-    h.W[1] = packed + pk.w_off[ks]; h.ldw[1] = pk.ldw[ks]; h.c0[1] = net->out_dim[ks - 1]; h.out[1] = net->out_dim[ks];
-    seg->h[1].layer = ks; seg->h[1].wx = h.W[1] + h.c0[1] + net->latent_size; seg->h[1].ldw = pk.ldw[ks];
+    h.W[1] = c.packed + c.pk.w_off[ks]; h.ldw[1] = c.pk.ldw[ks]; h.c0[1] = c.net->out_dim[ks - 1]; h.out[1] = c.net->out_dim[ks];
+    seg->h[1].layer = ks; seg->h[1].wx = h.W[1] + h.c0[1] + c.net->latent_size; seg->h[1].ldw = c.pk.ldw[ks];
   }
-  h.L = net->latent_size; h.seg_scene = b->seg_scene; h.table = table; h.R = (int)b->n_segments;
-  h.U = at<float>(ws, P.hoistU_off); h.ldu = P.ldu;
-  h.bf16 = net->fwd_bf16 ? 1 : 0;
+  h.L = c.net->latent_size; h.seg_scene = b->seg_scene; h.table = table; h.R = (int)b->n_segments;
+  h.U = c.at<float>(c.P.hoistU_off); h.ldu = c.P.ldu;
+  h.bf16 = c.net->fwd_bf16 ? 1 : 0;
   if (renorm != nullptr) {
-    h.max_norm = renorm->max_norm; h.zr = at<float>(ws, P.zr_off);
+    h.max_norm = renorm->max_norm; h.zr = c.at<float>(c.P.zr_off);
     h.dlat = renorm->nzero > 0 ? renorm->dlat : nullptr; h.nzero = renorm->nzero;
   }
   const int rows = h.out[0] + (ks > 0 ? h.out[1] : 0);
   const dim3 hgrid((unsigned)((rows + 3) / 4), (unsigned)((h.R + HOIST_SC - 1) / HOIST_SC));
   switch ((h.L + 63) >> 6) {               // k-units of 64 latent columns per lane (HOIST_MAXL = 512)
-    case 1: hipLaunchKernelGGL(seg_hoist_kernel<1>, hgrid, dim3(256), 0, st, h); break;
-    case 2: hipLaunchKernelGGL(seg_hoist_kernel<2>, hgrid, dim3(256), 0, st, h); break;
-    case 3: case 4: hipLaunchKernelGGL(seg_hoist_kernel<4>, hgrid, dim3(256), 0, st, h); break;
-    default: hipLaunchKernelGGL(seg_hoist_kernel<8>, hgrid, dim3(256), 0, st, h); break;
+    case 1: hipLaunchKernelGGL(seg_hoist_kernel<1>, hgrid, dim3(256), 0, c.st, h); break;
+    case 2: hipLaunchKernelGGL(seg_hoist_kernel<2>, hgrid, dim3(256), 0, c.st, h); break;
+    case 3: case 4: hipLaunchKernelGGL(seg_hoist_kernel<4>, hgrid, dim3(256), 0, c.st, h); break;
+    default: hipLaunchKernelGGL(seg_hoist_kernel<8>, hgrid, dim3(256), 0, c.st, h); break;
   }
   LAUNCH_OK("seg_hoist_kernel");
-  seg->wg_per_seg = (int)(b->seg_len / P.frows);
-  seg->xyz = b->xyz; seg->G = net->geom_dim; seg->U = h.U; seg->ldu = h.ldu;
+  seg->wg_per_seg = (int)(b->seg_len / c.P.frows);
+  seg->xyz = b->xyz; seg->G = c.net->geom_dim; seg->U = h.U; seg->ldu = h.ldu;
   return 0;
 }
 
 // seg != nullptr: segment mode (fused.hpp FusedSeg) -- x0 is not read at all, seg->h[] / seg->U come from run_hoist
-int run_fused_forward(const DsdfNet* net, const Path& path, const Plan& P, void* ws, const float* packed, const float* params,
-                      int64_t n, int training, const uint32_t* keys, uint32_t row_offset, bool store_act, float* y_out, float* u_out,
-                      hipStream_t st, const FusedSeg* seg = nullptr, FusedFwdArgs* defer = nullptr) {
+int run_fused_forward(const Call& c, bool store_act, float* y_out, float* u_out, const FusedSeg* seg = nullptr,
+                      FusedFwdArgs* defer = nullptr) {
   // defer != nullptr: fill *defer and launch nothing -- the caller hands it to run_backward_fused, which launches forward and
   // backward as ONE kernel (fused_fwd_bwd_kernel)
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1;
+  const int last = c.net->n_layers - 1;
   FusedFwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.n_hidden = last; a.N = (int)n; a.W0 = net->in_dim[0];
-  a.x0 = at<float>(ws, P.in_off[0]); a.ldx0 = P.ld_in[0];
-  a.row_offset = row_offset;
+  a.n_hidden = last; a.N = (int)c.n; a.W0 = c.net->in_dim[0];
+  a.x0 = c.at<float>(c.P.in_off[0]); a.ldx0 = c.P.ld_in[0];
+  a.row_offset = c.row_offset;
   for (int l = 0; l < last; ++l) {
     FusedLayer& y = a.ly[l];
-    y.wf = net->fwd_bf16 ? packed + pk.wfb_off[l] : (net->gemm_split ? packed + pk.ws_off[l] : packed + pk.wf_off[l]);   // (bf16 copy / split planes)
-    y.wplane = (int)(pk.ws_plane[l] * 2);   // bytes per plane (gemm_split)
-    y.wf32 = packed + pk.wf_off[l];
-    y.bias = params + L.bias_off[l];
-    y.out = store_act ? at<float>(ws, P.in_off[l + 1]) : nullptr;
-    y.ld_out = P.ld_in[l + 1];
-    y.in = net->in_dim[l]; y.out_dim = net->out_dim[l]; y.U = pk.uf[l];
-    const Drop drop = drop_of(net, l, training);
-    if (drop.on) { y.drop_thr = drop.thr; y.drop_key = keys[l]; y.drop_scale = drop.scale; }
-    y.x0_col = ((net->skip_mask >> (l + 1)) & 1) ? net->out_dim[l] : -1;
-    y.maskbits = store_act ? at<uint32_t>(ws, P.mask_off[l]) : nullptr;
+    y.wf = c.net->fwd_bf16 ? c.packed + c.pk.wfb_off[l] : (c.net->gemm_split ? c.packed + c.pk.ws_off[l] : c.packed + c.pk.wf_off[l]);   // (bf16 copy / split planes)
+    y.wplane = (int)(c.pk.ws_plane[l] * 2);   // bytes per plane (gemm_split)
+    y.wf32 = c.packed + c.pk.wf_off[l];
+    y.bias = c.params + c.L.bias_off[l];
+    y.out = store_act ? c.at<float>(c.P.in_off[l + 1]) : nullptr;
+    y.ld_out = c.P.ld_in[l + 1];
+    y.in = c.net->in_dim[l]; y.out_dim = c.net->out_dim[l]; y.U = c.pk.uf[l];
+    const Drop drop = drop_of(c.net, l, c.training);
+    if (drop.on) { y.drop_thr = drop.thr; y.drop_key = c.keys[l]; y.drop_scale = drop.scale; }
+    y.x0_col = ((c.net->skip_mask >> (l + 1)) & 1) ? c.net->out_dim[l] : -1;
+    y.maskbits = store_act ? c.at<uint32_t>(c.P.mask_off[l]) : nullptr;
     if (seg != nullptr) {   // hoisted x0 columns: nothing left to contract for layer 0, only the previous layer for the skip layer
       y.x0_col = -1;
       if (l == 0) y.in = 0;
-      else if ((net->skip_mask >> l) & 1) y.in = net->out_dim[l - 1];
+      else if ((c.net->skip_mask >> l) & 1) y.in = c.net->out_dim[l - 1];
     }
   }
   if (seg != nullptr) a.seg = *seg;
-  a.w_last = packed + pk.w_off[last]; a.b_last = params + L.bias_off[last]; a.in_last = net->in_dim[last];
-  a.use_tanh = net->use_tanh; a.y_out = y_out; a.u_out = u_out;
+  a.w_last = c.packed + c.pk.w_off[last]; a.b_last = c.params + c.L.bias_off[last]; a.in_last = c.net->in_dim[last];
+  a.use_tanh = c.net->use_tanh; a.y_out = y_out; a.u_out = u_out;
   if (defer != nullptr) {
     a.ly[last - 1].out = nullptr;   // the last hidden activation is consumed from the slab by the backward head: no global copy
     *defer = a;
     return 0;
   }
   double wmac = 0;
-  for (int l = 0; l < last; ++l) wmac += (double)net->in_dim[l] * net->out_dim[l];
-  ProfScope ps(DSDF_PROF_FUSED_FWD, 2.0 * (double)n * wmac, st);
+  for (int l = 0; l < last; ++l) wmac += (double)c.net->in_dim[l] * c.net->out_dim[l];
+  ProfScope ps(DSDF_PROF_FUSED_FWD, 2.0 * (double)c.n * wmac, c.st);
 #ifdef DSDF_LAB
   static LabStamps stamps{"DSDF_LAB_DBG", 8192 * 64 * 8, false, nullptr};
-  LabScope lab(stamps, st);
+  LabScope lab(stamps, c.st);
   a.dbg = stamps.dev;
 #endif
-  const FamilyKernels& k = KERNELS[path.family];
+  const FamilyKernels& k = KERNELS[c.path.family];
   const FwdKernel kernel = store_act ? k.fwd_act : k.fwd;
-  if (kernel == nullptr) return fail(DSDF_E_LAUNCH, "internal: kernel family %d has no forward of its own", (int)path.family);
-  const dim3 grid((unsigned)((n + P.frows - 1) / P.frows));
-  hipLaunchKernelGGL(kernel, grid, dim3(store_act ? k.block : k.fwd_block), 0, st, a);
+  if (kernel == nullptr) return fail(DSDF_E_LAUNCH, "internal: kernel family %d has no forward of its own", (int)c.path.family);
+  const dim3 grid((unsigned)((c.n + c.P.frows - 1) / c.P.frows));
+  hipLaunchKernelGGL(kernel, grid, dim3(store_act ? k.block : k.fwd_block), 0, c.st, a);
   LAUNCH_OK("fused_forward_kernel");
   return 0;
 }
 
 // hidden layers 0..nl-2: in[l+1][:, :out_l] = dropout(relu(in[l] W_l^T + b_l)); LayerNorm layers: Linear (bias) into the xhat
 // buffer, then ln_fwd_kernel normalises in place (kept for the backward when save_ln) and writes the activated output
-int run_hidden_forward(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* params, int64_t n,
-                       int training, const uint32_t* keys, uint32_t row_offset, hipStream_t st, bool save_ln = true) {
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  for (int l = 0; l < net->n_layers - 1; ++l) {
+int run_hidden_forward(const Call& c, bool save_ln = true) {
+  for (int l = 0; l < c.net->n_layers - 1; ++l) {
     NtArgs a;
     memset(&a, 0, sizeof(a));
-    a.A = at<float>(ws, P.in_off[l]); a.lda = P.ld_in[l];
-    a.B = packed + pk.w_off[l]; a.ldb = pk.ldw[l];
-    a.C = at<float>(ws, P.in_off[l + 1]); a.ldc = P.ld_in[l + 1];
-    a.M = (int)n; a.N = net->out_dim[l]; a.K = net->in_dim[l];
-    a.bias = params + L.bias_off[l];
+    a.A = c.at<float>(c.P.in_off[l]); a.lda = c.P.ld_in[l];
+    a.B = c.packed + c.pk.w_off[l]; a.ldb = c.pk.ldw[l];
+    a.C = c.at<float>(c.P.in_off[l + 1]); a.ldc = c.P.ld_in[l + 1];
+    a.M = (int)c.n; a.N = c.net->out_dim[l]; a.K = c.net->in_dim[l];
+    a.bias = c.params + c.L.bias_off[l];
     a.relu = 1;
-    const Drop drop = drop_of(net, l, training);
-    if (ln_applied(net, l)) {
-      a.C = at<float>(ws, P.lnx_off[l]);
-      TRY(launch_nt<EPI_PLAIN>(a, st));
+    const Drop drop = drop_of(c.net, l, c.training);
+    if (ln_applied(c.net, l)) {
+      a.C = c.at<float>(c.P.lnx_off[l]);
+      TRY(launch_nt<EPI_PLAIN>(a, c.st));
       LnFwdArgs f;
       memset(&f, 0, sizeof(f));
-      f.y = a.C; f.ldy = a.ldc; f.gamma = params + L.ln_w_off[l]; f.beta = params + L.ln_b_off[l];
-      f.out = at<float>(ws, P.in_off[l + 1]); f.ldo = P.ld_in[l + 1]; f.n = (int)n; f.width = net->out_dim[l];
-      f.save = save_ln ? 1 : 0; f.rstd = save_ln ? at<float>(ws, P.lnr_off[l]) : nullptr;
-      if (drop.on) { f.drop_thr = drop.thr; f.drop_key = keys[l]; f.drop_scale = drop.scale; f.row_offset = row_offset; }
-      hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, f);
+      f.y = a.C; f.ldy = a.ldc; f.gamma = c.params + c.L.ln_w_off[l]; f.beta = c.params + c.L.ln_b_off[l];
+      f.out = c.at<float>(c.P.in_off[l + 1]); f.ldo = c.P.ld_in[l + 1]; f.n = (int)c.n; f.width = c.net->out_dim[l];
+      f.save = save_ln ? 1 : 0; f.rstd = save_ln ? c.at<float>(c.P.lnr_off[l]) : nullptr;
+      if (drop.on) { f.drop_thr = drop.thr; f.drop_key = c.keys[l]; f.drop_scale = drop.scale; f.row_offset = c.row_offset; }
+      hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((c.n + 3) / 4)), dim3(256), 0, c.st, f);
       LAUNCH_OK("ln_fwd_kernel");
       continue;
     }
-    if (drop.on) { a.drop_thr = drop.thr; a.drop_key = keys[l]; a.drop_scale = drop.scale; a.row_offset = row_offset; }
-    TRY(launch_nt<EPI_FWD>(a, st));
+    if (drop.on) { a.drop_thr = drop.thr; a.drop_key = c.keys[l]; a.drop_scale = drop.scale; a.row_offset = c.row_offset; }
+    TRY(launch_nt<EPI_FWD>(a, c.st));
   }
   return 0;
 }
 
-struct FuseAdam { const DsdfAdamCfg* cfg; float* params; float* exp_avg; float* exp_avg_sq; float* packed; };
+struct FuseAdam { const DsdfAdamCfg* cfg; float* params; float* exp_avg; float* exp_avg_sq; float* packed; bool used; };
 
 // Where a layer's weight gradient comes from: its split-K slabs and the column-sum partials that are its bias gradient
 struct FinSrc { const float* slabs; int nsplit; long long slab; int ldc; const float* colsum; int npart; int ldcs; };
 // One layer's finalize descriptor: slab sums, weight-norm backward and bias gradient into the gradient arena -- or, fz != nullptr
 // (dsdf_train_step), consumed on the spot by Adam, which also writes the row's new weight-norm scale
-FinArgs fin_args(const DsdfNet* net, const DsdfParamLayout& L, const Packed& pk, int l, const FinSrc& src, const float* params,
-                 float* grads, int accumulate, const FuseAdam* fz = nullptr) {
+// ... and where it goes: the gradient arena (added to what is there, or not), or straight into Adam
+struct GradSink { float* grads; int accumulate; const FuseAdam* fz; };
+FinArgs fin_args(const Call& c, int l, const FinSrc& src, const GradSink& to) {
   FinArgs f;
   memset(&f, 0, sizeof(f));
   f.slabs = src.slabs; f.nsplit = src.nsplit; f.slab = src.slab; f.ldc = src.ldc;
   f.colsum = src.colsum; f.npart = src.npart; f.ldcs = src.ldcs;
-  f.g = L.g_off[l] >= 0 ? params + L.g_off[l] : nullptr;
-  f.v = params + L.v_off[l];
-  f.dg = L.g_off[l] >= 0 ? grads + L.g_off[l] : nullptr;
-  f.dv = grads + L.v_off[l];
-  f.db = grads + L.bias_off[l];
-  f.out = net->out_dim[l]; f.in = net->in_dim[l]; f.accumulate = accumulate;
-  if (fz != nullptr) {
-    const DsdfAdamCfg* c = fz->cfg;
-    const double bc1 = 1.0 - pow((double)c->beta1, (double)c->step), bc2 = 1.0 - pow((double)c->beta2, (double)c->step);
+  f.g = c.L.g_off[l] >= 0 ? c.params + c.L.g_off[l] : nullptr;
+  f.v = c.params + c.L.v_off[l];
+  f.dg = c.L.g_off[l] >= 0 ? to.grads + c.L.g_off[l] : nullptr;
+  f.dv = to.grads + c.L.v_off[l];
+  f.db = to.grads + c.L.bias_off[l];
+  f.out = c.net->out_dim[l]; f.in = c.net->in_dim[l]; f.accumulate = to.accumulate;
+  if (to.fz != nullptr) {
+    const DsdfAdamCfg* ad = to.fz->cfg;
+    const double bc1 = 1.0 - pow((double)ad->beta1, (double)ad->step), bc2 = 1.0 - pow((double)ad->beta2, (double)ad->step);
     f.adam = 1;
-    f.pb = fz->params + L.bias_off[l]; f.mb = fz->exp_avg + L.bias_off[l]; f.sb = fz->exp_avg_sq + L.bias_off[l];
-    f.pv = fz->params + L.v_off[l];    f.mv = fz->exp_avg + L.v_off[l];    f.sv = fz->exp_avg_sq + L.v_off[l];
-    if (L.g_off[l] >= 0) { f.pg = fz->params + L.g_off[l]; f.mg = fz->exp_avg + L.g_off[l]; f.sg = fz->exp_avg_sq + L.g_off[l]; }
+    f.pb = to.fz->params + c.L.bias_off[l]; f.mb = to.fz->exp_avg + c.L.bias_off[l]; f.sb = to.fz->exp_avg_sq + c.L.bias_off[l];
+    f.pv = to.fz->params + c.L.v_off[l];    f.mv = to.fz->exp_avg + c.L.v_off[l];    f.sv = to.fz->exp_avg_sq + c.L.v_off[l];
+    if (c.L.g_off[l] >= 0) { f.pg = to.fz->params + c.L.g_off[l]; f.mg = to.fz->exp_avg + c.L.g_off[l]; f.sg = to.fz->exp_avg_sq + c.L.g_off[l]; }
     int r0 = 0;
-    for (int q = 0; q < l; ++q) r0 += net->out_dim[q];
-    f.scale_out = fz->packed + pk.scale_off + r0;
-    f.omb1 = 1.0f - c->beta1; f.b2 = c->beta2; f.omb2 = 1.0f - c->beta2;
-    f.step_size = (float)((double)c->lr_decoder / bc1); f.bc2_sqrt = (float)sqrt(bc2); f.eps = c->eps;
+    for (int q = 0; q < l; ++q) r0 += c.net->out_dim[q];
+    f.scale_out = to.fz->packed + c.pk.scale_off + r0;
+    f.omb1 = 1.0f - ad->beta1; f.b2 = ad->beta2; f.omb2 = 1.0f - ad->beta2;
+    f.step_size = (float)((double)ad->lr_decoder / bc1); f.bc2_sqrt = (float)sqrt(bc2); f.eps = ad->eps;
   }
   return f;
 }
 
 // d_input [n][W0] = dzA (+ dzB): the x0 gradients of layer 0 and of the skip layer
-int add_dz_to_input(const Plan& P, void* ws, int64_t n, bool used_dzB, float* d_input, int64_t ld_din, hipStream_t st) {
-  const long long tot = (long long)n * P.W0;
-  hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dzA_off), P.ldz,
-                     used_dzB ? at<float>(ws, P.dzB_off) : nullptr, P.ldz, d_input, (long long)ld_din, (int)n, P.W0);
+int add_dz_to_input(const Call& c, bool used_dzB, float* d_input, int64_t ld_din) {
+  const long long tot = (long long)c.n * c.P.W0;
+  hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.st, c.at<float>(c.P.dzA_off), c.P.ldz,
+                     used_dzB ? c.at<float>(c.P.dzB_off) : nullptr, c.P.ldz, d_input, (long long)ld_din, (int)c.n, c.P.W0);
   LAUNCH_OK("add2_kernel");
   return 0;
 }
 
-// The output layer's arguments every mode shares; callers add their mode's fields
-LastArgs last_args(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* params, int64_t n) {
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1;
+// The output layer's arguments every mode shares; callers add their mode's fields.  backward: and what the two backward modes
+// (training, module) share -- dP of the last hidden layer and the per-block partials
+LastArgs last_args(const Call& c, bool backward = false) {
+  const int last = c.net->n_layers - 1;
   LastArgs a;
   memset(&a, 0, sizeof(a));
-  a.a = at<float>(ws, P.in_off[last]); a.lda = P.ld_in[last]; a.in = net->in_dim[last];
-  a.w = packed + pk.w_off[last]; a.b = params + L.bias_off[last]; a.n = (int)n; a.use_tanh = net->use_tanh;
+  a.a = c.at<float>(c.P.in_off[last]); a.lda = c.P.ld_in[last]; a.in = c.net->in_dim[last];
+  a.w = c.packed + c.pk.w_off[last]; a.b = c.params + c.L.bias_off[last]; a.n = (int)c.n; a.use_tanh = c.net->use_tanh;
+  if (!backward) return a;
+  a.dp_prev = c.at<float>(c.P.dp_off[0]);
+  a.lddp = c.P.ld_dp; a.mask_scale = mask_scale_of(c.net, last - 1, c.training);
+  a.part_dw = c.at<float>(c.P.part_off); a.ld_part = c.P.ld_part;
+  a.part_colsum = c.at<float>(c.P.part_off) + c.P.ld_in[last];
+  a.part_db = c.at<float>(c.P.partdb_off); a.part_loss = c.at<float>(c.P.partloss_off);
+  a.n_act = c.net->out_dim[last - 1];
   return a;
-}
-// ... and what the two backward modes (training, module) share: dP of the last hidden layer and the per-block partials
-void last_args_backward(LastArgs& a, const DsdfNet* net, const Plan& P, void* ws, int training) {
-  const int last = net->n_layers - 1;
-  a.dp_prev = at<float>(ws, P.dp_off[0]);
-  a.lddp = P.ld_dp; a.mask_scale = mask_scale_of(net, last - 1, training);
-  a.part_dw = at<float>(ws, P.part_off); a.ld_part = P.ld_part;
-  a.part_colsum = at<float>(ws, P.part_off) + P.ld_in[last];
-  a.part_db = at<float>(ws, P.partdb_off); a.part_loss = at<float>(ws, P.partloss_off);
-  a.n_act = net->out_dim[last - 1];
 }
 
 // shared backward over hidden layers, given dp of layer nl-2 in dp[0] and the last layer's partials.
 // ncols_dz: how many leading x0 columns of d/dx0 are needed (L for training, W0 for the module path).
-// keys / row_offset: latent_dropout nets mask the latent part of layer 0's dX (dzA) with the forward's hash.
+// c.keys / c.row_offset: latent_dropout nets mask the latent part of layer 0's dX (dzA) with the forward's hash.
 // xyz_acc != nullptr (xyz_in_all, module path with d/d(input)): *xyz_acc = true when dxz_off[1] holds the sum of the xyz_in
 // layers' d/d(xyz) (the caller adds it to the xyz columns of d_input).
-int run_backward(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* params, int64_t n,
-                 int training, float* grads, int accumulate, int ncols_dz, bool* used_dzB, hipStream_t st, bool want_dw = true,
-                 const uint32_t* keys = nullptr, uint32_t row_offset = 0, bool* xyz_acc = nullptr) {
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int nl = net->n_layers;
-  const int last = nl - 1;
+int run_backward(const Call& c, const GradSink& to, int ncols_dz, bool* used_dzB, bool want_dw, bool* xyz_acc = nullptr) {
+  const int last = c.net->n_layers - 1;
   // second stage of the last layer's partials
   if (want_dw) {
-    const int w = P.ld_part;
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((w + 63) / 64, LAST_GROUPS), dim3(256), 0, st,
-                       ReduceRowsArgs{at<float>(ws, P.part_off), P.last_blocks, P.ld_part, w, at<float>(ws, P.part2_off), LAST_GROUPS});
+    const int w = c.P.ld_part;
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3((w + 63) / 64, LAST_GROUPS), dim3(256), 0, c.st,
+                       ReduceRowsArgs{c.at<float>(c.P.part_off), c.P.last_blocks, c.P.ld_part, w, c.at<float>(c.P.part2_off), LAST_GROUPS});
     LAUNCH_OK("reduce_rows_kernel");
-    const FinSrc src{at<float>(ws, P.part2_off), LAST_GROUPS, P.ld_part, P.ld_part, at<float>(ws, P.partdb_off), P.last_blocks, 1};
-    const FinArgs f = fin_args(net, L, pk, last, src, params, grads, accumulate);      // (out_dim[last] == 1: one block)
-    hipLaunchKernelGGL(finalize_layer_kernel, dim3(1), dim3(256), 0, st, f);
+    const FinSrc src{c.at<float>(c.P.part2_off), LAST_GROUPS, c.P.ld_part, c.P.ld_part, c.at<float>(c.P.partdb_off), c.P.last_blocks, 1};
+    const FinArgs f = fin_args(c, last, src, to);      // (out_dim[last] == 1: one block)
+    hipLaunchKernelGGL(finalize_layer_kernel, dim3(1), dim3(256), 0, c.st, f);
     LAUNCH_OK("finalize_layer_kernel(last)");
-    if ((net->ln_param_mask >> last) & 1) {   // bn module of the last Linear: created by the reference, never called: zero gradient
+    if ((c.net->ln_param_mask >> last) & 1) {   // bn module of the last Linear: created by the reference, never called: zero gradient
       LnGradArgs z;
       memset(&z, 0, sizeof(z));
-      z.dgamma = grads + L.ln_w_off[last]; z.dbeta = grads + L.ln_b_off[last]; z.width = net->out_dim[last]; z.accumulate = accumulate; z.zero = 1;
-      hipLaunchKernelGGL(ln_param_grad_kernel, dim3(1), dim3(64), 0, st, z);
+      z.dgamma = to.grads + c.L.ln_w_off[last]; z.dbeta = to.grads + c.L.ln_b_off[last]; z.width = c.net->out_dim[last]; z.accumulate = to.accumulate; z.zero = 1;
+      hipLaunchKernelGGL(ln_param_grad_kernel, dim3(1), dim3(64), 0, c.st, z);
       LAUNCH_OK("ln_param_grad_kernel(last)");
     }
   }
   *used_dzB = false;
   int cur = 0;
   for (int l = last - 1; l >= 0; --l) {
-    float* dp = at<float>(ws, P.dp_off[cur]);
+    float* dp = c.at<float>(c.P.dp_off[cur]);
     // column-sum partials of dp as it arrives (from the output layer's kernel or the next layer's dX epilogue)
-    const float* cs_ptr = l == last - 1 ? at<float>(ws, P.part2_off) + P.ld_in[last] : at<float>(ws, P.colsum_off);
-    int cs_n = l == last - 1 ? LAST_GROUPS : P.mt, cs_ld = l == last - 1 ? P.ld_part : P.ldcs;
-    const bool ln = ln_applied(net, l);
+    const float* cs_ptr = l == last - 1 ? c.at<float>(c.P.part2_off) + c.P.ld_in[last] : c.at<float>(c.P.colsum_off);
+    int cs_n = l == last - 1 ? LAST_GROUPS : c.P.mt, cs_ld = l == last - 1 ? c.P.ld_part : c.P.ldcs;
+    const bool ln = ln_applied(c.net, l);
     if (ln) {   // dp is d/dz (after LayerNorm): turn it into d/d(Linear output) in place; gamma / beta / bias partials
       LnBwdArgs b;
       memset(&b, 0, sizeof(b));
-      b.dz = dp; b.ldz = P.ld_dp; b.xhat = at<float>(ws, P.lnx_off[l]); b.ldx = P.ld_in[l + 1]; b.rstd = at<float>(ws, P.lnr_off[l]);
-      b.gamma = params + L.ln_w_off[l]; b.n = (int)n; b.width = net->out_dim[l];
-      b.part_dgamma = at<float>(ws, P.lnpg_off); b.part_db = at<float>(ws, P.lnpb_off); b.ldp = P.ldcs;
-      int blocks = (int)((n + 3) / 4);
+      b.dz = dp; b.ldz = c.P.ld_dp; b.xhat = c.at<float>(c.P.lnx_off[l]); b.ldx = c.P.ld_in[l + 1]; b.rstd = c.at<float>(c.P.lnr_off[l]);
+      b.gamma = c.params + c.L.ln_w_off[l]; b.n = (int)c.n; b.width = c.net->out_dim[l];
+      b.part_dgamma = c.at<float>(c.P.lnpg_off); b.part_db = c.at<float>(c.P.lnpb_off); b.ldp = c.P.ldcs;
+      int blocks = (int)((c.n + 3) / 4);
       if (blocks > LN_BLOCKS) blocks = LN_BLOCKS;
-      hipLaunchKernelGGL(ln_bwd_kernel, dim3(blocks), dim3(256), 0, st, b);
+      hipLaunchKernelGGL(ln_bwd_kernel, dim3(blocks), dim3(256), 0, c.st, b);
       LAUNCH_OK("ln_bwd_kernel");
       if (want_dw) {
         LnGradArgs g;
         memset(&g, 0, sizeof(g));
         g.part_dgamma = b.part_dgamma; g.nblk = blocks; g.ldp = b.ldp; g.cs = cs_ptr; g.ncs = cs_n; g.ldcs = cs_ld;
-        g.dgamma = grads + L.ln_w_off[l]; g.dbeta = grads + L.ln_b_off[l]; g.width = net->out_dim[l]; g.accumulate = accumulate;
-        hipLaunchKernelGGL(ln_param_grad_kernel, dim3((g.width + 255) / 256), dim3(256), 0, st, g);
+        g.dgamma = to.grads + c.L.ln_w_off[l]; g.dbeta = to.grads + c.L.ln_b_off[l]; g.width = c.net->out_dim[l]; g.accumulate = to.accumulate;
+        hipLaunchKernelGGL(ln_param_grad_kernel, dim3((g.width + 255) / 256), dim3(256), 0, c.st, g);
         LAUNCH_OK("ln_param_grad_kernel");
       }
       cs_ptr = b.part_db; cs_n = blocks; cs_ld = b.ldp;     // the Linear's bias gradient = column sums of dy
@@ -1011,47 +1007,47 @@ int run_backward(const DsdfNet* net, const Plan& P, void* ws, const float* packe
     if (want_dw) {
     TnArgs t;
     memset(&t, 0, sizeof(t));
-    t.A = dp; t.lda = P.ld_dp; t.B = at<float>(ws, P.in_off[l]); t.ldb = P.ld_in[l];
-    t.C = at<float>(ws, P.slab_off); t.ldc = P.ld_in[l]; t.M = net->out_dim[l]; t.N = net->in_dim[l]; t.K = (int)n;
-    t.kchunk = P.kchunk; t.slab = P.slab;
-    TRY(launch_tn(t, P.nsplit, st));
-    const FinArgs f = fin_args(net, L, pk, l, FinSrc{t.C, P.nsplit, P.slab, t.ldc, cs_ptr, cs_n, cs_ld}, params, grads, accumulate);
-    hipLaunchKernelGGL(finalize_layer_kernel, dim3(f.out), dim3(256), 0, st, f);
+    t.A = dp; t.lda = c.P.ld_dp; t.B = c.at<float>(c.P.in_off[l]); t.ldb = c.P.ld_in[l];
+    t.C = c.at<float>(c.P.slab_off); t.ldc = c.P.ld_in[l]; t.M = c.net->out_dim[l]; t.N = c.net->in_dim[l]; t.K = (int)c.n;
+    t.kchunk = c.P.kchunk; t.slab = c.P.slab;
+    TRY(launch_tn(t, c.P.nsplit, c.st));
+    const FinArgs f = fin_args(c, l, FinSrc{t.C, c.P.nsplit, c.P.slab, t.ldc, cs_ptr, cs_n, cs_ld}, to);
+    hipLaunchKernelGGL(finalize_layer_kernel, dim3(f.out), dim3(256), 0, c.st, f);
     LAUNCH_OK("finalize_layer_kernel");
     }
     // dX
     NtArgs a;
     memset(&a, 0, sizeof(a));
-    a.A = dp; a.lda = P.ld_dp; a.B = packed + pk.wt_off[l]; a.ldb = pk.ldwt[l];
-    a.M = (int)n; a.K = net->out_dim[l];
+    a.A = dp; a.lda = c.P.ld_dp; a.B = c.packed + c.pk.wt_off[l]; a.ldb = c.pk.ldwt[l];
+    a.M = (int)c.n; a.K = c.net->out_dim[l];
     if (l > 0) {
-      const bool skip = (net->skip_mask >> l) & 1;
-      a.C = at<float>(ws, P.dp_off[cur ^ 1]); a.ldc = P.ld_dp;
-      a.act = at<float>(ws, P.in_off[l]); a.ldact = P.ld_in[l];
-      a.mask_cols = net->out_dim[l - 1];
-      a.mask_scale = mask_scale_of(net, l - 1, training);
-      const bool xyz_l = !skip && net->xyz_in_all;                 // this layer's input is [a || xyz]
-      const bool want_xyz = xyz_l && xyz_acc != nullptr && ncols_dz > net->latent_size;
-      a.N = skip ? (ncols_dz > 0 ? a.mask_cols + ncols_dz : a.mask_cols) : (xyz_l ? a.mask_cols + (want_xyz ? net->geom_dim : 0) : net->in_dim[l]);
-      if (skip && ncols_dz > 0) { a.C2 = at<float>(ws, P.dzB_off); a.ldc2 = P.ldz; a.c2_cols = ncols_dz; *used_dzB = true; }
-      if (want_xyz) { a.C2 = at<float>(ws, P.dxz_off[0]); a.ldc2 = 4; a.c2_cols = net->geom_dim; }
-      a.colsum = at<float>(ws, P.colsum_off); a.ldcs = P.ldcs;
-      TRY(launch_nt<EPI_BWD>(a, st));
+      const bool skip = (c.net->skip_mask >> l) & 1;
+      a.C = c.at<float>(c.P.dp_off[cur ^ 1]); a.ldc = c.P.ld_dp;
+      a.act = c.at<float>(c.P.in_off[l]); a.ldact = c.P.ld_in[l];
+      a.mask_cols = c.net->out_dim[l - 1];
+      a.mask_scale = mask_scale_of(c.net, l - 1, c.training);
+      const bool xyz_l = !skip && c.net->xyz_in_all;                 // this layer's input is [a || xyz]
+      const bool want_xyz = xyz_l && xyz_acc != nullptr && ncols_dz > c.net->latent_size;
+      a.N = skip ? (ncols_dz > 0 ? a.mask_cols + ncols_dz : a.mask_cols) : (xyz_l ? a.mask_cols + (want_xyz ? c.net->geom_dim : 0) : c.net->in_dim[l]);
+      if (skip && ncols_dz > 0) { a.C2 = c.at<float>(c.P.dzB_off); a.ldc2 = c.P.ldz; a.c2_cols = ncols_dz; *used_dzB = true; }
+      if (want_xyz) { a.C2 = c.at<float>(c.P.dxz_off[0]); a.ldc2 = 4; a.c2_cols = c.net->geom_dim; }
+      a.colsum = c.at<float>(c.P.colsum_off); a.ldcs = c.P.ldcs;
+      TRY(launch_nt<EPI_BWD>(a, c.st));
       if (want_xyz) {
-        const long long tot = (long long)n * net->geom_dim;
-        hipLaunchKernelGGL(acc_cols_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dxz_off[0]), 4,
-                           at<float>(ws, P.dxz_off[1]), 4, 0, (int)n, net->geom_dim, *xyz_acc ? 1 : 0);
+        const long long tot = (long long)c.n * c.net->geom_dim;
+        hipLaunchKernelGGL(acc_cols_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.st, c.at<float>(c.P.dxz_off[0]), 4,
+                           c.at<float>(c.P.dxz_off[1]), 4, 0, (int)c.n, c.net->geom_dim, *xyz_acc ? 1 : 0);
         LAUNCH_OK("acc_cols_kernel");
         *xyz_acc = true;
       }
       cur ^= 1;
     } else if (ncols_dz > 0) {
-      a.C = at<float>(ws, P.dzA_off); a.ldc = P.ldz; a.N = ncols_dz;
-      TRY(launch_nt<EPI_PLAIN>(a, st));
-      if (net->latent_dropout && training && keys != nullptr && net->latent_size > 0) {   // layer 0 saw the DROPPED latent
-        const long long tot = (long long)n * net->latent_size;
-        hipLaunchKernelGGL(latent_drop_bwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dzA_off), P.ldz,
-                           (int)n, net->latent_size, keys[LATENT_DROPOUT_KEY], latent_drop_thr(), 1.0f / (1.0f - LATENT_DROPOUT_P), row_offset);
+      a.C = c.at<float>(c.P.dzA_off); a.ldc = c.P.ldz; a.N = ncols_dz;
+      TRY(launch_nt<EPI_PLAIN>(a, c.st));
+      if (c.net->latent_dropout && c.training && c.keys != nullptr && c.net->latent_size > 0) {   // layer 0 saw the DROPPED latent
+        const long long tot = (long long)c.n * c.net->latent_size;
+        hipLaunchKernelGGL(latent_drop_bwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.st, c.at<float>(c.P.dzA_off), c.P.ldz,
+                           (int)c.n, c.net->latent_size, c.keys[LATENT_DROPOUT_KEY], latent_drop_thr(), 1.0f / (1.0f - LATENT_DROPOUT_P), c.row_offset);
         LAUNCH_OK("latent_drop_bwd_kernel");
       }
     }
@@ -1072,75 +1068,72 @@ struct SegBwd { const FusedSeg* seg; const int64_t* seg_scene; const float* tabl
 inline bool in_phase(const Plan& P, int phase, int l) { return phase == 0 || (l >= P.dw_cut[phase] && l < P.dw_cut[phase - 1]); }
 
 // (1) The dX chain's arguments: one descriptor per layer, deepest first (layer 0 only when d/dx0 is wanted: ncols_dz > 0)
-FusedBwdArgs dx_chain_args(const DsdfNet* net, const Plan& P, void* ws, const float* packed, int64_t n, int training, int ncols_dz,
-                           bool want_dw, const FusedBwdHead& head, const SegBwd* sb, bool* used_dzB) {
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1, ks = skip_layer(net);
+FusedBwdArgs dx_chain_args(const Call& c, int ncols_dz, bool want_dw, const FusedBwdHead& head, const SegBwd* sb, bool* used_dzB) {
+  const int last = c.net->n_layers - 1, ks = skip_layer(c.net);
   const bool segmode = sb != nullptr;
   *used_dzB = false;
   FusedBwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.N = (int)n;
+  a.N = (int)c.n;
   a.head = head;
   if (segmode) { a.xyz = sb->seg->xyz; a.G = sb->seg->G; }
   int cnt = 0;
   for (int l = last - 1; l >= 0; --l) {
     if (l == 0 && ncols_dz <= 0) break;
     FusedBwdLayer& y = a.ly[cnt++];
-    y.wtf = net->gemm_split ? packed + pk.wts_off[l] : packed + pk.wtf_off[l]; y.U = pk.utf[l]; y.K = net->out_dim[l];
-    y.wplane = (int)(pk.wts_plane[l] * 2);
-    y.wtf32 = packed + pk.wtf_off[l];
+    y.wtf = c.net->gemm_split ? c.packed + c.pk.wts_off[l] : c.packed + c.pk.wtf_off[l]; y.U = c.pk.utf[l]; y.K = c.net->out_dim[l];
+    y.wplane = (int)(c.pk.wts_plane[l] * 2);
+    y.wtf32 = c.packed + c.pk.wtf_off[l];
     if (l > 0) {
-      const bool skip = (net->skip_mask >> l) & 1;
-      y.mask_cols = net->out_dim[l - 1];
-      y.mask_scale = mask_scale_of(net, l - 1, training);
-      y.maskbits = at<uint32_t>(ws, P.mask_off[l - 1]);
-      y.dp_out = at<float>(ws, P.dpl_off[l - 1]); y.ld_dp = P.ld_dp;
-      y.colsum = at<float>(ws, P.cs_off[l - 1]); y.ldcs = P.ldcs;
-      if (segmode && want_dw && (l - 1 == 0 || l - 1 == ks)) y.xsum = at<float>(ws, P.xsum_off[l - 1 == 0 ? 0 : 1]);
+      const bool skip = (c.net->skip_mask >> l) & 1;
+      y.mask_cols = c.net->out_dim[l - 1];
+      y.mask_scale = mask_scale_of(c.net, l - 1, c.training);
+      y.maskbits = c.at<uint32_t>(c.P.mask_off[l - 1]);
+      y.dp_out = c.at<float>(c.P.dpl_off[l - 1]); y.ld_dp = c.P.ld_dp;
+      y.colsum = c.at<float>(c.P.cs_off[l - 1]); y.ldcs = c.P.ldcs;
+      if (segmode && want_dw && (l - 1 == 0 || l - 1 == ks)) y.xsum = c.at<float>(c.P.xsum_off[l - 1 == 0 ? 0 : 1]);
       if (segmode && l - 1 == 0) y.dp_out = nullptr;   // dP_0 is consumed through its column sums only
-      if (skip && ncols_dz > 0) { y.dz_out = at<float>(ws, P.dzB_off); y.ldz = P.ldz; y.dz_cols = ncols_dz; *used_dzB = true; }
+      if (skip && ncols_dz > 0) { y.dz_out = c.at<float>(c.P.dzB_off); y.ldz = c.P.ldz; y.dz_cols = ncols_dz; *used_dzB = true; }
       y.ncols = y.mask_cols + y.dz_cols;
     } else {
       y.mask_cols = 0; y.mask_scale = 1.f;
-      y.dz_out = at<float>(ws, P.dzA_off); y.ldz = P.ldz; y.dz_cols = ncols_dz; y.ncols = ncols_dz;
+      y.dz_out = c.at<float>(c.P.dzA_off); y.ldz = c.P.ldz; y.dz_cols = ncols_dz; y.ncols = ncols_dz;
     }
   }
   a.n_layers = cnt;
-  if (last_layer_skip(net)) {   // the head hands the x0 columns' gradient du w[x0 cols] to the skip-layer buffer of d/dx0
-    a.head.dz_out = ncols_dz > 0 ? at<float>(ws, P.dzB_off) : nullptr; a.head.ldz = P.ldz; a.head.dz_cols = ncols_dz;
+  if (last_layer_skip(c.net)) {   // the head hands the x0 columns' gradient du w[x0 cols] to the skip-layer buffer of d/dx0
+    a.head.dz_out = ncols_dz > 0 ? c.at<float>(c.P.dzB_off) : nullptr; a.head.ldz = c.P.ldz; a.head.dz_cols = ncols_dz;
     if (ncols_dz > 0) *used_dzB = true;
   }
   return a;
 }
 
 // (2) The dX chain's launch: merged with the deferred forward of the same points (fwd != nullptr), or the backward alone
-int launch_dx_chain(const DsdfNet* net, const Path& path, const Plan& P, int64_t n, FusedBwdArgs& a, const FusedFwdArgs* fwd,
-                    hipStream_t st) {
+int launch_dx_chain(const Call& c, FusedBwdArgs& a, const FusedFwdArgs* fwd) {
   // algorithmic FLOPs of the dX chain (the reference back-propagates through every hidden layer down to x0); the executed count is
   // smaller: layer 0's dX and the skip layer's x0 columns come from column sums instead
   double amac = 0;
-  for (int l = 0; l < net->n_layers - 1; ++l) amac += (double)net->in_dim[l] * net->out_dim[l];
-  const FamilyKernels& k = KERNELS[path.family];
-  const dim3 grid((unsigned)P.nwg), block(k.block);
+  for (int l = 0; l < c.net->n_layers - 1; ++l) amac += (double)c.net->in_dim[l] * c.net->out_dim[l];
+  const FamilyKernels& k = KERNELS[c.path.family];
+  const dim3 grid((unsigned)c.P.nwg), block(k.block);
   if (fwd != nullptr) {
-    if (k.fwd_bwd == nullptr) return fail(DSDF_E_LAUNCH, "internal: kernel family %d has no merged forward + backward", (int)path.family);
+    if (k.fwd_bwd == nullptr) return fail(DSDF_E_LAUNCH, "internal: kernel family %d has no merged forward + backward", (int)c.path.family);
 #ifdef DSDF_LAB
     // lab: stamps of the MERGED launch (forward slots 0.., backward slots 32..), dumped after every launch
     static LabStamps stamps{"DSDF_LAB_MDBG", 8192 * 64 * 8, true, nullptr};
-    LabScope lab(stamps, st);
+    LabScope lab(stamps, c.st);
     FusedFwdArgs fwd_l = *fwd;
     if (stamps.dev) { fwd_l.dbg = stamps.dev; a.dbg = stamps.dev; fwd = &fwd_l; }
 #endif
-    ProfScope ps(DSDF_PROF_FUSED_FWD_BWD, 4.0 * (double)n * amac, st);   // forward + dX chain
-    hipLaunchKernelGGL(k.fwd_bwd, grid, block, 0, st, *fwd, a);
+    ProfScope ps(DSDF_PROF_FUSED_FWD_BWD, 4.0 * (double)c.n * amac, c.st);   // forward + dX chain
+    hipLaunchKernelGGL(k.fwd_bwd, grid, block, 0, c.st, *fwd, a);
     LAUNCH_OK("fused_fwd_bwd_kernel");
     return 0;
   }
-  ProfScope ps(DSDF_PROF_FUSED_BWD, 2.0 * (double)n * amac, st);
-  if (path.frows != FROWS || k.bwd == nullptr)
+  ProfScope ps(DSDF_PROF_FUSED_BWD, 2.0 * (double)c.n * amac, c.st);
+  if (c.path.frows != FROWS || k.bwd == nullptr)
     return fail(DSDF_E_LAUNCH, "internal: the separate backward kernel has 64-row workgroups only");
-  hipLaunchKernelGGL(k.bwd, grid, block, 0, st, a);
+  hipLaunchKernelGGL(k.bwd, grid, block, 0, c.st, a);
   LAUNCH_OK("fused_backward_kernel");
   return 0;
 }
@@ -1155,15 +1148,13 @@ struct Roles {
   int cus, dw_items, dw_busy;        // the dW launch: its items and the workgroups they keep busy
   bool rides;
 };
-Roles plan_roles(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const DwSched& DS, bool want_dw, const SegBwd* sb,
-                 int phase) {
-  const Packed pk = packed_layout(net);
-  const int ks = skip_layer(net);
+Roles plan_roles(const Call& c, const DwSched& DS, bool want_dw, const SegBwd* sb, int phase) {
+  const int ks = skip_layer(c.net);
   const bool segmode = sb != nullptr;
   Roles R;
   memset(&R, 0, sizeof(R));
-  R.rr = ReduceRowsArgs{at<float>(ws, P.part_off), P.nwg, P.ld_part, P.ld_part, at<float>(ws, P.part2_off), LAST_GROUPS};
-  R.rr_bx = (P.ld_part + 63) / 64;
+  R.rr = ReduceRowsArgs{c.at<float>(c.P.part_off), c.P.nwg, c.P.ld_part, c.P.ld_part, c.at<float>(c.P.part2_off), LAST_GROUPS};
+  R.rr_bx = (c.P.ld_part + 63) / 64;
   R.lat_slices = 1;
   PostBwdArgs& q = R.q;
   if (segmode) {
@@ -1171,31 +1162,31 @@ Roles plan_roles(const DsdfNet* net, const Plan& P, void* ws, const float* packe
       q.rr = R.rr; q.rr_bx = R.rr_bx; q.rr_n = R.rr_bx * LAST_GROUPS;
       SegDwArgs& d = q.dw;
       d.nh = ks > 0 ? 2 : 1;
-      d.cs[0] = at<float>(ws, P.cs_off[0]); d.xsum[0] = at<float>(ws, P.xsum_off[0]); d.out[0] = net->out_dim[0];
-      if (ks > 0) { d.cs[1] = at<float>(ws, P.cs_off[ks]); d.xsum[1] = at<float>(ws, P.xsum_off[1]); d.out[1] = net->out_dim[ks]; }
-      d.ldcs = P.ldcs; d.nwg = P.nwg; d.wg_per_seg = sb->seg->wg_per_seg; d.R = sb->R; d.L = net->latent_size; d.G = net->geom_dim;
+      d.cs[0] = c.at<float>(c.P.cs_off[0]); d.xsum[0] = c.at<float>(c.P.xsum_off[0]); d.out[0] = c.net->out_dim[0];
+      if (ks > 0) { d.cs[1] = c.at<float>(c.P.cs_off[ks]); d.xsum[1] = c.at<float>(c.P.xsum_off[1]); d.out[1] = c.net->out_dim[ks]; }
+      d.ldcs = c.P.ldcs; d.nwg = c.P.nwg; d.wg_per_seg = sb->seg->wg_per_seg; d.R = sb->R; d.L = c.net->latent_size; d.G = c.net->geom_dim;
       d.seg_scene = sb->seg_scene; d.table = sb->table; d.zr = sb->zr;
-      d.HS = at<float>(ws, P.hs_off); d.ldh = P.ldh; d.hstride = P.hstride;
+      d.HS = c.at<float>(c.P.hs_off); d.ldh = c.P.ldh; d.hstride = c.P.hstride;
       // (block counts of the launch-of-its-own form; the riding form below has its own)
       q.dw_n = (d.out[0] + SDW_ROWS_WIDE - 1) / SDW_ROWS_WIDE + (ks > 0 ? (d.out[1] + SDW_ROWS_WIDE - 1) / SDW_ROWS_WIDE : 0);
       if (seg_dw_long_form(d.wg_per_seg, d.out[0], d.out[1])) q.dw_n = d.out[0] + d.out[1];      // long segments, narrow layers: one row per block (seg_dw_row_body)
     }
     SegLatArgs& g = q.lat;   // per-segment latent gradient from the column sums of dP_0 / dP_skip
-    g.cs0 = at<float>(ws, P.cs_off[0]); g.ldcs = P.ldcs; g.out0 = net->out_dim[0];
-    g.W0 = packed + pk.w_off[0]; g.ldw0 = pk.ldw[0];
+    g.cs0 = c.at<float>(c.P.cs_off[0]); g.ldcs = c.P.ldcs; g.out0 = c.net->out_dim[0];
+    g.W0 = c.packed + c.pk.w_off[0]; g.ldw0 = c.pk.ldw[0];
     if (ks > 0) {
-      g.csk = at<float>(ws, P.cs_off[ks]); g.outk = net->out_dim[ks];
-      g.Wk = packed + pk.w_off[ks]; g.ldwk = pk.ldw[ks]; g.koff = net->out_dim[ks - 1];
+      g.csk = c.at<float>(c.P.cs_off[ks]); g.outk = c.net->out_dim[ks];
+      g.Wk = c.packed + c.pk.w_off[ks]; g.ldwk = c.pk.ldw[ks]; g.koff = c.net->out_dim[ks - 1];
     }
-    g.wg_per_seg = sb->seg->wg_per_seg; g.R = sb->R; g.L = net->latent_size;
+    g.wg_per_seg = sb->seg->wg_per_seg; g.R = sb->R; g.L = c.net->latent_size;
     g.seg_scene = sb->seg_scene; g.table = sb->table; g.zr = sb->zr;
-    g.segpart = at<float>(ws, P.segpart_off); g.segnorm = at<float>(ws, P.segnorm_off);
+    g.segpart = c.at<float>(c.P.segpart_off); g.segnorm = c.at<float>(c.P.segnorm_off);
     q.lat_bx = sb->R;
-    g.nchunk = (net->latent_size + 15) / 16;
+    g.nchunk = (c.net->latent_size + 15) / 16;
     R.lat_n = sb->R * g.nchunk;
     // few long segments in a launch of their own (config 4: one shape): cut each segment's workgroups into slices so that the launch
     // has blocks for the chip; the scatter adds the slices
-    g.nslice = 1; g.slice_stride = (long long)sb->R * net->latent_size;
+    g.nslice = 1; g.slice_stride = (long long)sb->R * c.net->latent_size;
     while (g.nslice < LAT_SLICES_MAX && R.lat_n * g.nslice * 2 <= chip_waves() / 4 && g.wg_per_seg / (g.nslice * 2) >= 16) g.nslice *= 2;
     R.lat_n *= g.nslice;
     R.lat_slices = g.nslice;
@@ -1213,12 +1204,12 @@ Roles plan_roles(const DsdfNet* net, const Plan& P, void* ws, const float* packe
   // seg_latgrad_all_body: one block per 16 latent columns takes all segments): they now end 242 us into the launch.
   // (gemm_split: measured again with the rebuilt roles -- they end 242 us into the launch, the split items 174 us: riding there made
   // the launch 253 us instead of 174 + 18 for a launch of their own, so they still do not ride in split mode)
-  R.rides = segmode && want_dw && R.cus - R.dw_busy >= 8 && P.nwg <= R.cus && !no_ride && !net->gemm_split && phase <= 1 &&
+  R.rides = segmode && want_dw && R.cus - R.dw_busy >= 8 && c.P.nwg <= R.cus && !no_ride && !c.net->gemm_split && phase <= 1 &&
             R.dw_items > 0;
   if (R.rides) {   // the few-workgroups forms: 32 weight-gradient rows per block, one latent-gradient block per 16 columns
     q.lat.nslice = 1; R.lat_slices = 1;
     q.lat_bx = 0;
-    R.lat_n = (net->latent_size + 15) / 16;
+    R.lat_n = (c.net->latent_size + 15) / 16;
     q.rr_n = q.rr_bx;               // one block per 64-column strip of the head's partials takes all groups (reduce_rows_strip_body)
     q.dw_n = (q.dw.out[0] + SDW_ROWS_RIDE - 1) / SDW_ROWS_RIDE + (ks > 0 ? (q.dw.out[1] + SDW_ROWS_RIDE - 1) / SDW_ROWS_RIDE : 0);
   }
@@ -1226,37 +1217,36 @@ Roles plan_roles(const DsdfNet* net, const Plan& P, void* ws, const float* packe
 }
 
 // (4) All dW_l = dP_l^T a_l (of this phase's layers) in one launch; the riding roles go to the workgroups its items leave idle
-int launch_dw(const DsdfNet* net, const Path& path, const Plan& P, void* ws, int64_t n, const DwSched& DS, const Roles& R, bool segmode,
-              int phase, hipStream_t st) {
-  const int last = net->n_layers - 1;
+int launch_dw(const Call& c, const DwSched& DS, const Roles& R, bool segmode, int phase) {
+  const int last = c.net->n_layers - 1;
   DwArgs d;
   memset(&d, 0, sizeof(d));
-  d.n_layers = last; d.n_full = DS.n_full; d.n_narrow = DS.n_narrow; d.N = (int)n;
+  d.n_layers = last; d.n_full = DS.n_full; d.n_narrow = DS.n_narrow; d.N = (int)c.n;
   double fl = 0;
   for (int l = 0; l < last; ++l) {
     DwLayer& y = d.ly[l];
-    y.dp = at<float>(ws, P.dpl_off[l]); y.ld_dp = P.ld_dp;
-    y.act = at<float>(ws, P.in_off[l]); y.ld_act = P.ld_in[l];
-    y.slabs = at<float>(ws, P.dwslab_off[l]); y.slab = DS.slab[l];
-    y.M = net->out_dim[l]; y.Nc = dw_cols(net, l, segmode); y.ldc = P.ld_in[l];
+    y.dp = c.at<float>(c.P.dpl_off[l]); y.ld_dp = c.P.ld_dp;
+    y.act = c.at<float>(c.P.in_off[l]); y.ld_act = c.P.ld_in[l];
+    y.slabs = c.at<float>(c.P.dwslab_off[l]); y.slab = DS.slab[l];
+    y.M = c.net->out_dim[l]; y.Nc = dw_cols(c.net, l, segmode); y.ldc = c.P.ld_in[l];
     y.tiles_m = DS.tiles_m[l]; y.tiles_n = DS.tiles_n[l]; y.last_nj = DS.last_nj[l]; y.nfull_n = DS.nfull_n[l];
     y.nsplit = DS.nsplit[l]; y.kchunk = DS.kchunk[l]; y.full0 = DS.full0[l]; y.narrow0 = DS.narrow0[l];
-    if (in_phase(P, phase, l)) fl += 2.0 * (double)n * y.M * net->in_dim[l];   // algorithmic (segment mode executes fewer: hoisted x0 columns)
+    if (in_phase(c.P, phase, l)) fl += 2.0 * (double)c.n * y.M * c.net->in_dim[l];   // algorithmic (segment mode executes fewer: hoisted x0 columns)
   }
 #ifdef DSDF_LAB
   static LabStamps stamps{"DSDF_LAB_DWDBG", 1024 * 4 * 8 * 8, true, nullptr};      // lab: per-wave stamps of the LAST dW launch, dumped at every launch
-  LabScope lab(stamps, st);
+  LabScope lab(stamps, c.st);
   d.dbg = stamps.dev;
 #endif
-  ProfScope ps(DSDF_PROF_DW_STREAM, fl, st);
-  const DwKernel kernel = KERNELS[path.family].dw;
+  ProfScope ps(DSDF_PROF_DW_STREAM, fl, c.st);
+  const DwKernel kernel = KERNELS[c.path.family].dw;
   if (R.rides) {
-    hipLaunchKernelGGL(kernel, dim3(R.cus), dim3(256), 0, st, d, R.q, R.lat_n, R.dw_busy);
+    hipLaunchKernelGGL(kernel, dim3(R.cus), dim3(256), 0, c.st, d, R.q, R.lat_n, R.dw_busy);
   } else {
     PostBwdArgs none;
     memset(&none, 0, sizeof(none));
     const int grid = R.dw_busy < 1 ? 1 : R.dw_busy;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, d, none, 0, grid);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, c.st, d, none, 0, grid);
   }
   LAUNCH_OK("dw_stream_kernel");
   return 0;
@@ -1264,26 +1254,22 @@ int launch_dw(const DsdfNet* net, const Path& path, const Plan& P, void* ws, int
 
 // (5) The finalize table: split-K sums, weight-norm backward and bias gradients [+ Adam] of ALL of this phase's layers (last layer
 // included), one launch.  Returns the launch's block count (0: an empty bucket -- fewer layers than buckets).
-int fin_table(const DsdfNet* net, const Plan& P, void* ws, const DwSched& DS, const float* params, float* grads, int accumulate,
-              const FuseAdam* fz, bool segmode, int phase, FinAll* fa) {
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1, ks = skip_layer(net);
+int fin_table(const Call& c, const DwSched& DS, const GradSink& to, bool segmode, int phase, FinAll* fa) {
+  const int last = c.net->n_layers - 1, ks = skip_layer(c.net);
   memset(fa, 0, sizeof(*fa));
   int rows = 0;      // counts BLOCKS of the finalize launch
   for (int l = last; l >= 0; --l) {
-    if (!in_phase(P, phase, l)) continue;
+    if (!in_phase(c.P, phase, l)) continue;
     FinSrc src;
-    if (l == last) src = FinSrc{at<float>(ws, P.part2_off), LAST_GROUPS, P.ld_part, P.ld_part, at<float>(ws, P.partdb_off), P.nwg, 1};
+    if (l == last) src = FinSrc{c.at<float>(c.P.part2_off), LAST_GROUPS, c.P.ld_part, c.P.ld_part, c.at<float>(c.P.partdb_off), c.P.nwg, 1};
     else if (l == last - 1)
-      src = FinSrc{at<float>(ws, P.dwslab_off[l]), DS.nsplit[l], DS.slab[l], P.ld_in[l], at<float>(ws, P.part2_off) + P.ld_in[last], LAST_GROUPS, P.ld_part};
-    else src = FinSrc{at<float>(ws, P.dwslab_off[l]), DS.nsplit[l], DS.slab[l], P.ld_in[l], at<float>(ws, P.cs_off[l]), P.nwg, P.ldcs};
+      src = FinSrc{c.at<float>(c.P.dwslab_off[l]), DS.nsplit[l], DS.slab[l], c.P.ld_in[l], c.at<float>(c.P.part2_off) + c.P.ld_in[last], LAST_GROUPS, c.P.ld_part};
+    else src = FinSrc{c.at<float>(c.P.dwslab_off[l]), DS.nsplit[l], DS.slab[l], c.P.ld_in[l], c.at<float>(c.P.cs_off[l]), c.P.nwg, c.P.ldcs};
     FinArgs& f = fa->f[fa->n];
-    f = fin_args(net, L, pk, l, src, params, grads, accumulate, fz);
+    f = fin_args(c, l, src, to);
     if (segmode && (l == 0 || l == ks)) {
-      f.hoist = 1; f.lat0 = l == 0 ? 0 : net->out_dim[l - 1]; f.hW = net->latent_size + net->geom_dim; f.ldh = P.ldh;
-      f.hs = at<float>(ws, P.hs_off) + (l == 0 ? 0 : P.hstride);
+      f.hoist = 1; f.lat0 = l == 0 ? 0 : c.net->out_dim[l - 1]; f.hW = c.net->latent_size + c.net->geom_dim; f.ldh = c.P.ldh;
+      f.hs = c.at<float>(c.P.hs_off) + (l == 0 ? 0 : c.P.hstride);
     }
     fa->row0[fa->n] = rows;
     rows += fin_blocks(f.out, f.in);
@@ -1296,69 +1282,88 @@ int fin_table(const DsdfNet* net, const Plan& P, void* ws, const DwSched& DS, co
 // fwd: the deferred forward of the same points -> one launch for both.
 // phase (DsdfLossCfg.dw_phase): 0 = everything; p >= 1: dW + finalize of bucket p - 1 only (p = 1: after the forward + backward launch
 // and its roles)
-int run_backward_fused(const DsdfNet* net, const Path& path, const Plan& P, void* ws, const float* packed, const float* params, int64_t n,
-                       int training, float* grads, int accumulate, int ncols_dz, bool* used_dzB, hipStream_t st, bool want_dw,
-                       const FusedBwdHead& head, const FuseAdam* fz = nullptr, const SegBwd* sb = nullptr,
-                       const FusedFwdArgs* fwd = nullptr, int phase = 0) {
-  const DwSched& DS = phase == 0 ? P.dw : P.dwph[phase - 1];
+int run_backward_fused(const Call& c, const GradSink& to, int ncols_dz, bool* used_dzB, bool want_dw, const FusedBwdHead& head,
+                       const SegBwd* sb, const FusedFwdArgs* fwd, int phase) {
+  const DwSched& DS = phase == 0 ? c.P.dw : c.P.dwph[phase - 1];
   const bool segmode = sb != nullptr;
-  FusedBwdArgs a = dx_chain_args(net, P, ws, packed, n, training, ncols_dz, want_dw, head, sb, used_dzB);
-  if (phase <= 1) TRY(launch_dx_chain(net, path, P, n, a, fwd, st));
-  const Roles R = plan_roles(net, P, ws, packed, DS, want_dw, sb, phase);
+  FusedBwdArgs a = dx_chain_args(c, ncols_dz, want_dw, head, sb, used_dzB);
+  if (phase <= 1) TRY(launch_dx_chain(c, a, fwd));
+  const Roles R = plan_roles(c, DS, want_dw, sb, phase);
   if (!segmode && phase <= 1 && want_dw) {
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(R.rr_bx, LAST_GROUPS), dim3(256), 0, st, R.rr);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(R.rr_bx, LAST_GROUPS), dim3(256), 0, c.st, R.rr);
     LAUNCH_OK("reduce_rows_kernel");
   }
-  if (segmode && sb->scatter != nullptr) { sb->scatter->nslice = R.lat_slices; sb->scatter->slice_stride = (long long)sb->R * net->latent_size; }
+  if (segmode && sb->scatter != nullptr) { sb->scatter->nslice = R.lat_slices; sb->scatter->slice_stride = (long long)sb->R * c.net->latent_size; }
   if (segmode && !R.rides && phase <= 1) {
-    hipLaunchKernelGGL(post_bwd_kernel, dim3((unsigned)(R.q.rr_n + R.q.dw_n + R.lat_n)), dim3(256), 0, st, R.q, R.lat_n);
+    hipLaunchKernelGGL(post_bwd_kernel, dim3((unsigned)(R.q.rr_n + R.q.dw_n + R.lat_n)), dim3(256), 0, c.st, R.q, R.lat_n);
     LAUNCH_OK("post_bwd_kernel");
   }
   if (!want_dw) return 0;
-  if (R.dw_items > 0) TRY(launch_dw(net, path, P, ws, n, DS, R, segmode, phase, st));
+  if (R.dw_items > 0) TRY(launch_dw(c, DS, R, segmode, phase));
   FinAll fa;
-  const int rows = fin_table(net, P, ws, DS, params, grads, accumulate, fz, segmode, phase, &fa);
+  const int rows = fin_table(c, DS, to, segmode, phase, &fa);
   if (rows == 0) return 0;
   if (segmode && sb->scatter != nullptr && phase <= 1) {   // the dense latent-gradient scatter rides on the finalize launch
-    hipLaunchKernelGGL(finalize_scatter_kernel, dim3(rows + sb->R), dim3(256), 0, st, fa, *sb->scatter, rows);
+    hipLaunchKernelGGL(finalize_scatter_kernel, dim3(rows + sb->R), dim3(256), 0, c.st, fa, *sb->scatter, rows);
     LAUNCH_OK("finalize_scatter_kernel");
     *sb->scatter_done = true;
   } else {
-    hipLaunchKernelGGL(finalize_all_kernel, dim3(rows), dim3(256), 0, st, fa);
+    hipLaunchKernelGGL(finalize_all_kernel, dim3(rows), dim3(256), 0, c.st, fa);
     LAUNCH_OK("finalize_all_kernel");
   }
   return 0;
 }
 
-FusedBwdHead make_head(const DsdfNet* net, const Plan& P, void* ws, const float* packed, const float* params, int mode,
-                       int training) {
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
-  const int last = net->n_layers - 1;
+FusedBwdHead make_head(const Call& c, int mode) {
+  const int last = c.net->n_layers - 1;
   FusedBwdHead h;
   memset(&h, 0, sizeof(h));
   h.mode = mode;
-  h.a_last = at<float>(ws, P.in_off[last]); h.ld_a = P.ld_in[last]; h.in_last = net->in_dim[last];
-  h.w_last = packed + pk.w_off[last]; h.b_last = params + L.bias_off[last]; h.use_tanh = net->use_tanh;
-  h.mask_scale = mask_scale_of(net, last - 1, training);
-  h.dp_out = at<float>(ws, P.dpl_off[last - 1]); h.ld_dp = P.ld_dp;
-  h.part = at<float>(ws, P.part_off); h.ld_part = P.ld_part;
-  h.part_db = at<float>(ws, P.partdb_off); h.part_loss = at<float>(ws, P.partloss_off);
-  h.n_act = net->out_dim[last - 1];      // (< in_last only when latent_in names the output layer: run_backward_fused points dz_out)
+  h.a_last = c.at<float>(c.P.in_off[last]); h.ld_a = c.P.ld_in[last]; h.in_last = c.net->in_dim[last];
+  h.w_last = c.packed + c.pk.w_off[last]; h.b_last = c.params + c.L.bias_off[last]; h.use_tanh = c.net->use_tanh;
+  h.mask_scale = mask_scale_of(c.net, last - 1, c.training);
+  h.dp_out = c.at<float>(c.P.dpl_off[last - 1]); h.ld_dp = c.P.ld_dp;
+  h.part = c.at<float>(c.P.part_off); h.ld_part = c.P.ld_part;
+  h.part_db = c.at<float>(c.P.partdb_off); h.part_loss = c.at<float>(c.P.partloss_off);
+  h.n_act = c.net->out_dim[last - 1];      // (< in_last only when latent_in names the output layer: run_backward_fused points dz_out)
   return h;
 }
 
-// (validate() admits fwd_bf16 / gemm_split only for nets the fused kernels cover: without them the switch is the one reason)
-int check_common(const DsdfNet* net, const Switches& sw, const void* packed, const void* params, const void* ws) {
+// The opening of every entry point that launches the decoder, in the order a caller can observe through the error it gets:
+//   switches -> the checks all of them share -> n == 0 is a no-op (training excepted: an empty batch is an error of its own) ->
+//   own(), the entry's argument checks (net is valid and c.path picked by then) -> layouts -> lay(c), the workspace plan for
+//   c.path (recording t_last_plan) -> the size check against its total.
+// Returns 0 with c filled, or the error; after a 0 the caller returns at once when n == 0.  training / keys / row_offset stay zero.
+template <class Own, class Lay>
+int open_call(Call& c, Entry entry, const DsdfNet* net, const float* packed, const float* params, void* ws, size_t ws_bytes,
+              void* stream, int64_t n, Own own, Lay lay) {
+  memset(&c, 0, sizeof(c));
+  c.sw = Switches::read();
   TRY(validate(net));
-  const bool fused = pick_path(net, 0, ENTRY_MODULE_FWD, sw).fused;
+  // (validate() admits fwd_bf16 / gemm_split only for nets the fused kernels cover: without them the switch is the one reason)
+  const bool fused = pick_path(net, 0, ENTRY_MODULE_FWD, c.sw).fused;
   if (net->fwd_bf16 && !fused) return fail(DSDF_E_INVALID, "fwd_bf16 exists only in the fused kernels (DSDF_NO_FUSED is set)");
   if (net->gemm_split && !fused) return fail(DSDF_E_INVALID, "gemm_split exists only in the fused kernels (DSDF_NO_FUSED is set)");
   if (!packed || !params || !ws) return fail(DSDF_E_INVALID, "NULL packed/params/workspace pointer");
   if (!aligned16(packed) || !aligned16(params) || (reinterpret_cast<uintptr_t>(ws) & 255))
     return fail(DSDF_E_INVALID, "packed/params must be 16-byte and workspace 256-byte aligned");
+  if (n == 0 && entry != ENTRY_TRAIN) return 0;
+  c.net = net; c.packed = packed; c.params = params; c.ws = ws; c.n = n; c.st = (hipStream_t)stream;
+  c.path = pick_path(net, n, entry, c.sw);
+  TRY(own());
+  param_layout(net, &c.L);
+  c.pk = packed_layout(net);
+  c.P = lay(c);
+  if (ws_bytes < c.P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, c.P.total);
   return 0;
+}
+// ... with the layout of a call without segments or buckets: the inference plan or the module path's, for the path's rows (or frows)
+template <class Own>
+int open_call(Call& c, Entry entry, const DsdfNet* net, const float* packed, const float* params, void* ws, size_t ws_bytes,
+              void* stream, int64_t n, Own own, int frows = 0) {
+  return open_call(c, entry, net, packed, params, ws, ws_bytes, stream, n, own, [=](const Call& c) {
+    return make_plan(c.net, c.n, 0, entry == ENTRY_INFER, false, 2, frows ? frows : c.path.frows, &t_last_plan);
+  });
 }
 
 }  // namespace
@@ -1441,32 +1446,29 @@ int dsdf_materialize_weights(const DsdfNet* net, const float* params, float* pac
 
 int dsdf_decode(const DsdfNet* net, const float* packed, const float* params, const float* input, int64_t ld_in,
                 int64_t n, float* sdf_out, void* ws, size_t ws_bytes, void* stream) {
-  const Switches sw = Switches::read();
-  TRY(check_common(net, sw, packed, params, ws));
-  if (n == 0) return 0;
-  if (!input || !sdf_out || n < 0 || ld_in < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in");
-  const Path path = pick_path(net, n, ENTRY_INFER, sw);
-  const Plan P = make_plan(net, n, 0, true, false, 2, path.frows, &t_last_plan);
-  if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
-  hipStream_t st = (hipStream_t)stream;
-  TRY(run_gather(net, P, ws, nullptr, nullptr, input, ld_in, n, st));
-  if (path.fused) return run_fused_forward(net, path, P, ws, packed, params, n, 0, nullptr, 0, false, sdf_out, nullptr, st);
-  TRY(run_hidden_forward(net, P, ws, packed, params, n, 0, nullptr, 0, st, false));
-  LastArgs a = last_args(net, P, ws, packed, params, n);
+  Call c;
+  const int rc = open_call(c, ENTRY_INFER, net, packed, params, ws, ws_bytes, stream, n, [&] {
+    return !input || !sdf_out || n < 0 || ld_in < net->in_dim[0] ? fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in") : 0;
+  });
+  if (rc != 0 || n == 0) return rc;
+  TRY(run_gather(c, nullptr, nullptr, input, ld_in));
+  if (c.path.fused) return run_fused_forward(c, false, sdf_out, nullptr);
+  TRY(run_hidden_forward(c, false));
+  LastArgs a = last_args(c);
   a.y_out = sdf_out;
   int blocks = (int)((n + 15) / 16);
   if (blocks > 2048) blocks = 2048;
-  return launch_last<LAST_FWD>(a, blocks, st);
+  return launch_last<LAST_FWD>(a, blocks, c.st);
 }
 
 // dsdf_decode_latent's own layout: the one-row "scene table" index and U [1][2][FMAXW] behind it.  The caller's buffer is still
-// sized like dsdf_decode's (at least 16384 bytes); none of that plan's regions is touched.
-static Plan decode_latent_plan(const DsdfNet* net, int64_t n, int frows, size_t* scene_off, size_t* need, WsTable* rec) {
+// sized like dsdf_decode's (at least 16384 bytes: the plan's total); none of that plan's regions is touched.
+static Plan decode_latent_plan(const DsdfNet* net, int64_t n, int frows, size_t* scene_off, WsTable* rec) {
   Plan P = make_plan(net, n, 0, true, false, 2, frows);
   WsCarver c(rec);
   *scene_off = c.take("dl_scene", -1, 8);                                             // seg_scene[0] = 0: the "table" is the single latent row
   P.hoistU_off = c.take("dl_hoistU", -1, (size_t)2 * FMAXW * 4); P.ldu = FMAXW;      // U [1][2][512] behind it
-  *need = c.finish(std::max(std::max<size_t>(P.total, 16384), c.o));
+  P.total = c.finish(std::max(std::max<size_t>(P.total, 16384), c.o));
   return P;
 }
 
@@ -1482,26 +1484,27 @@ int dsdf_decode_latent_supported(const DsdfNet* net) {
 
 int dsdf_decode_latent(const DsdfNet* net, const float* packed, const float* params, const float* latent, const float* xyz,
                        int64_t n, float* sdf_out, void* ws, size_t ws_bytes, void* stream) {
-  const Switches sw = Switches::read();
-  TRY(check_common(net, sw, packed, params, ws));
-  if (n == 0) return 0;
-  if (!latent || !xyz || !sdf_out || n < 0) return fail(DSDF_E_INVALID, "bad latent/xyz/sdf_out");
-  const Path path = pick_path(net, n, ENTRY_INFER, sw);
-  if (!decode_latent_ok(net, path))
-    return fail(DSDF_E_INVALID, "dsdf_decode_latent needs the fused forward (widths <= 512, geom_dim <= 4): use dsdf_decode");
-  size_t scene_off = 0, need = 0;
-  const Plan P = decode_latent_plan(net, n, path.frows, &scene_off, &need, &t_last_plan);
-  if (ws_bytes < need) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
+  Call c;
+  size_t scene_off = 0;
+  const int rc = open_call(
+      c, ENTRY_INFER, net, packed, params, ws, ws_bytes, stream, n,
+      [&] {
+        if (!latent || !xyz || !sdf_out || n < 0) return fail(DSDF_E_INVALID, "bad latent/xyz/sdf_out");
+        if (!decode_latent_ok(net, c.path))
+          return fail(DSDF_E_INVALID, "dsdf_decode_latent needs the fused forward (widths <= 512, geom_dim <= 4): use dsdf_decode");
+        return 0;
+      },
+      [&](const Call& c) { return decode_latent_plan(net, n, c.path.frows, &scene_off, &t_last_plan); });
+  if (rc != 0 || n == 0) return rc;
   // ONE segment covering every point: the segment-mode forward with the latent's products hoisted (fused.hpp FusedSeg)
-  HIP_OK(hipMemsetAsync(at<char>(ws, scene_off), 0, 8, st));
+  HIP_OK(hipMemsetAsync(c.at<char>(scene_off), 0, 8, c.st));
   DsdfBatch b;
   memset(&b, 0, sizeof(b));
-  b.seg_scene = at<int64_t>(ws, scene_off); b.n_segments = 1; b.xyz = xyz; b.n_points = n; b.seg_len = n;
+  b.seg_scene = c.at<int64_t>(scene_off); b.n_segments = 1; b.xyz = xyz; b.n_points = n; b.seg_len = n;
   FusedSeg seg;
-  TRY(run_hoist(net, P, ws, packed, latent, &b, &seg, st));
-  seg.wg_per_seg = (int)((n + P.frows - 1) / P.frows);  // every workgroup belongs to segment 0
-  return run_fused_forward(net, path, P, ws, packed, params, n, 0, nullptr, 0, false, sdf_out, nullptr, st, &seg);
+  TRY(run_hoist(c, latent, &b, &seg));
+  seg.wg_per_seg = (int)((n + c.P.frows - 1) / c.P.frows);  // every workgroup belongs to segment 0
+  return run_fused_forward(c, false, sdf_out, nullptr, &seg);
 }
 
 // ---- debug only: red zones and the region table of the workspace planners (include/dsdf.h) ----------------
@@ -1539,8 +1542,8 @@ int dsdf_debug_ws_plan(const DsdfNet* net, int64_t n_points, int64_t n_segments,
     case DSDF_WS_PLAN_TRAIN: make_plan(net, n_points, n_segments, false, segmode != 0, n_buckets, frows, &t_last_plan); return 0;
     case DSDF_WS_PLAN_DECODE: make_plan(net, n_points, 0, true, false, 2, frows, &t_last_plan); return 0;
     case DSDF_WS_PLAN_DECODE_LATENT: {
-      size_t scene_off = 0, need = 0;
-      decode_latent_plan(net, n_points, frows, &scene_off, &need, &t_last_plan);
+      size_t scene_off = 0;
+      decode_latent_plan(net, n_points, frows, &scene_off, &t_last_plan);
       return 0;
     }
     default: return fail(DSDF_E_INVALID, "plan kind %d", kind);
@@ -1568,76 +1571,72 @@ int dsdf_debug_packed_layout(const DsdfNet* net, DsdfPackedLayout* out) {
 int dsdf_module_forward(const DsdfNet* net, const float* packed, const float* params, const float* input,
                         int64_t ld_in, int64_t n, int32_t training, const uint32_t* dropout_key, float* sdf_out,
                         void* ws, size_t ws_bytes, void* stream) {
-  const Switches sw = Switches::read();
-  TRY(check_common(net, sw, packed, params, ws));
-  if (n == 0) return 0;
-  if (!input || !sdf_out || n < 0 || ld_in < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in");
-  if (training && net->dropout_p > 0.f && net->dropout_mask && !dropout_key) return fail(DSDF_E_INVALID, "dropout_key is NULL");
-  const Path path = pick_path(net, n, ENTRY_MODULE_FWD, sw);
-  const Plan P = make_plan(net, n, 0, false, false, 2, path.frows, &t_last_plan);
-  if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
-  hipStream_t st = (hipStream_t)stream;
-  TRY(run_gather(net, P, ws, nullptr, nullptr, input, ld_in, n, st, training, dropout_key, 0));
-  if (path.fused)
-    return run_fused_forward(net, path, P, ws, packed, params, n, training, dropout_key, 0, true, sdf_out, at<float>(ws, P.u_off), st);
-  TRY(run_hidden_forward(net, P, ws, packed, params, n, training, dropout_key, 0, st));
-  LastArgs a = last_args(net, P, ws, packed, params, n);
-  a.y_out = sdf_out; a.u_save = at<float>(ws, P.u_off);
-  return launch_last<LAST_FWD>(a, P.last_blocks, st);
+  Call c;
+  const int rc = open_call(c, ENTRY_MODULE_FWD, net, packed, params, ws, ws_bytes, stream, n, [&] {
+    if (!input || !sdf_out || n < 0 || ld_in < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad input/sdf_out/ld_in");
+    if (training && net->dropout_p > 0.f && net->dropout_mask && !dropout_key) return fail(DSDF_E_INVALID, "dropout_key is NULL");
+    return 0;
+  });
+  if (rc != 0 || n == 0) return rc;
+  c.training = training; c.keys = dropout_key;
+  TRY(run_gather(c, nullptr, nullptr, input, ld_in));
+  if (c.path.fused) return run_fused_forward(c, true, sdf_out, c.at<float>(c.P.u_off));
+  TRY(run_hidden_forward(c));
+  LastArgs a = last_args(c);
+  a.y_out = sdf_out; a.u_save = c.at<float>(c.P.u_off);
+  return launch_last<LAST_FWD>(a, c.P.last_blocks, c.st);
 }
 
 // want_dw == false (dsdf_module_input_grad): the same launches without the weight-gradient ones; grads is not touched
 static int module_backward_impl(const DsdfNet* net, const float* packed, const float* params, const float* d_sdf, int64_t n,
                                 int32_t training, const uint32_t* dropout_key, float* grads, int32_t accumulate, float* d_input,
                                 int64_t ld_din, void* ws, size_t ws_bytes, void* stream, bool want_dw) {
-  const Switches sw = Switches::read();
-  TRY(check_common(net, sw, packed, params, ws));
-  if (n == 0) return 0;
-  if (!d_sdf || (want_dw && !grads) || n < 0) return fail(DSDF_E_INVALID, "bad d_sdf/grads");
-  if (d_input && ld_din < net->in_dim[0]) return fail(DSDF_E_INVALID, "ld_din too small");
-  if (training && net->latent_dropout && d_input && !dropout_key)
-    return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key for d/d(input))");
-  const Path path = pick_path(net, n, ENTRY_MODULE_BWD, sw);
-  const Plan P = make_plan(net, n, 0, false, false, 2, path.frows, &t_last_plan);
-  if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
-  hipStream_t st = (hipStream_t)stream;
+  Call c;
+  const int rc = open_call(c, ENTRY_MODULE_BWD, net, packed, params, ws, ws_bytes, stream, n, [&] {
+    if (!d_sdf || (want_dw && !grads) || n < 0) return fail(DSDF_E_INVALID, "bad d_sdf/grads");
+    if (d_input && ld_din < net->in_dim[0]) return fail(DSDF_E_INVALID, "ld_din too small");
+    if (training && net->latent_dropout && d_input && !dropout_key)
+      return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key for d/d(input))");
+    return 0;
+  });
+  if (rc != 0 || n == 0) return rc;
+  c.training = training; c.keys = dropout_key;
+  const Plan& P = c.P;
+  const GradSink to{grads, accumulate, nullptr};
   bool used_dzB = false;
-  if (path.fused) {
-    FusedBwdHead h = make_head(net, P, ws, packed, params, HEAD_EXT, training);
-    h.d_sdf = d_sdf; h.u_in = at<float>(ws, P.u_off);
-    TRY(run_backward_fused(net, path, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, want_dw, h));
+  if (c.path.fused) {
+    FusedBwdHead h = make_head(c, HEAD_EXT);
+    h.d_sdf = d_sdf; h.u_in = c.at<float>(P.u_off);
+    TRY(run_backward_fused(c, to, d_input ? P.W0 : 0, &used_dzB, want_dw, h, nullptr, nullptr, 0));
   } else {
-    const Packed pk = packed_layout(net);
     const int last = net->n_layers - 1;
-    LastArgs a = last_args(net, P, ws, packed, params, n);
-    last_args_backward(a, net, P, ws, training);
-    a.d_sdf = d_sdf; a.u_in = at<float>(ws, P.u_off);
-    if (last_layer_skip(net) && d_input) { a.dz = at<float>(ws, P.dzB_off); a.ldz = P.ldz; a.dz_cols = P.W0; }
-    TRY(launch_last<LAST_BWD_EXT>(a, P.last_blocks, st));
+    LastArgs a = last_args(c, true);
+    a.d_sdf = d_sdf; a.u_in = c.at<float>(P.u_off);
+    if (last_layer_skip(net) && d_input) { a.dz = c.at<float>(P.dzB_off); a.ldz = P.ldz; a.dz_cols = P.W0; }
+    TRY(launch_last<LAST_BWD_EXT>(a, P.last_blocks, c.st));
     bool xyz_acc = false;
     if (d_input && net->xyz_in_all && last > 0) {   // the last layer's input is [a || xyz] too: its own d/d(xyz) opens the running sum
       const long long tot = (long long)n * net->geom_dim;
-      hipLaunchKernelGGL(last_xyz_grad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_sdf, at<float>(ws, P.u_off),
-                         packed + pk.w_off[last] + net->out_dim[last - 1], net->geom_dim, net->use_tanh, at<float>(ws, P.dxz_off[1]), 4, 0,
+      hipLaunchKernelGGL(last_xyz_grad_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.st, d_sdf, c.at<float>(P.u_off),
+                         packed + c.pk.w_off[last] + net->out_dim[last - 1], net->geom_dim, net->use_tanh, c.at<float>(P.dxz_off[1]), 4, 0,
                          (int)n, 0);
       LAUNCH_OK("last_xyz_grad_kernel");
       xyz_acc = true;
     }
-    TRY(run_backward(net, P, ws, packed, params, n, training, grads, accumulate, d_input ? P.W0 : 0, &used_dzB, st, want_dw, dropout_key, 0,
-                     (d_input && net->xyz_in_all) ? &xyz_acc : nullptr));
+    TRY(run_backward(c, to, d_input ? P.W0 : 0, &used_dzB, want_dw, (d_input && net->xyz_in_all) ? &xyz_acc : nullptr));
     if (last_layer_skip(net) && d_input) used_dzB = true;      // (last_layer_kernel wrote it)
     if (d_input) {
-      TRY(add_dz_to_input(P, ws, n, used_dzB, d_input, ld_din, st));
+      TRY(add_dz_to_input(c, used_dzB, d_input, ld_din));
       if (xyz_acc) {
         const long long tx = (long long)n * net->geom_dim;
-        hipLaunchKernelGGL(acc_cols_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.dxz_off[1]), 4, d_input,
+        hipLaunchKernelGGL(acc_cols_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, c.st, c.at<float>(P.dxz_off[1]), 4, d_input,
                            (int)ld_din, net->latent_size, (int)n, net->geom_dim, 1);
         LAUNCH_OK("acc_cols_kernel");
       }
     }
     return 0;
   }
-  if (d_input) TRY(add_dz_to_input(P, ws, n, used_dzB, d_input, ld_din, st));
+  if (d_input) TRY(add_dz_to_input(c, used_dzB, d_input, ld_din));
   return 0;
 }
 
@@ -1661,22 +1660,22 @@ int dsdf_module_input_grad(const DsdfNet* net, const float* packed, const float*
 // Layer-by-layer MFMA GEMM launches (gemm.hpp) -- this is the one-extra-pass tool of mesh.py:420, not the training hot path.
 int dsdf_module_jvp(const DsdfNet* net, const float* packed, const float* params, const float* tangent, int64_t ld_t,
                     int64_t n, int32_t training, const uint32_t* dropout_key, float* jvp_out, void* ws, size_t ws_bytes, void* stream) {
-  TRY(check_common(net, Switches::read(), packed, params, ws));
-  if (n == 0) return 0;
-  if (!tangent || !jvp_out || n < 0 || ld_t < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad tangent/jvp_out/ld_t");
-  const bool lat_drop = net->latent_dropout && training && net->latent_size > 0;
-  if (lat_drop && !dropout_key) return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key)");
-  const Plan P = make_plan(net, n, 0, false, false, 2, FROWS, &t_last_plan);
-  if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
-  hipStream_t st = (hipStream_t)stream;
-  DsdfParamLayout L;
-  param_layout(net, &L);
-  const Packed pk = packed_layout(net);
+  Call c;
+  const bool lat_drop = net && net->latent_dropout && training && net->latent_size > 0;
+  // (FROWS: the layout dsdf_module_forward left its activations in; the launches below use no path)
+  const int rc = open_call(c, ENTRY_MODULE_FWD, net, packed, params, ws, ws_bytes, stream, n, [&] {
+    if (!tangent || !jvp_out || n < 0 || ld_t < net->in_dim[0]) return fail(DSDF_E_INVALID, "bad tangent/jvp_out/ld_t");
+    if (lat_drop && !dropout_key) return fail(DSDF_E_INVALID, "dropout_key is NULL (latent_dropout needs the forward's key)");
+    return 0;
+  }, FROWS);
+  if (rc != 0 || n == 0) return rc;
+  const Plan& P = c.P;
+  hipStream_t st = c.st;
   const int last = net->n_layers - 1;
-  float* t0 = at<float>(ws, P.dzA_off);                      // the input tangent in a 16-byte-aligned, zero-padded layout
+  float* t0 = c.at<float>(P.dzA_off);                      // the input tangent in a 16-byte-aligned, zero-padded layout
   HIP_OK(hipMemsetAsync(t0, 0, (size_t)n * P.ldz * 4, st));
-  HIP_OK(hipMemsetAsync(at<float>(ws, P.dp_off[0]), 0, (size_t)n * P.ld_dp * 4, st));
-  HIP_OK(hipMemsetAsync(at<float>(ws, P.dp_off[1]), 0, (size_t)n * P.ld_dp * 4, st));
+  HIP_OK(hipMemsetAsync(c.at<float>(P.dp_off[0]), 0, (size_t)n * P.ld_dp * 4, st));
+  HIP_OK(hipMemsetAsync(c.at<float>(P.dp_off[1]), 0, (size_t)n * P.ld_dp * 4, st));
   {
     const long long tot = (long long)n * P.W0;
     hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, tangent, (int)ld_t, (const float*)nullptr, 0,
@@ -1685,7 +1684,7 @@ int dsdf_module_jvp(const DsdfNet* net, const float* packed, const float* params
   }
   float* t0_layer0 = t0;                                     // latent_dropout: layer 0 sees the tangent of the DROPPED latent,
   if (lat_drop) {                                            // the skip layer the raw one (deep_sdf_decoder.py:79-89)
-    t0_layer0 = at<float>(ws, P.dzB_off);
+    t0_layer0 = c.at<float>(P.dzB_off);
     HIP_OK(hipMemcpyAsync(t0_layer0, t0, (size_t)n * P.ldz * 4, hipMemcpyDeviceToDevice, st));
     const long long tot = (long long)n * net->latent_size;
     hipLaunchKernelGGL(latent_drop_bwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, t0_layer0, P.ldz, (int)n,
@@ -1704,40 +1703,40 @@ int dsdf_module_jvp(const DsdfNet* net, const float* packed, const float* params
   };
   int cur = 0;
   for (int l = 0; l < last; ++l) {
-    float* in_t = l == 0 ? t0_layer0 : at<float>(ws, P.dp_off[cur]);
+    float* in_t = l == 0 ? t0_layer0 : c.at<float>(P.dp_off[cur]);
     if (l > 0) { append(in_t, l); LAUNCH_OK("add2_kernel(concat tangent)"); }
     NtArgs a;
     memset(&a, 0, sizeof(a));
     a.A = in_t; a.lda = l == 0 ? P.ldz : P.ld_dp;
-    a.B = packed + pk.w_off[l]; a.ldb = pk.ldw[l];
-    a.C = at<float>(ws, P.dp_off[l == 0 ? 0 : cur ^ 1]); a.ldc = P.ld_dp;
+    a.B = packed + c.pk.w_off[l]; a.ldb = c.pk.ldw[l];
+    a.C = c.at<float>(P.dp_off[l == 0 ? 0 : cur ^ 1]); a.ldc = P.ld_dp;
     a.M = (int)n; a.N = net->out_dim[l]; a.K = net->in_dim[l];
     if (ln_applied(net, l)) {                                // Linear tangent, then LayerNorm + ReLU/dropout in one row pass
       TRY(launch_nt<EPI_PLAIN>(a, st));
       LnJvpArgs j;
       memset(&j, 0, sizeof(j));
-      j.t = a.C; j.ldt = a.ldc; j.xhat = at<float>(ws, P.lnx_off[l]); j.ldx = P.ld_in[l + 1]; j.rstd = at<float>(ws, P.lnr_off[l]);
-      j.gamma = params + L.ln_w_off[l]; j.act = at<float>(ws, P.in_off[l + 1]); j.ldact = P.ld_in[l + 1];
+      j.t = a.C; j.ldt = a.ldc; j.xhat = c.at<float>(P.lnx_off[l]); j.ldx = P.ld_in[l + 1]; j.rstd = c.at<float>(P.lnr_off[l]);
+      j.gamma = params + c.L.ln_w_off[l]; j.act = c.at<float>(P.in_off[l + 1]); j.ldact = P.ld_in[l + 1];
       j.mask_scale = mask_scale_of(net, l, training); j.n = (int)n; j.width = net->out_dim[l];
       hipLaunchKernelGGL(ln_jvp_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, j);
       LAUNCH_OK("ln_jvp_kernel");
     } else {
-      a.act = at<float>(ws, P.in_off[l + 1]); a.ldact = P.ld_in[l + 1];
+      a.act = c.at<float>(P.in_off[l + 1]); a.ldact = P.ld_in[l + 1];
       a.mask_cols = net->out_dim[l]; a.mask_scale = mask_scale_of(net, l, training);
       TRY(launch_nt<EPI_BWD>(a, st));
     }
     if (l > 0) cur ^= 1;
   }
-  if (last > 0) { append(at<float>(ws, P.dp_off[cur]), last); LAUNCH_OK("add2_kernel(concat tangent, last)"); }
+  if (last > 0) { append(c.at<float>(P.dp_off[cur]), last); LAUNCH_OK("add2_kernel(concat tangent, last)"); }
   NtArgs a;                                                   // du = t_last . w_last
   memset(&a, 0, sizeof(a));
-  a.A = at<float>(ws, P.dp_off[cur]); a.lda = P.ld_dp;
-  a.B = packed + pk.w_off[last]; a.ldb = pk.ldw[last];
-  a.C = at<float>(ws, P.y_off); a.ldc = 1;
+  a.A = c.at<float>(P.dp_off[cur]); a.lda = P.ld_dp;
+  a.B = packed + c.pk.w_off[last]; a.ldb = c.pk.ldw[last];
+  a.C = c.at<float>(P.y_off); a.ldc = 1;
   a.M = (int)n; a.N = 1; a.K = net->in_dim[last];
   TRY(launch_nt<EPI_PLAIN>(a, st));
-  hipLaunchKernelGGL(jvp_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, at<float>(ws, P.y_off),
-                     at<float>(ws, P.u_off), jvp_out, (int)n, net->use_tanh);
+  hipLaunchKernelGGL(jvp_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c.at<float>(P.y_off),
+                     c.at<float>(P.u_off), jvp_out, (int)n, net->use_tanh);
   LAUNCH_OK("jvp_tail_kernel");
   return 0;
 }
@@ -1745,48 +1744,53 @@ int dsdf_module_jvp(const DsdfNet* net, const float* packed, const float* params
 }  // extern "C"
 
 namespace {
-// returns 1 in *adam_fused when the decoder's Adam update (and the new weight-norm scales) was folded into the finalize pass
+// fz != nullptr: sets fz->used when the decoder's Adam update (and the new weight-norm scales) was folded into the finalize pass
 int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, float* latent_table, int64_t n_scenes,
                   const DsdfBatch* b, const DsdfLossCfg* cfg, float* grads, float* dlat, float* loss_out, float* sdf_out,
-                  int32_t accumulate, void* ws, size_t ws_bytes, void* stream, const FuseAdam* fz, int* adam_fused) {
-  if (adam_fused) *adam_fused = 0;
-  const Switches sw = Switches::read();
-  TRY(check_common(net, sw, packed, params, ws));
-  if (!b || !cfg || !latent_table || !grads || !dlat || !loss_out) return fail(DSDF_E_INVALID, "NULL argument");
-  const int64_t n = b->n_points, R = b->n_segments;
-  if (n <= 0 || R <= 0 || n_scenes <= 0) return fail(DSDF_E_INVALID, "empty batch (n_points %lld, n_segments %lld)", (long long)n, (long long)R);
-  if (!b->seg_scene || !b->seg_offset || !b->xyz || !b->sdf_gt) return fail(DSDF_E_INVALID, "NULL batch pointer");
-  if (b->n_norm <= 0) return fail(DSDF_E_INVALID, "n_norm must be positive");
-  if (net->latent_size <= 0) return fail(DSDF_E_INVALID, "training needs latent_size > 0");
-  // Segment mode: the batch is scenes x samples with every segment a whole number of 64-row workgroups, so a workgroup
-  // sees ONE latent vector: its products with the weights are hoisted out of the per-point work (fused.hpp FusedSeg),
-  // and the latent gradient / the x0 columns of the weight gradients come from per-workgroup column sums.
-  const Path path = pick_path(net, n, ENTRY_TRAIN, sw);
-  const bool fusedb = path.fused, merged = path.merged;
-  const int skip_l = skip_layer(net);
-  const bool segsum = fusedb && b->seg_len > 0 && b->seg_len % path.frows == 0 && b->seg_len * R == n && net->n_layers > 2 &&
-                      skip_l != net->n_layers - 2 &&   // the deepest hidden layer's dP column sums live in the head's partials
-                      !last_layer_skip(net) &&
-                      net->geom_dim <= FGEO && net->latent_size >= 1 && net->latent_size <= HOIST_MAXL;   // (config 5 too: bf16 rounding is element-wise
-                                                                                  // on the operands, so the latent products still hoist)
-  const int phase = cfg->dw_phase, nbk = cfg->dw_buckets;
-  if (nbk < 0 || nbk > DSDF_MAX_BUCKETS) return fail(DSDF_E_INVALID, "dw_buckets %d out of range [0, %d]", nbk, DSDF_MAX_BUCKETS);
-  if (phase < 0 || (nbk <= 1 ? phase != 0 : phase < 1 || phase > nbk))
-    return fail(DSDF_E_INVALID, "dw_phase %d out of range for dw_buckets %d (0 without buckets, 1..K with K >= 2)", phase, nbk);
-  const Plan P = make_plan(net, n, R, false, segsum, nbk, path.frows, &t_last_plan);
-  if (ws_bytes < P.total) return fail(DSDF_E_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, P.total);
-  hipStream_t st = (hipStream_t)stream;
-  const int Lc = net->latent_size;
+                  int32_t accumulate, void* ws, size_t ws_bytes, void* stream, FuseAdam* fz) {
+  Call c;
+  TRY(open_call(
+      c, ENTRY_TRAIN, net, packed, params, ws, ws_bytes, stream, b ? b->n_points : 0,
+      [&] {
+        if (!b || !cfg || !latent_table || !grads || !dlat || !loss_out) return fail(DSDF_E_INVALID, "NULL argument");
+        if (b->n_points <= 0 || b->n_segments <= 0 || n_scenes <= 0)
+          return fail(DSDF_E_INVALID, "empty batch (n_points %lld, n_segments %lld)", (long long)b->n_points, (long long)b->n_segments);
+        if (!b->seg_scene || !b->seg_offset || !b->xyz || !b->sdf_gt) return fail(DSDF_E_INVALID, "NULL batch pointer");
+        if (b->n_norm <= 0) return fail(DSDF_E_INVALID, "n_norm must be positive");
+        if (net->latent_size <= 0) return fail(DSDF_E_INVALID, "training needs latent_size > 0");
+        const int phase = cfg->dw_phase, nbk = cfg->dw_buckets;
+        if (nbk < 0 || nbk > DSDF_MAX_BUCKETS) return fail(DSDF_E_INVALID, "dw_buckets %d out of range [0, %d]", nbk, DSDF_MAX_BUCKETS);
+        if (phase < 0 || (nbk <= 1 ? phase != 0 : phase < 1 || phase > nbk))
+          return fail(DSDF_E_INVALID, "dw_phase %d out of range for dw_buckets %d (0 without buckets, 1..K with K >= 2)", phase, nbk);
+        return 0;
+      },
+      [&](const Call& c) {
+        // Segment mode: the batch is scenes x samples with every segment a whole number of 64-row workgroups, so a workgroup
+        // sees ONE latent vector: its products with the weights are hoisted out of the per-point work (fused.hpp FusedSeg),
+        // and the latent gradient / the x0 columns of the weight gradients come from per-workgroup column sums.
+        const bool seg = c.path.fused && b->seg_len > 0 && b->seg_len % c.path.frows == 0 && b->seg_len * b->n_segments == c.n &&
+                         net->n_layers > 2 &&
+                         skip_layer(net) != net->n_layers - 2 &&   // the deepest hidden layer's dP column sums live in the head's partials
+                         !last_layer_skip(net) &&
+                         net->geom_dim <= FGEO && net->latent_size >= 1 && net->latent_size <= HOIST_MAXL;   // (config 5 too: bf16 rounding
+                                                             // is element-wise on the operands, so the latent products still hoist)
+        return make_plan(net, c.n, b->n_segments, false, seg, cfg->dw_buckets, c.path.frows, &t_last_plan);
+      }));
+  c.training = cfg->training; c.keys = cfg->dropout_key; c.row_offset = (uint32_t)b->row_offset;
+  const Plan& P = c.P;
+  hipStream_t st = c.st;
+  const int64_t n = c.n, R = b->n_segments;
+  const bool fusedb = c.path.fused, merged = c.path.merged, segsum = P.segmode != 0;
+  const int phase = cfg->dw_phase, Lc = net->latent_size;
   if (phase != 0 && (!fusedb || cfg->frozen_decoder || accumulate || fz != nullptr))
     return fail(DSDF_E_INVALID, "dw_phase needs the fused kernels (dsdf_dw_phase_supported), a trainable decoder, accumulate = 0 and the two-call path");
   if (phase >= 2) {   // only the weight gradients of bucket phase - 1, from what the phase-1 call left in the workspace
     FusedSeg seg0;
     memset(&seg0, 0, sizeof(seg0));
-    const FusedBwdHead h0 = make_head(net, P, ws, packed, params, HEAD_TRAIN, cfg->training);
+    const FusedBwdHead h0 = make_head(c, HEAD_TRAIN);
     const SegBwd sb0{&seg0, b->seg_scene, latent_table, (int)R, nullptr, nullptr, nullptr};
     bool used = false;
-    return run_backward_fused(net, path, P, ws, packed, params, n, cfg->training, grads, 0, segsum ? 0 : Lc, &used, st, true, h0, nullptr,
-                              segsum ? &sb0 : nullptr, nullptr, phase);
+    return run_backward_fused(c, GradSink{grads, 0, nullptr}, segsum ? 0 : Lc, &used, true, h0, segsum ? &sb0 : nullptr, nullptr, phase);
   }
 
   if (!segsum && (cfg->code_bound > 0.f || !accumulate)) {   // max-norm renorm of the looked-up rows + zero of the dense latent gradient
@@ -1804,23 +1808,18 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
   FusedFwdArgs fwd_args;                                   // merged: forward + backward go out as ONE launch below
   if (segsum) {
     const HoistRenorm hr{cfg->code_bound > 0.f ? cfg->code_bound : 0.f, dlat, accumulate ? 0 : (long long)n_scenes * Lc};
-    TRY(run_hoist(net, P, ws, packed, latent_table, b, &seg, st, &hr));
-    TRY(run_fused_forward(net, path, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, true,
-                          nullptr, nullptr, st, &seg, merged ? &fwd_args : nullptr));
+    TRY(run_hoist(c, latent_table, b, &seg, &hr));
+    TRY(run_fused_forward(c, true, nullptr, nullptr, &seg, merged ? &fwd_args : nullptr));
   } else {
-    TRY(run_gather(net, P, ws, latent_table, b, nullptr, 0, n, st, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset));
-    if (fusedb)
-      TRY(run_fused_forward(net, path, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, true,
-                            nullptr, nullptr, st, nullptr, merged ? &fwd_args : nullptr));
-    else
-      TRY(run_hidden_forward(net, P, ws, packed, params, n, cfg->training, cfg->dropout_key, (uint32_t)b->row_offset, st));
+    TRY(run_gather(c, latent_table, b, nullptr, 0));
+    if (fusedb) TRY(run_fused_forward(c, true, nullptr, nullptr, nullptr, merged ? &fwd_args : nullptr));
+    else TRY(run_hidden_forward(c));
   }
 
   if (!fusedb) {
-    LastArgs a = last_args(net, P, ws, packed, params, n);
-    last_args_backward(a, net, P, ws, cfg->training);
+    LastArgs a = last_args(c, true);
     a.y_out = sdf_out; a.gt = b->sdf_gt; a.delta = cfg->clamp_dist; a.inv_n = 1.0f / (float)b->n_norm;
-    if (last_layer_skip(net)) { a.dz = at<float>(ws, P.dzB_off); a.ldz = P.ldz; a.dz_cols = Lc; }
+    if (last_layer_skip(net)) { a.dz = c.at<float>(P.dzB_off); a.ldz = P.ldz; a.dz_cols = Lc; }
     TRY(launch_last<LAST_TRAIN>(a, P.last_blocks, st));
   }
 
@@ -1828,33 +1827,32 @@ int train_fb_impl(const DsdfNet* net, const float* packed, const float* params, 
   const bool want_dw = cfg->frozen_decoder == 0;
   ScatterArgs sc;   // dense latent gradient + regulariser + loss (block 0); launched below unless it rode on the finalize launch
   memset(&sc, 0, sizeof(sc));
-  sc.segpart = at<float>(ws, P.segpart_off); sc.segnorm = at<float>(ws, P.segnorm_off);
+  sc.segpart = c.at<float>(P.segpart_off); sc.segnorm = c.at<float>(P.segnorm_off);
   sc.seg_scene = b->seg_scene; sc.seg_offset = b->seg_offset;
   sc.R = (int)R; sc.L = Lc; sc.table = latent_table; sc.dlat = dlat;
-  sc.zr = segsum ? at<float>(ws, P.zr_off) : nullptr;
+  sc.zr = segsum ? c.at<float>(P.zr_off) : nullptr;
   sc.creg = cfg->reg_coef / (float)b->n_norm;
-  sc.part_loss = at<float>(ws, P.partloss_off); sc.n_part = fusedb ? P.nwg : P.last_blocks;
+  sc.part_loss = c.at<float>(P.partloss_off); sc.n_part = fusedb ? P.nwg : P.last_blocks;
   sc.loss_scale = 1.0f / (float)b->n_norm; sc.loss_out = loss_out; sc.accumulate = accumulate;
   bool scatter_done = false;
   if (fusedb) {
-    FusedBwdHead h = make_head(net, P, ws, packed, params, HEAD_TRAIN, cfg->training);
+    FusedBwdHead h = make_head(c, HEAD_TRAIN);
     h.gt = b->sdf_gt; h.delta = cfg->clamp_dist; h.inv_n = 1.0f / (float)b->n_norm; h.y_out = sdf_out;
     const FuseAdam* use = (fz != nullptr && want_dw && !accumulate) ? fz : nullptr;
     const SegBwd sb{&seg, b->seg_scene, latent_table, (int)R, &sc, &scatter_done, sc.zr};
-    TRY(run_backward_fused(net, path, P, ws, packed, params, n, cfg->training, grads, accumulate, segsum ? 0 : Lc, &used_dzB, st, want_dw, h,
-                           use, segsum ? &sb : nullptr, merged ? &fwd_args : nullptr, phase));
-    if (use != nullptr && adam_fused) *adam_fused = 1;
+    TRY(run_backward_fused(c, GradSink{grads, accumulate, use}, segsum ? 0 : Lc, &used_dzB, want_dw, h, segsum ? &sb : nullptr,
+                           merged ? &fwd_args : nullptr, phase));
+    if (use != nullptr) fz->used = true;
   } else {
-    TRY(run_backward(net, P, ws, packed, params, n, cfg->training, grads, accumulate, Lc, &used_dzB, st, want_dw, cfg->dropout_key,
-                     (uint32_t)b->row_offset));
+    TRY(run_backward(c, GradSink{grads, accumulate, nullptr}, Lc, &used_dzB, want_dw));
     if (last_layer_skip(net)) used_dzB = true;                 // (last_layer_kernel wrote it)
   }
 
   SegArgs s;
   memset(&s, 0, sizeof(s));
-  s.dzA = at<float>(ws, P.dzA_off); s.dzB = used_dzB ? at<float>(ws, P.dzB_off) : nullptr; s.ldz = P.ldz;
+  s.dzA = c.at<float>(P.dzA_off); s.dzB = used_dzB ? c.at<float>(P.dzB_off) : nullptr; s.ldz = P.ldz;
   s.seg_scene = b->seg_scene; s.seg_offset = b->seg_offset; s.R = (int)R; s.L = Lc; s.table = latent_table;
-  s.segpart = at<float>(ws, P.segpart_off); s.segnorm = at<float>(ws, P.segnorm_off);
+  s.segpart = c.at<float>(P.segpart_off); s.segnorm = c.at<float>(P.segnorm_off);
   if (!segsum) {   // (segment mode: per-segment latent gradients came out of post_bwd_kernel)
     // few long segments: cut their rows into slices until the launch has blocks for the chip (the scatter adds the slices)
     int nsl = 1;
@@ -1880,7 +1878,7 @@ int dsdf_train_forward_backward(const DsdfNet* net, const float* packed, const f
                                 float* loss_out, float* sdf_out, int32_t accumulate, void* ws, size_t ws_bytes,
                                 void* stream) {
   return train_fb_impl(net, packed, params, latent_table, n_scenes, b, cfg, grads, dlat, loss_out, sdf_out, accumulate, ws,
-                       ws_bytes, stream, nullptr, nullptr);
+                       ws_bytes, stream, nullptr);
 }
 
 int dsdf_grad_norm(const float* grads, int64_t n, float max_norm, float* norm_out, float* coef_out, void* ws,
@@ -1958,13 +1956,12 @@ int dsdf_train_step(const DsdfNet* net, float* packed, float* params, float* gra
                     void* ws, size_t ws_bytes, void* stream) {
   if (!adam || !exp_avg || !exp_avg_sq || !lat_exp_avg || !lat_exp_avg_sq) return fail(DSDF_E_INVALID, "NULL argument");
   if (adam->step < 1) return fail(DSDF_E_INVALID, "Adam step must be >= 1");
-  FuseAdam fz{adam, params, exp_avg, exp_avg_sq, packed};
-  int fused = 0;
+  FuseAdam fz{adam, params, exp_avg, exp_avg_sq, packed, false};
   const bool can_fuse = adam->grad_scale == nullptr && cfg && !cfg->frozen_decoder;
   TRY(train_fb_impl(net, packed, params, latent_table, n_scenes, b, cfg, grads, dlat, loss_out, sdf_out, 0, ws, ws_bytes, stream,
-                    can_fuse ? &fz : nullptr, &fused));
+                    can_fuse ? &fz : nullptr));
   const int64_t nlat = n_scenes * net->latent_size;
-  if (!fused)
+  if (!fz.used)
     return dsdf_adam_step(net, params, grads, exp_avg, exp_avg_sq, latent_table, dlat, lat_exp_avg, lat_exp_avg_sq, nlat, adam,
                           packed, stream);
   hipStream_t st = (hipStream_t)stream;
@@ -2088,7 +2085,7 @@ int dsdf_gemm_tn(const float* A, int64_t lda, const float* B, int64_t ldb, float
   f.slabs = t.C; f.nsplit = nsplit; f.slab = slab; f.ldc = (int)ldc; f.colsum = nullptr; f.npart = 0; f.ldcs = 0;
   WsCarver c(&t_last_plan, 1);
   c.take("tn_slabs", -1, (size_t)nsplit * slab * 4);
-  f.dv = C; f.db = at<float>(ws, c.take("tn_db", -1, (size_t)M * 4));   // scratch row of M floats behind the slabs
+  f.dv = C; f.db = (float*)((char*)ws + c.take("tn_db", -1, (size_t)M * 4));   // scratch row of M floats behind the slabs
   if (ws_bytes < c.finish(c.o)) return fail(DSDF_E_WORKSPACE, "gemm_tn workspace too small");
   f.out = (int)M; f.in = (int)N;
   hipLaunchKernelGGL(finalize_layer_kernel, dim3((unsigned)M), dim3(256), 0, st, f);
@@ -2131,16 +2128,20 @@ int mc_plan(int32_t nx, int32_t ny, int32_t nz, McPlan* P, WsTable* rec = nullpt
   return 0;
 }
 
+void mc_bind(const McPlan& P, void* ws, McWs* w) {
+  char* b = (char*)ws;
+  w->mask = (uint8_t*)(b + P.mask); w->cas = (uint8_t*)(b + P.cas); w->vbase = (int32_t*)(b + P.vbase);
+  w->bv = (int32_t*)(b + P.bv); w->bf = (int32_t*)(b + P.bf); w->ov = (int64_t*)(b + P.ov); w->of = (int64_t*)(b + P.of);
+  w->nblocks = P.nblocks;
+}
+
 int mc_setup(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, void* ws, size_t ws_bytes, McGrid* g,
              McWs* w, McPlan* P) {
   TRY(mc_plan(nx, ny, nz, P, &t_last_plan));
   if (!sdf || !ws) return fail(DSDF_E_INVALID, "marching cubes: NULL sdf or workspace");
   if (ws_bytes < P->total) return fail(DSDF_E_WORKSPACE, "marching cubes: workspace %zu < %zu bytes", ws_bytes, P->total);
   g->sdf = sdf; g->nx = nx; g->ny = ny; g->nz = nz; g->level = level; g->npts = P->npts;
-  char* b = (char*)ws;
-  w->mask = (uint8_t*)(b + P->mask); w->cas = (uint8_t*)(b + P->cas); w->vbase = (int32_t*)(b + P->vbase);
-  w->bv = (int32_t*)(b + P->bv); w->bf = (int32_t*)(b + P->bf); w->ov = (int64_t*)(b + P->ov); w->of = (int64_t*)(b + P->of);
-  w->nblocks = P->nblocks;
+  mc_bind(*P, ws, w);
   return 0;
 }
 }  // namespace
@@ -2200,10 +2201,7 @@ int dsdf_mc_edges(int32_t nx, int32_t ny, int32_t nz, int64_t n_verts, int64_t* 
   if (n_verts > 0 && (!edge_point || !edge_axis)) return fail(DSDF_E_INVALID, "marching cubes edges: NULL edge_point or edge_axis");
   if (n_verts == 0) return 0;
   McWs w;
-  char* b = (char*)ws;
-  w.mask = (uint8_t*)(b + P.mask); w.cas = (uint8_t*)(b + P.cas); w.vbase = (int32_t*)(b + P.vbase);
-  w.bv = (int32_t*)(b + P.bv); w.bf = (int32_t*)(b + P.bf); w.ov = (int64_t*)(b + P.ov); w.of = (int64_t*)(b + P.of);
-  w.nblocks = P.nblocks;
+  mc_bind(P, ws, &w);
   hipLaunchKernelGGL(mc_edge_kernel, dim3((unsigned)P.nblocks), dim3(MC_BLOCK), 0, (hipStream_t)stream, P.npts, w, n_verts, edge_point,
                      edge_axis);
   LAUNCH_OK("mc_edge_kernel");

@@ -627,3 +627,203 @@ def test_latent_size_zero_never_reaches_segment_mode(lib):
     assert rc == -1 and b"latent_size > 0" in lib.dsdf_last_error()
     rc = lib.dsdf_decode_latent(C.byref(net), dummy, dummy, dummy, dummy, 256, dummy, dummy, 1 << 30, None)
     assert rc == -1 and b"dsdf_decode_latent needs" in lib.dsdf_last_error()
+
+
+# ---- the opening of the decoder entry points: which error an invalid call gets --------------------------------------------------
+# One argument list per ABI name, valid but for what a row overrides.  Pointers are never dereferenced: every row fails on the host
+# (or is the n == 0 no-op).
+_OPEN_N, _OPEN_R = 128, 2
+_OPEN_ARGS = {
+    "dsdf_decode": "net packed params input ld_in n sdf_out ws ws_bytes stream",
+    "dsdf_decode_latent": "net packed params latent xyz n sdf_out ws ws_bytes stream",
+    "dsdf_module_forward": "net packed params input ld_in n training dropout_key sdf_out ws ws_bytes stream",
+    "dsdf_module_backward": "net packed params d_sdf n training dropout_key grads accumulate d_input ld_din ws ws_bytes stream",
+    "dsdf_module_input_grad": "net packed params d_sdf n d_input ld_din ws ws_bytes stream",
+    "dsdf_module_jvp": "net packed params tangent ld_t n training dropout_key jvp_out ws ws_bytes stream",
+    "dsdf_train_forward_backward": "net packed params latent_table n_scenes b cfg grads dlat loss_out sdf_out accumulate ws ws_bytes "
+                                   "stream",
+    "dsdf_train_step": "net packed params grads exp_avg exp_avg_sq latent_table n_scenes dlat lat_exp_avg lat_exp_avg_sq b cfg adam "
+                       "loss_out sdf_out ws ws_bytes stream",
+}
+_OPEN_INTS = {"ld_in": 16, "ld_din": 16, "ld_t": 16, "n": _OPEN_N, "training": 0, "accumulate": 0, "n_scenes": 4, "ws_bytes": 1 << 30}
+_WS = "workspace {got} < {need} bytes"      # a -2 row's message; the test says what `need` is compared with
+_NULL3 = "NULL packed/params/workspace pointer"
+_ALIGN = "packed/params must be 16-byte and workspace 256-byte aligned"
+_PHASE = "dw_phase needs the fused kernels (dsdf_dw_phase_supported), a trainable decoder, accumulate = 0 and the two-call path"
+_LATENT = "dsdf_decode_latent needs the fused forward (widths <= 512, geom_dim <= 4): use dsdf_decode"
+_DECODERS = ("dsdf_decode", "dsdf_decode_latent", "dsdf_module_forward", "dsdf_module_backward", "dsdf_module_input_grad",
+             "dsdf_module_jvp", "dsdf_train_forward_backward")
+_OWN = {"dsdf_decode": "bad input/sdf_out/ld_in", "dsdf_decode_latent": "bad latent/xyz/sdf_out",
+        "dsdf_module_forward": "bad input/sdf_out/ld_in", "dsdf_module_backward": "bad d_sdf/grads",
+        "dsdf_module_input_grad": "input gradient: -1 rows", "dsdf_module_jvp": "bad tangent/jvp_out/ld_t",
+        "dsdf_train_forward_backward": "empty batch (n_points -1, n_segments 2)"}
+# the data pointer whose NULL is the entry's own fault, and its message
+_OWN_NULL = {"dsdf_decode": ("input", "bad input/sdf_out/ld_in"), "dsdf_decode_latent": ("xyz", "bad latent/xyz/sdf_out"),
+             "dsdf_module_forward": ("sdf_out", "bad input/sdf_out/ld_in"), "dsdf_module_backward": ("d_sdf", "bad d_sdf/grads"),
+             "dsdf_module_input_grad": ("d_sdf", "input gradient: NULL d_sdf or d_input"),
+             "dsdf_module_jvp": ("jvp_out", "bad tangent/jvp_out/ld_t"), "dsdf_train_forward_backward": ("dlat", "NULL argument")}
+_SMALL_LD = {"dsdf_decode": ("ld_in", "bad input/sdf_out/ld_in"), "dsdf_module_forward": ("ld_in", "bad input/sdf_out/ld_in"),
+             "dsdf_module_backward": ("ld_din", "ld_din too small"), "dsdf_module_input_grad": ("ld_din", "ld_din too small"),
+             "dsdf_module_jvp": ("ld_t", "bad tangent/jvp_out/ld_t")}
+# (kind, segment mode, buckets, rows per workgroup) of the plan each entry lays out for the default call: dsdf_debug_ws_plan's arguments
+_OPEN_PLAN = {"dsdf_decode": (1, 0, 2, 32), "dsdf_decode_latent": (2, 0, 2, 32), "dsdf_module_forward": (0, 0, 2, 64),
+              "dsdf_module_backward": (0, 0, 2, 64), "dsdf_module_input_grad": (0, 0, 2, 64), "dsdf_module_jvp": (0, 0, 2, 64),
+              "dsdf_train_forward_backward": (0, 0, 0, 32), "dsdf_train_step": (0, 0, 0, 32)}
+
+
+def _open_rows():
+    """(id, ABI name, net keywords, environment, overrides, rc, message).  Overrides: argument name -> value; "b.<field>" /
+    "cfg.<field>" / "adam.<field>" set a field of the training structs."""
+    rows = []
+
+    def row(name, what, over, rc, msg, net=None, env=None):
+        rows.append((f"{name[5:]}-{what}", name, net or {}, env or {}, over, rc, msg))
+
+    for e in _DECODERS:
+        train = e == "dsdf_train_forward_backward"
+        nkey = "b.n_points" if train else "n"
+        row(e, "null-net", {"net": None}, -1, "net is NULL")
+        for p in ("packed", "params", "ws"):
+            row(e, f"null-{p}", {p: None}, -1, _NULL3)
+        row(e, "misaligned-ws", {"ws": 256 + 64}, -1, _ALIGN)
+        row(e, "misaligned-params", {"params": 256 + 8}, -1, _ALIGN)
+        row(e, "negative-n", {nkey: -1}, -1, _OWN[e])
+        if e in _SMALL_LD:
+            row(e, "small-ld", {_SMALL_LD[e][0]: 10}, -1, _SMALL_LD[e][1])          # in_dim[0] = 11
+        row(e, "small-ws", {"ws_bytes": 0}, -2, _WS)
+        row(e, "ws-one-byte-short", {"ws_bytes": -1}, -2, _WS)                       # -1: the plan's size less one
+        own_ptr, own_msg = _OWN_NULL[e]
+        row(e, "null-data", {own_ptr: None}, -1, own_msg)
+        # n == 0: nothing to do, whatever the data pointers -- but only behind the shared checks; an empty training batch is an error
+        nulls = {k: None for k in _OPEN_ARGS[e].split() if k in ("input", "latent", "xyz", "sdf_out", "d_sdf", "grads", "d_input",
+                                                                    "tangent", "jvp_out", "dropout_key")}
+        if train:
+            row(e, "empty", {nkey: 0}, -1, "empty batch (n_points 0, n_segments 2)")
+        else:
+            row(e, "n0-null-data", dict(nulls, n=0), 0, None)
+            row(e, "n0-small-ws", dict(nulls, n=0, ws_bytes=0), 0, None)
+            row(e, "n0-null-packed", dict(nulls, n=0, packed=None), -1, _NULL3)
+        # two faults at once: the shared check before the entry's own, the entry's own before the size
+        shared_first = "input gradient: -1 rows" if e == "dsdf_module_input_grad" else _NULL3   # (its wrapper looks at n first)
+        row(e, "shared-vs-own", {"packed": None, nkey: -1}, -1, shared_first)
+        row(e, "net-vs-own", {"net": None, own_ptr: None}, -1, own_msg if e == "dsdf_module_input_grad" else "net is NULL")
+        row(e, "own-vs-size", {own_ptr: None, "ws_bytes": 0}, -1, own_msg)
+    # dropout keys: the module entries want them when they will hash
+    row("dsdf_module_forward", "null-key", {"training": 1, "dropout_key": None}, -1, "dropout_key is NULL",
+        net=dict(dropout=[0, 1], dropout_prob=0.2))
+    row("dsdf_module_forward", "null-key-vs-size", {"training": 1, "dropout_key": None, "ws_bytes": 0}, -1, "dropout_key is NULL",
+        net=dict(dropout=[0, 1], dropout_prob=0.2))
+    row("dsdf_module_backward", "null-key", {"training": 1, "dropout_key": None}, -1,
+        "dropout_key is NULL (latent_dropout needs the forward's key for d/d(input))", net=dict(latent_dropout=True))
+    row("dsdf_module_jvp", "null-key", {"training": 1, "dropout_key": None}, -1,
+        "dropout_key is NULL (latent_dropout needs the forward's key)", net=dict(latent_dropout=True))
+    row("dsdf_module_backward", "null-grads-vs-ld", {"grads": None, "ld_din": 10}, -1, "bad d_sdf/grads")
+    # training
+    t = "dsdf_train_forward_backward"
+    row(t, "null-batch", {"b": None}, -1, "NULL argument")
+    row(t, "null-cfg", {"cfg": None}, -1, "NULL argument")
+    row(t, "null-batch-vs-packed", {"b": None, "packed": None}, -1, _NULL3)
+    row(t, "no-segments", {"b.n_segments": 0}, -1, "empty batch (n_points 128, n_segments 0)")
+    row(t, "no-scenes", {"n_scenes": 0}, -1, "empty batch (n_points 128, n_segments 2)")
+    row(t, "null-batch-pointer", {"b.sdf_gt": None}, -1, "NULL batch pointer")
+    row(t, "n-norm", {"b.n_norm": 0}, -1, "n_norm must be positive")
+    row(t, "empty-vs-n-norm", {"b.n_points": 0, "b.n_norm": 0}, -1, "empty batch (n_points 0, n_segments 2)")
+    row(t, "latent-size-0", {}, -1, "training needs latent_size > 0", net=dict(latent_size=0))
+    row(t, "n-norm-vs-latent-size-0", {"b.n_norm": -3}, -1, "n_norm must be positive", net=dict(latent_size=0))
+    for k in (-1, 9):
+        row(t, f"buckets{k}", {"cfg.dw_buckets": k}, -1, f"dw_buckets {k} out of range [0, 8]")
+    for k, p in ((0, 1), (1, 1), (2, 0), (2, 3), (2, -1), (8, 9)):
+        row(t, f"buckets{k}-phase{p}", {"cfg.dw_buckets": k, "cfg.dw_phase": p}, -1,
+            f"dw_phase {p} out of range for dw_buckets {k} (0 without buckets, 1..K with K >= 2)")
+    row(t, "buckets-vs-phase", {"cfg.dw_buckets": 9, "cfg.dw_phase": -1}, -1, "dw_buckets 9 out of range [0, 8]")
+    row(t, "phase-range-vs-size", {"cfg.dw_buckets": 2, "cfg.dw_phase": 3, "ws_bytes": 0}, -1,
+        "dw_phase 3 out of range for dw_buckets 2 (0 without buckets, 1..K with K >= 2)")
+    phased = {"cfg.dw_buckets": 2, "cfg.dw_phase": 1}
+    row(t, "phase-accumulate", dict(phased, accumulate=1), -1, _PHASE)
+    row(t, "phase2-accumulate", {"cfg.dw_buckets": 2, "cfg.dw_phase": 2, "accumulate": 1}, -1, _PHASE)
+    row(t, "phase-frozen", dict(phased, **{"cfg.frozen_decoder": 1}), -1, _PHASE)
+    row(t, "phase-accumulate-small-ws", dict(phased, accumulate=1, ws_bytes=0), -2, _WS)      # the size check comes first
+    row(t, "phase-layered", phased, -1, _PHASE, env={"DSDF_NO_FUSED": "1"})
+    row(t, "phase-layered-net", phased, -1, _PHASE, net=dict(xyz_in_all=True))
+    s = "dsdf_train_step"
+    row(s, "phase", phased, -1, _PHASE)
+    row(s, "phase-small-ws", dict(phased, ws_bytes=0), -2, _WS)
+    row(s, "null-adam", {"adam": None}, -1, "NULL argument")
+    row(s, "null-adam-vs-net", {"adam": None, "net": None}, -1, "NULL argument")             # its wrapper's checks come first
+    row(s, "adam-step-0", {"adam.step": 0}, -1, "Adam step must be >= 1")
+    row(s, "null-net", {"net": None}, -1, "net is NULL")
+    row(s, "null-batch", {"b": None}, -1, "NULL argument")
+    row(s, "small-ws", {"ws_bytes": 0}, -2, _WS)
+    # the single-code decode takes no layer-by-layer net; nets that exist in the fused kernels only, with those switched off
+    row("dsdf_decode_latent", "layernorm", {}, -1, _LATENT, net=dict(norm_layers=[0, 1], weight_norm=False))
+    row("dsdf_decode_latent", "layernorm-vs-size", {"ws_bytes": 0}, -1, _LATENT, net=dict(norm_layers=[0, 1], weight_norm=False))
+    row("dsdf_decode_latent", "no-fused", {}, -1, _LATENT, env={"DSDF_NO_FUSED": "1"})
+    for e in _DECODERS:
+        for kw, flag in ((dict(gemm_split=True), "gemm_split"), (dict(forward_bf16=True), "fwd_bf16")):
+            msg = f"{flag} exists only in the fused kernels (DSDF_NO_FUSED is set)"
+            row(e, f"no-fused-{flag}", {}, -1, msg, net=kw, env={"DSDF_NO_FUSED": "1"})
+            if e != "dsdf_module_input_grad":
+                row(e, f"no-fused-{flag}-vs-null", {"packed": None}, -1, msg, net=kw, env={"DSDF_NO_FUSED": "1"})
+    return rows
+
+
+def _open_call(lib, name, net_kw, over):
+    """Call `name` with the default arguments but `over`; returns (rc, message, the net)."""
+    from deepsdf_amd import _lib
+    from deepsdf_amd.net import NetSpec
+    kw = dict(latent_size=8)
+    kw.update(net_kw)
+    net = NetSpec(kw.pop("latent_size"), [64, 64], 3, **kw).c_struct()
+    dummy = 256
+    batch = _lib.DsdfBatch(dummy, dummy, _OPEN_R, dummy, dummy, _OPEN_N, _OPEN_N, 0, 0)
+    cfg = _lib.DsdfLossCfg()
+    cfg.clamp_dist, cfg.training = 0.1, 1
+    adam = _lib.DsdfAdamCfg(1, 5e-4, 1e-3, 0.9, 0.999, 1e-8, None)
+    structs = {"net": net, "b": batch, "cfg": cfg, "adam": adam}
+    for k, v in over.items():
+        if "." in k:
+            s, f = k.split(".")
+            setattr(structs[s], f, v)
+    args = []
+    for a in _OPEN_ARGS[name].split():
+        if a in over:
+            v = over[a]
+        elif a in structs:
+            v = structs[a]
+        elif a == "stream":
+            v = None
+        elif a == "dropout_key":
+            v = (C.c_uint32 * 16)()
+        else:
+            v = _OPEN_INTS.get(a, dummy)
+        args.append(C.byref(v) if isinstance(v, C.Structure) else v)
+    rc = getattr(lib, name)(*args)
+    return rc, (lib.dsdf_last_error().decode() if rc != 0 else None), net
+
+
+@pytest.mark.parametrize("name,net_kw,env,over,rc,msg", [pytest.param(*r[1:], id=r[0]) for r in _open_rows()])
+def test_invalid_calls_of_the_decoder_entries_get_the_same_answer(lib, monkeypatch, name, net_kw, env, over, rc, msg):
+    """Return code AND message of the entry points that launch the decoder, for calls that never reach a launch: which check speaks
+    first when two arguments are wrong is part of what a caller sees.  The literals were recorded from the library before the
+    entry points got one shared opening.  Byte counts are not literals: the message's `need` must be the total of the plan the
+    entry lays out for this call (dsdf_debug_ws_plan), which the size queries must cover (dsdf_decode_workspace_bytes: equal)."""
+    from deepsdf_amd import _lib
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)          # (the switches are read per call)
+    if rc != -2:
+        assert _open_call(lib, name, net_kw, over)[:2] == (rc, msg)
+        return
+    kind, seg, K, fr = _OPEN_PLAN[name]
+    K = over.get("cfg.dw_buckets", K)
+    R = _OPEN_R if "train" in name else 0
+    net = _open_call(lib, name, net_kw, dict(over, net=None))[2]
+    assert lib.dsdf_debug_ws_plan(C.byref(net), _OPEN_N, R, kind, seg, K, fr) == 0
+    need = _lib.ws_regions()[1]
+    cover = C.c_size_t()
+    if kind == 0:
+        assert lib.dsdf_workspace_bytes_buckets(C.byref(net), _OPEN_N, R, K, C.byref(cover)) == 0 and need <= cover.value
+    else:
+        assert lib.dsdf_decode_workspace_bytes(C.byref(net), _OPEN_N, C.byref(cover)) == 0
+        assert need == (cover.value if kind == 1 else max(cover.value, 16384))
+    got = need - 1 if over["ws_bytes"] == -1 else over["ws_bytes"]
+    assert _open_call(lib, name, net_kw, dict(over, ws_bytes=got))[:2] == (-2, _WS.format(got=got, need=need))
