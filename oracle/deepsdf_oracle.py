@@ -258,6 +258,8 @@ class Saved:
     latent_mask: Optional[torch.Tensor] = None                 # [N, L] keep mask of latent_dropout (training), else None
     xhat: List[Optional[torch.Tensor]] = field(default_factory=list)   # per layer: LayerNorm's normalised pre-activation, or None
     rstd: List[Optional[torch.Tensor]] = field(default_factory=list)
+    relu_keep: Optional[List[Optional[torch.Tensor]]] = None   # forced ReLU decisions (bool [N, out_l] per hidden layer), or None
+    drop_keep: List[Optional[torch.Tensor]] = field(default_factory=list)   # per hidden layer: the dropout mask applied, or None
 
 
 LATENT_DROPOUT_P = 0.2      # nn.Dropout(0.2), deep_sdf_decoder.py:36
@@ -273,10 +275,15 @@ def latent_dropout_mask(net: Net, seed: int, step: int, n_rows: int, row_offset:
 
 def decoder_forward(net: Net, params, x0: torch.Tensor, training: bool = False,
                     masks: Optional[Sequence[Optional[torch.Tensor]]] = None, track_margin: bool = False,
-                    latent_mask: Optional[torch.Tensor] = None):
-    """x0: [N, L+G] (latent first, coordinates last).  Returns (y [N,1], Saved)."""
+                    latent_mask: Optional[torch.Tensor] = None, relu_keep: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """x0: [N, L+G] (latent first, coordinates last).  Returns (y [N,1], Saved).
+    relu_keep: forced ReLU decisions, one bool [N, out_l] (or None) per hidden layer.  Where one is given the layer computes
+    x * keep in place of clamp_min(x, 0) -- the branch somebody else took, whatever the sign of x here -- and the backward pass
+    uses the same mask instead of a > 0 (a forced activation may be a tiny negative number: its value no longer tells the branch)."""
     Wb = effective_weights(net, params)
     sv = Saved(x0=x0)
+    if relu_keep is not None:
+        sv.relu_keep = [None if k is None else k.to(torch.bool) for k in relu_keep]
     L, G = net.latent_size, net.geom_dimension
     xyz = x0[:, L:]
     x = x0
@@ -313,11 +320,17 @@ def decoder_forward(net: Net, params, x0: torch.Tensor, training: bool = False,
             if track_margin:
                 mn = x.abs().amin(dim=1)
                 sv.min_abs_pre = mn if sv.min_abs_pre is None else torch.minimum(sv.min_abs_pre, mn)
-            x = torch.clamp_min(x, 0.0)
+            if sv.relu_keep is not None and sv.relu_keep[l] is not None:
+                x = torch.where(sv.relu_keep[l], x, torch.zeros_like(x))     # x * keep, without the -0.0 of a negative x times 0
+            else:
+                x = torch.clamp_min(x, 0.0)
             if training and ly.dropout and net.dropout_prob > 0.0:
                 if masks is None or masks[l] is None:
                     raise ValueError("training-mode forward with dropout needs explicit masks")
                 x = x * masks[l].to(x.dtype) * scale
+                sv.drop_keep.append(masks[l].to(torch.bool))
+            else:
+                sv.drop_keep.append(None)
             sv.acts.append(x)
     sv.u = x
     if net.use_tanh:
@@ -384,7 +397,12 @@ def decoder_backward(net: Net, params, sv: Saved, dy: torch.Tensor, training: bo
         prev = net.layers[l - 1]
         s = scale if (training and prev.dropout and net.dropout_prob > 0.0) else 1.0
         # a > 0  <=>  pre-activation > 0 and kept  (mask recovered from the STORED forward value)
-        dp = din * (a > 0).to(din.dtype) * s
+        on = a > 0
+        if sv.relu_keep is not None and sv.relu_keep[l - 1] is not None:      # forced decision: the branch, and what dropout kept of it
+            on = sv.relu_keep[l - 1]
+            if sv.drop_keep[l - 1] is not None:
+                on = on & sv.drop_keep[l - 1]
+        dp = din * on.to(din.dtype) * s
     return grads, dx0
 
 
@@ -393,14 +411,20 @@ def decoder_backward(net: Net, params, sv: Saved, dy: torch.Tensor, training: bo
 # --------------------------------------------------------------------------------------------
 
 
-def clamped_l1(y, sdf_gt, delta: float, n_norm: int):
-    """Returns (loss scalar, dLoss/dy [N,1]).  sdf_gt is clamped here (train_deep_sdf.py:493)."""
+def clamped_l1(y, sdf_gt, delta: float, n_norm: int, forced=None):
+    """Returns (loss scalar, dLoss/dy [N,1]).  sdf_gt is clamped here (train_deep_sdf.py:493).
+    forced: (sign [N,1], inside [N,1]) used for the gradient instead of the two decisions computed here (the loss is a continuous
+    function of y and keeps its own formula)."""
     yh = torch.clamp(y, -delta, delta)
     th = torch.clamp(sdf_gt, -delta, delta)
     diff = yh - th
     loss = diff.abs().sum() / n_norm
-    inside = ((y >= -delta) & (y <= delta)).to(y.dtype)  # clamp backward passes at the boundary
-    dy = torch.sign(diff) * inside / n_norm
+    if forced is not None:
+        sign, inside = (t.reshape(y.shape).to(y.dtype) for t in forced)
+    else:
+        sign = torch.sign(diff)
+        inside = ((y >= -delta) & (y <= delta)).to(y.dtype)  # clamp backward passes at the boundary
+    dy = sign * inside / n_norm
     return loss, dy
 
 
@@ -480,16 +504,21 @@ class TrainState:
 
 
 def step_gradients(net: Net, params, latents, indices, xyz, sdf_gt, *, delta, code_bound,
-                   code_reg, code_reg_lambda, epoch, n_norm=None, training=True, masks=None, latent_mask=None):
+                   code_reg, code_reg_lambda, epoch, n_norm=None, training=True, masks=None, latent_mask=None, decisions=None):
     """One chunk's forward+backward.  ``indices`` [N] int64 (scene of every point).  Mutates ``latents``
-    (renorm) like the reference.  Returns dict(loss, y, grads, dlat [S_tot, L], dx0)."""
+    (renorm) like the reference.  Returns dict(loss, y, grads, dlat [S_tot, L], dx0).
+    decisions: None, or dict(relu_keep=<decoder_forward's>, head=<clamped_l1's forced>) -- either may be missing: the branches
+    of another run of the same step (tests/near_ties.py), taken here whatever this run's own values say."""
     N = xyz.shape[0]
     n_norm = N if n_norm is None else n_norm
     renorm_rows_(latents, indices, code_bound)
     z = latents[indices]
     x0 = torch.cat([z, xyz], dim=1)
-    y, sv = decoder_forward(net, params, x0, training=training, masks=masks, latent_mask=latent_mask)
-    loss, dy = clamped_l1(y, sdf_gt.reshape(-1, 1), delta, n_norm)
+    decisions = decisions or {}                              # (without them the two calls below are exactly the unforced ones)
+    fwd_kw = dict(relu_keep=decisions["relu_keep"]) if decisions.get("relu_keep") is not None else {}
+    l1_kw = dict(forced=decisions["head"]) if decisions.get("head") is not None else {}
+    y, sv = decoder_forward(net, params, x0, training=training, masks=masks, latent_mask=latent_mask, **fwd_kw)
+    loss, dy = clamped_l1(y, sdf_gt.reshape(-1, 1), delta, n_norm, **l1_kw)
     grads, dx0 = decoder_backward(net, params, sv, dy, training)
     L = net.latent_size
     dz = dx0[:, :L].clone()
@@ -499,17 +528,23 @@ def step_gradients(net: Net, params, latents, indices, xyz, sdf_gt, *, delta, co
         dz = dz + dzr
     dlat = torch.zeros_like(latents)
     dlat.index_add_(0, indices, dz)
-    return dict(loss=loss, y=y, grads=grads, dlat=dlat, dx0=dx0)
+    return dict(loss=loss, y=y, grads=grads, dlat=dlat, dx0=dx0, saved=sv)
 
 
 def train_step(net: Net, st: TrainState, indices, xyz, sdf_gt, *, delta, code_bound, code_reg=True,
                code_reg_lambda=1e-4, epoch=1, lr_decoder=5e-4, lr_latent=1e-3, batch_split=1,
-               grad_clip=None, training=True, seed=0, masks_per_chunk=None, betas=(0.9, 0.999), eps=1e-8, n_norm=None):
+               grad_clip=None, training=True, seed=0, masks_per_chunk=None, betas=(0.9, 0.999), eps=1e-8, n_norm=None,
+               decisions=None):
     """Full optimiser step incl. --batch_split accumulation.  Returns dict(loss, grads, dlat, grad_norm, y [N, 1], grads_unclipped: the
     gradients before grad_clip scaled them, None without clipping).
     betas / eps: torch.optim.Adam's (its defaults); n_norm: the loss's divisor where it is not this batch's point count (a
-    data-parallel rank's share of a larger step)."""
+    data-parallel rank's share of a larger step); decisions: step_gradients', one dict for the whole batch (batch_split 1) or a
+    list of one per chunk."""
     N = xyz.shape[0]
+    if decisions is not None and not isinstance(decisions, (list, tuple)):
+        if batch_split != 1:
+            raise ValueError("forced decisions of a split batch come as a list, one entry per chunk")
+        decisions = [decisions]
     ys = []
     xs, is_, ts = torch.chunk(xyz, batch_split), torch.chunk(indices, batch_split), torch.chunk(sdf_gt, batch_split)
     tot_g = None
@@ -527,7 +562,8 @@ def train_step(net: Net, st: TrainState, indices, xyz, sdf_gt, *, delta, code_bo
         lmask = latent_dropout_mask(net, seed, st.step, n, row_offset=row0) if (training and net.latent_dropout) else None
         r = step_gradients(net, st.params, st.latents, is_[ci], xs[ci], ts[ci], delta=delta,
                            code_bound=code_bound, code_reg=code_reg, code_reg_lambda=code_reg_lambda,
-                           epoch=epoch, n_norm=N if n_norm is None else n_norm, training=training, masks=masks, latent_mask=lmask)
+                           epoch=epoch, n_norm=N if n_norm is None else n_norm, training=training, masks=masks, latent_mask=lmask,
+                           decisions=None if decisions is None else decisions[ci])
         loss += float(r["loss"])
         ys.append(r["y"])
         tot_dlat += r["dlat"]
