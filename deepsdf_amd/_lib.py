@@ -3,6 +3,9 @@ no CPU fallback anywhere in this package."""
 import ctypes as C
 import os
 
+import numpy as np
+import torch  # before the library is loaded: lib() below says why
+
 from .build import LIB
 
 MAX_LAYERS = 16
@@ -201,8 +204,8 @@ def lib():
     if _lib is not None:
         return _lib
     # torch bundles its own libamdhip64; it must be in the process BEFORE our library is dlopen'ed so that both use
-    # ONE HIP runtime (loaded the other way round, ours binds /opt/rocm's copy and sees "no ROCm-capable device")
-    import torch  # noqa: F401
+    # ONE HIP runtime (loaded the other way round, ours binds /opt/rocm's copy and sees "no ROCm-capable device"): the import
+    # at the top of this module
     if not os.path.exists(LIB):
         raise DsdfError(f"{LIB} is missing: build it with `python -m deepsdf_amd.build` "
                         "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
@@ -227,6 +230,24 @@ def ws_regions():
     table = (DsdfWsRegion * WS_MAX_REGIONS)()
     check(lib().dsdf_debug_ws_regions(table, WS_MAX_REGIONS, C.byref(n), C.byref(total)))
     return [(table[i].name.decode(), int(table[i].offset), int(table[i].bytes)) for i in range(n.value)], int(total.value)
+
+
+def ptr(t):
+    """A tensor's address for a void* argument; None is NULL."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def stream():
+    """torch's current stream for a `void* stream` argument."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def triple(x, what):
+    """Three floats from a scalar or a sequence of three."""
+    t = [float(v) for v in (x if isinstance(x, (list, tuple, np.ndarray, torch.Tensor)) else [x] * 3)]
+    if len(t) != 3:
+        raise ValueError(f"{what} needs 3 values, got {len(t)}")
+    return t
 
 
 def check(rc):

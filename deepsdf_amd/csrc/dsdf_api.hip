@@ -2111,9 +2111,15 @@ struct McPlan {
   size_t mask, cas, vbase, bv, bf, ov, of, total;
 };
 
-int mc_plan(int32_t nx, int32_t ny, int32_t nz, McPlan* P, WsTable* rec = nullptr) {
+// The grid every mesher and the sparse grid accept: 2 .. MC_MAX_DIM points per axis.
+int grid_dims_ok(const char* what, int32_t nx, int32_t ny, int32_t nz) {
   if (nx < 2 || ny < 2 || nz < 2 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
-    return fail(DSDF_E_INVALID, "marching cubes: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
+    return fail(DSDF_E_INVALID, "%s: grid %d x %d x %d outside [2, %d] per axis", what, nx, ny, nz, MC_MAX_DIM);
+  return 0;
+}
+
+int mc_plan(int32_t nx, int32_t ny, int32_t nz, McPlan* P, WsTable* rec = nullptr) {
+  TRY(grid_dims_ok("marching cubes", nx, ny, nz));
   P->npts = (int64_t)nx * ny * nz;
   P->nblocks = (P->npts + MC_BLOCK - 1) / MC_BLOCK;
   WsCarver c(rec);
@@ -2162,8 +2168,9 @@ int dsdf_mc_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float le
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)P.nblocks), dim3(MC_BLOCK), 0, st, g, w);
   LAUNCH_OK("mc_classify_kernel");
-  hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w, totals);
-  LAUNCH_OK("mc_scan_kernel");
+  const OffsetScan<2> scan = {{w.bv, w.bf}, {w.ov, w.of}, w.nblocks, totals};
+  hipLaunchKernelGGL(offset_scan_kernel<2>, dim3(1), dim3(MC_SCAN_THREADS), 0, st, scan);
+  LAUNCH_OK("offset_scan_kernel<2>");
   return 0;
 }
 
@@ -2718,6 +2725,8 @@ int dsdf_ms_caps(const DsdfMsGrid* grid, int64_t start, int64_t end, const DsdfM
   return 0;
 }
 
+}  // extern "C"
+
 // ---- surface topology and geometry (meshtopo.hpp) ----------------------------------------------------------
 namespace {
 struct MtPlan { int64_t stat_blocks, vol_blocks, vol_slice; size_t stat_off, gf_off, flag_off, vol_off, ws; };
@@ -2750,7 +2759,42 @@ int mt_ws(const MtPlan& P, const void* ws, size_t ws_bytes) {
 }
 
 inline dim3 mt_grid(int64_t n) { return dim3((unsigned)((n + MT_BLOCK - 1) / MT_BLOCK)); }
+
+// The host loop of components.hpp over n nodes, after the caller's init kernel: launch_hook(flag) enqueues the caller's hook kernel
+// and returns its status.  Waits for the stream: the change flags of every MT_CC_GROUP rounds are read on the host (as
+// dsdf_surf_prepare reads its total).  Then the component sizes, if asked for.
+template <class Hook>
+int cc_run(hipStream_t st, int32_t* label, int32_t* gf, int32_t* flags, int64_t n, Hook launch_hook, int32_t* size, int32_t* n_rounds) {
+  const dim3 grid((unsigned)((n + CC_BLOCK - 1) / CC_BLOCK));
+  int rounds = 0;
+  for (bool done = false; !done;) {                          // no cap: f only decreases, so a round without a change comes
+    hipLaunchKernelGGL(cc_flags_kernel, dim3(1), dim3(CC_BLOCK), 0, st, flags);
+    LAUNCH_OK("cc_flags_kernel");
+    for (int r = 0; r < MT_CC_GROUP; ++r) {
+      hipLaunchKernelGGL(cc_grand_kernel, grid, dim3(CC_BLOCK), 0, st, (const int32_t*)label, n, gf);
+      LAUNCH_OK("cc_grand_kernel");
+      TRY(launch_hook(flags + r));
+    }
+    int32_t host[MT_CC_GROUP];
+    HIP_OK(hipMemcpyAsync(host, flags, sizeof(host), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int r = 0; r < MT_CC_GROUP && !done; ++r) {
+      ++rounds;
+      done = host[r] == 0;
+    }
+  }
+  if (n_rounds) *n_rounds = rounds;
+  if (size) {
+    hipLaunchKernelGGL(cc_zero_kernel, grid, dim3(CC_BLOCK), 0, st, size, n);
+    LAUNCH_OK("cc_zero_kernel");
+    hipLaunchKernelGGL(cc_size_kernel, grid, dim3(CC_BLOCK), 0, st, (const int32_t*)label, n, size);
+    LAUNCH_OK("cc_size_kernel");
+  }
+  return 0;
+}
 }  // namespace
+
+extern "C" {
 
 int dsdf_mt_plan(int64_t n_verts, int64_t n_faces, size_t* ws_bytes) {
   MtPlan P;
@@ -2789,7 +2833,6 @@ int dsdf_mt_adjacency(const int32_t* faces, int64_t n_faces, const int64_t* sort
   return 0;
 }
 
-// Waits for the stream: the change flags of every MT_CC_GROUP rounds are read on the host (as dsdf_surf_prepare reads its total).
 int dsdf_mt_components(const int32_t* mate, int64_t n_faces, int32_t* label, int32_t* size, int32_t* n_rounds, void* ws,
                        size_t ws_bytes, void* stream) {
   MtPlan P;
@@ -2805,32 +2848,11 @@ int dsdf_mt_components(const int32_t* mate, int64_t n_faces, int32_t* label, int
   const dim3 grid = mt_grid(n_faces);
   hipLaunchKernelGGL(mt_cc_init_kernel, grid, dim3(MT_BLOCK), 0, st, label, nf);
   LAUNCH_OK("mt_cc_init_kernel");
-  int rounds = 0;
-  for (bool done = false; !done;) {                          // no cap: f only decreases, so a round without a change comes
-    hipLaunchKernelGGL(mt_cc_flags_kernel, dim3(1), dim3(MT_BLOCK), 0, st, flags);
-    LAUNCH_OK("mt_cc_flags_kernel");
-    for (int r = 0; r < MT_CC_GROUP; ++r) {
-      hipLaunchKernelGGL(mt_cc_grand_kernel, grid, dim3(MT_BLOCK), 0, st, (const int32_t*)label, nf, gf);
-      LAUNCH_OK("mt_cc_grand_kernel");
-      hipLaunchKernelGGL(mt_cc_hook_kernel, grid, dim3(MT_BLOCK), 0, st, mate, nf, label, (const int32_t*)gf, flags + r);
-      LAUNCH_OK("mt_cc_hook_kernel");
-    }
-    int32_t host[MT_CC_GROUP];
-    HIP_OK(hipMemcpyAsync(host, flags, sizeof(host), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (int r = 0; r < MT_CC_GROUP && !done; ++r) {
-      ++rounds;
-      done = host[r] == 0;
-    }
-  }
-  if (n_rounds) *n_rounds = rounds;
-  if (size) {
-    hipLaunchKernelGGL(mt_cc_zero_kernel, grid, dim3(MT_BLOCK), 0, st, size, nf);
-    LAUNCH_OK("mt_cc_zero_kernel");
-    hipLaunchKernelGGL(mt_cc_size_kernel, grid, dim3(MT_BLOCK), 0, st, (const int32_t*)label, nf, size);
-    LAUNCH_OK("mt_cc_size_kernel");
-  }
-  return 0;
+  return cc_run(st, label, gf, flags, n_faces, [&](int32_t* flag) {
+    hipLaunchKernelGGL(mt_cc_hook_kernel, grid, dim3(MT_BLOCK), 0, st, mate, nf, label, (const int32_t*)gf, flag);
+    LAUNCH_OK("mt_cc_hook_kernel");
+    return 0;
+  }, size, n_rounds);
 }
 
 int dsdf_mt_face_degenerate(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, uint8_t* out, void* stream) {
@@ -2910,8 +2932,7 @@ struct SgPlan {
 };
 
 int sg_plan(int32_t nx, int32_t ny, int32_t nz, int32_t block, SgPlan* P, WsTable* rec = nullptr) {
-  if (nx < 2 || ny < 2 || nz < 2 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
-    return fail(DSDF_E_INVALID, "sparse grid: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
+  TRY(grid_dims_ok("sparse grid", nx, ny, nz));
   if (block < 2) return fail(DSDF_E_INVALID, "sparse grid: block edge %d < 2 cells", block);
   SgGrid& g = P->g;
   g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
@@ -3012,8 +3033,9 @@ int dsdf_sg_points_count(int32_t nx, int32_t ny, int32_t nz, int32_t block, int6
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(sg_points_count_kernel, sg_launch(P.g.npts), dim3(SG_BLOCK), 0, st, P.g, (const uint8_t*)w.state, (const uint8_t*)w.have, w.part);
   LAUNCH_OK("sg_points_count_kernel");
-  hipLaunchKernelGGL(sg_scan_kernel, dim3(1), dim3(SG_SCAN_THREADS), 0, st, (const int32_t*)w.part, P.nparts, w.offs, n_points);
-  LAUNCH_OK("sg_scan_kernel");
+  const OffsetScan<1> scan = {{w.part}, {w.offs}, P.nparts, n_points};
+  hipLaunchKernelGGL(offset_scan_kernel<1>, dim3(1), dim3(MC_SCAN_THREADS), 0, st, scan);
+  LAUNCH_OK("offset_scan_kernel<1>");
   return 0;
 }
 
@@ -3097,8 +3119,7 @@ struct TetPlan {
 };
 
 int tet_plan(int32_t nx, int32_t ny, int32_t nz, TetPlan* P, WsTable* rec = nullptr) {
-  if (nx < 2 || ny < 2 || nz < 2 || nx > MC_MAX_DIM || ny > MC_MAX_DIM || nz > MC_MAX_DIM)
-    return fail(DSDF_E_INVALID, "tet mesh: grid %d x %d x %d outside [2, %d] per axis", nx, ny, nz, MC_MAX_DIM);
+  TRY(grid_dims_ok("tet mesh", nx, ny, nz));
   P->npts = (int64_t)nx * ny * nz;
   P->nblocks = (P->npts + TET_BLOCK - 1) / TET_BLOCK;
   WsCarver c(rec);
@@ -3111,7 +3132,7 @@ int tet_plan(int32_t nx, int32_t ny, int32_t nz, TetPlan* P, WsTable* rec = null
   for (int s = 0; s < 3; ++s) P->bcount[s] = c.take(cnt_name[s], -1, (size_t)P->nblocks * 4);
   for (int s = 0; s < 3; ++s) P->boff[s] = c.take(off_name[s], -1, (size_t)(P->nblocks + 1) * 8);
   P->gf = c.take("tet_cc_gf", -1, (size_t)P->npts * 4);
-  P->flags = c.take("tet_cc_flags", -1, (size_t)TET_CC_GROUP * 4);
+  P->flags = c.take("tet_cc_flags", -1, (size_t)MT_CC_GROUP * 4);
   P->total = c.finish(c.o);
   return 0;
 }
@@ -3147,8 +3168,9 @@ int dsdf_tet_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float l
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(tet_classify_kernel, dim3((unsigned)P.nblocks), dim3(TET_BLOCK), 0, st, g, w);
   LAUNCH_OK("tet_classify_kernel");
-  hipLaunchKernelGGL(tet_scan_kernel, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w, totals);
-  LAUNCH_OK("tet_scan_kernel");
+  const OffsetScan<3> scan = {{w.bcount[0], w.bcount[1], w.bcount[2]}, {w.boff[0], w.boff[1], w.boff[2]}, w.nblocks, totals};
+  hipLaunchKernelGGL(offset_scan_kernel<3>, dim3(1), dim3(MC_SCAN_THREADS), 0, st, scan);
+  LAUNCH_OK("offset_scan_kernel<3>");
   return 0;
 }
 
@@ -3181,7 +3203,6 @@ int dsdf_tet_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float le
   return 0;
 }
 
-// Waits for the stream: the change flags of every TET_CC_GROUP rounds are read on the host (as dsdf_mt_components does).
 int dsdf_tet_components(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int32_t* label, int32_t* size,
                         int32_t* n_rounds, void* ws, size_t ws_bytes, void* stream) {
   McGrid g; TetWs w; TetPlan P;
@@ -3194,32 +3215,11 @@ int dsdf_tet_components(const float* sdf, int32_t nx, int32_t ny, int32_t nz, fl
   const dim3 grid((unsigned)P.nblocks);
   hipLaunchKernelGGL(tet_cc_init_kernel, grid, dim3(TET_BLOCK), 0, st, g, label);
   LAUNCH_OK("tet_cc_init_kernel");
-  int rounds = 0;
-  for (bool done = false; !done;) {                          // no cap: f only decreases, so a round without a change comes
-    hipLaunchKernelGGL(mt_cc_flags_kernel, dim3(1), dim3(MT_BLOCK), 0, st, flags);
-    LAUNCH_OK("mt_cc_flags_kernel");
-    for (int r = 0; r < TET_CC_GROUP; ++r) {
-      hipLaunchKernelGGL(tet_cc_grand_kernel, grid, dim3(TET_BLOCK), 0, st, (const int32_t*)label, P.npts, gf);
-      LAUNCH_OK("tet_cc_grand_kernel");
-      hipLaunchKernelGGL(tet_cc_hook_kernel, grid, dim3(TET_BLOCK), 0, st, g, label, (const int32_t*)gf, flags + r);
-      LAUNCH_OK("tet_cc_hook_kernel");
-    }
-    int32_t host[TET_CC_GROUP];
-    HIP_OK(hipMemcpyAsync(host, flags, sizeof(host), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (int r = 0; r < TET_CC_GROUP && !done; ++r) {
-      ++rounds;
-      done = host[r] == 0;
-    }
-  }
-  if (n_rounds) *n_rounds = rounds;
-  if (size) {
-    hipLaunchKernelGGL(tet_cc_zero_kernel, grid, dim3(TET_BLOCK), 0, st, size, P.npts);
-    LAUNCH_OK("tet_cc_zero_kernel");
-    hipLaunchKernelGGL(tet_cc_size_kernel, grid, dim3(TET_BLOCK), 0, st, (const int32_t*)label, P.npts, size);
-    LAUNCH_OK("tet_cc_size_kernel");
-  }
-  return 0;
+  return cc_run(st, label, gf, flags, P.npts, [&](int32_t* flag) {
+    hipLaunchKernelGGL(tet_cc_hook_kernel, grid, dim3(TET_BLOCK), 0, st, g, label, (const int32_t*)gf, flag);
+    LAUNCH_OK("tet_cc_hook_kernel");
+    return 0;
+  }, size, n_rounds);
 }
 
 }  // extern "C"

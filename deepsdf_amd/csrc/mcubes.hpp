@@ -7,7 +7,8 @@
 // Passes (one thread per grid point, MC_BLOCK points per workgroup, linear order):
 //   1. classify:  mask[p] = 3-bit crossing mask of p's edges, cas[p] = 8-bit case of the cell at p (0 off the cell range);
 //                 per workgroup, its vertex and triangle totals
-//   2. scan:      one workgroup turns the per-workgroup totals into 64-bit exclusive offsets (+ the two grand totals)
+//   2. scan:      one workgroup turns the per-workgroup totals into 64-bit exclusive offsets (+ the two grand totals):
+//                 blockops.hpp's offset_scan_kernel<2>
 //   3. vertices:  workgroup scan of popcount(mask) + offset -> vbase[p] (id of p's first vertex) and the interpolated positions
 //   4. faces:     workgroup scan of the triangle counts + offset; edge (corner c of cell p, axis a) has vertex id
 //                 vbase[q] + popcount(mask[q] & ((1 << a) - 1)), q = p + offset(c): no edge-id map
@@ -18,14 +19,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blockops.hpp"
 #include "common.hpp"
 #include "mc_table.hpp"
 
 namespace dsdf {
 
 constexpr int MC_BLOCK = 256;
-constexpr int MC_SCAN_THREADS = 1024;
-constexpr int MC_SCAN_PER_THREAD = 8;
 constexpr int MC_MAX_DIM = 1024;
 
 __constant__ int8_t mc_tri_d[256][MC_TABLE_W] = DSDF_MC_TRI_INIT;
@@ -58,35 +58,13 @@ struct McOut {
   int64_t nv, nf;         // sizes of the caller's buffers: nothing is written past them
 };
 
-// Inclusive scan of one int per thread over the MC_BLOCK threads of a workgroup (Hillis-Steele in LDS).
-__device__ __forceinline__ int mc_block_scan(int x, int* s) {
-  const int t = threadIdx.x;
-  s[t] = x;
-  __syncthreads();
-  for (int d = 1; d < MC_BLOCK; d <<= 1) {
-    const int y = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += y;
-    __syncthreads();
-  }
-  return s[t];
-}
-
-__device__ __forceinline__ void mc_coords(int64_t p, const McGrid& g, int& i, int& j, int& k) {
-  const int64_t syz = (int64_t)g.ny * g.nz;
-  i = (int)(p / syz);
-  const int r = (int)(p - (int64_t)i * syz);
-  j = r / g.nz;
-  k = r - j * g.nz;
-}
-
 __global__ __launch_bounds__(MC_BLOCK) void mc_classify_kernel(McGrid g, McWs w) {
   __shared__ int s[MC_BLOCK];
   const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
   int nv = 0, nt = 0;
   if (p < g.npts) {
     int i, j, k;
-    mc_coords(p, g, i, j, k);
+    grid_ijk(p, g.ny, g.nz, i, j, k);
     const int64_t syz = (int64_t)g.ny * g.nz;
     const float* v = g.sdf + p;
     const bool in0 = v[0] < g.level;
@@ -109,56 +87,10 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_classify_kernel(McGrid g, McWs w)
     nt = mc_ntri_d[cs];
   }
   // both counts in one scan: a workgroup has at most 3 * 256 vertices and 5 * 256 triangles (< 2^16 each)
-  const int tot = mc_block_scan(nv | (nt << 16), s);
+  const int tot = block_scan_incl<int, MC_BLOCK>(nv | (nt << 16), s);
   if (threadIdx.x == MC_BLOCK - 1) {
     w.bv[blockIdx.x] = tot & 0xFFFF;
     w.bf[blockIdx.x] = tot >> 16;
-  }
-}
-
-// One workgroup: exclusive 64-bit scans of bv and bf into ov / of, the grand totals into ov[nb], of[nb] and totals[0..1].
-__global__ __launch_bounds__(MC_SCAN_THREADS) void mc_scan_kernel(McWs w, int64_t* totals) {
-  __shared__ int64_t sv[MC_SCAN_THREADS], sf[MC_SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int64_t nb = w.nblocks;
-  int64_t carry_v = 0, carry_f = 0;
-  for (int64_t base = 0; base < nb; base += (int64_t)MC_SCAN_THREADS * MC_SCAN_PER_THREAD) {
-    const int64_t b0 = base + (int64_t)t * MC_SCAN_PER_THREAD;
-    int64_t xv = 0, xf = 0;
-    for (int q = 0; q < MC_SCAN_PER_THREAD; ++q) {
-      if (b0 + q < nb) {
-        xv += w.bv[b0 + q];
-        xf += w.bf[b0 + q];
-      }
-    }
-    sv[t] = xv;
-    sf[t] = xf;
-    __syncthreads();
-    for (int d = 1; d < MC_SCAN_THREADS; d <<= 1) {
-      const int64_t yv = t >= d ? sv[t - d] : 0, yf = t >= d ? sf[t - d] : 0;
-      __syncthreads();
-      sv[t] += yv;
-      sf[t] += yf;
-      __syncthreads();
-    }
-    int64_t ev = carry_v + sv[t] - xv, ef = carry_f + sf[t] - xf;     // exclusive offset of element b0
-    for (int q = 0; q < MC_SCAN_PER_THREAD; ++q) {
-      if (b0 + q < nb) {
-        w.ov[b0 + q] = ev;
-        w.of[b0 + q] = ef;
-        ev += w.bv[b0 + q];
-        ef += w.bf[b0 + q];
-      }
-    }
-    carry_v += sv[MC_SCAN_THREADS - 1];
-    carry_f += sf[MC_SCAN_THREADS - 1];
-    __syncthreads();     // every thread has read the last entries before the next chunk overwrites them
-  }
-  if (t == 0) {
-    w.ov[nb] = carry_v;
-    w.of[nb] = carry_f;
-    totals[0] = carry_v;
-    totals[1] = carry_f;
   }
 }
 
@@ -167,13 +99,13 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_vertex_kernel(McGrid g, McWs w, M
   const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
   const uint32_t m = p < g.npts ? w.mask[p] : 0u;
   const int n = __popc(m);
-  const int inc = mc_block_scan(n, s);
+  const int inc = block_scan_incl<int, MC_BLOCK>(n, s);
   if (p >= g.npts) return;
   int64_t id = w.ov[blockIdx.x] + inc - n;
   w.vbase[p] = (int32_t)id;          // the host refuses totals above INT32_MAX before this launch
   if (!m) return;
   int i, j, k;
-  mc_coords(p, g, i, j, k);
+  grid_ijk(p, g.ny, g.nz, i, j, k);
   const int64_t stride[3] = {(int64_t)g.ny * g.nz, (int64_t)g.nz, 1};
   const int idx[3] = {i, j, k};
   const float v0 = g.sdf[p];
@@ -202,7 +134,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_edge_kernel(int64_t npts, McWs w,
   const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
   const uint32_t m = p < npts ? w.mask[p] : 0u;
   const int n = __popc(m);
-  const int inc = mc_block_scan(n, s);
+  const int inc = block_scan_incl<int, MC_BLOCK>(n, s);
   if (!m) return;
   int64_t id = w.ov[blockIdx.x] + inc - n;
   for (int a = 0; a < 3; ++a) {
@@ -220,7 +152,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_face_kernel(McGrid g, McWs w, McO
   const int64_t p = (int64_t)blockIdx.x * MC_BLOCK + threadIdx.x;
   const uint32_t cs = p < g.npts ? w.cas[p] : 0u;
   const int n = mc_ntri_d[cs];
-  const int inc = mc_block_scan(n, s);
+  const int inc = block_scan_incl<int, MC_BLOCK>(n, s);
   if (p >= g.npts || n == 0) return;
   const int64_t first = w.of[blockIdx.x] + inc - n;
   const int64_t syz = (int64_t)g.ny * g.nz;

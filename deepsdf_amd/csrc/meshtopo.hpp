@@ -6,11 +6,8 @@
 //   mt_adjacency_kernel    a stencil over positions i - 2 .. i + 2 of the sorted keys: a key >= 0 that occurs exactly twice pairs its two
 //                          half-edges (trimesh's face_adjacency rule: an edge of 1 or of more than 2 faces joins nothing); six integer
 //                          counts per workgroup, summed by mt_stats_sum_kernel in workgroup order
-//   mt_cc_*                connected components of the faces under the mate relation by min-hooking with shortcutting (the shape of
-//                          FastSV): per round gf = f[f], then for every mated pair (u, v) f[f[u]] <- min(., gf[v]), f[u] <- min(., gf[v]),
-//                          and f[u] <- min(., gf[u]).  f only ever decreases, f[u] <= u names a face of u's component throughout, and
-//                          the only fixed point is f[u] = the lowest face index of u's component: the int32 atomicMin / atomicAdd here
-//                          (the ONLY atomics of this file) change the road, never the result.
+//   mt_cc_*                connected components of the faces under the mate relation: the init and hook kernels of components.hpp's
+//                          scheme (min-hooking with shortcutting; its int32 atomicMin / atomicAdd are the ONLY atomics this file uses)
 //   mt_degenerate_kernel   the zero-area rule of meshsdf.hpp's prepare pass (|ab x ac|^2 <= 1e-14 (longest edge)^4, fp64 on the fp32
 //                          vertices), restated: sharing the function would change that kernel's code object
 //   mt_vertex_kernel       one lane per vertex gathers its corners (sorted by vertex: a fixed order, no atomics), fp64 throughout:
@@ -24,16 +21,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blockops.hpp"
+#include "components.hpp"
+
 namespace dsdf {
 
 constexpr int MT_BLOCK = 256;            // lanes per workgroup of every kernel of this file
 constexpr int MT_VOL_MAX_BLOCKS = 1024;  // partial sums of the volume
 constexpr int MT_VOL_MIN_SLICE = 4096;   // faces per workgroup before a second workgroup is started
-constexpr int MT_CC_GROUP = 4;           // rounds enqueued between two reads of the change flags on the host
 constexpr int MT_STATS = 6;              // distinct, boundary, non-manifold, paired, paired same-direction, key -1
+constexpr int MT_STAT_BITS = 10;         // of a workgroup's count of one of them
+static_assert(MT_BLOCK < (1 << MT_STAT_BITS) && MT_STATS * MT_STAT_BITS < 64, "six counts share one summed int64");
 
 __device__ __forceinline__ int mt_clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-__device__ __forceinline__ int64_t mt_clampl(int64_t i, int64_t n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
 
 __global__ __launch_bounds__(MT_BLOCK) void mt_edge_keys_kernel(const int32_t* __restrict__ F, int64_t n_half, int nv,
                                                                 int64_t* __restrict__ keys) {
@@ -55,7 +55,7 @@ __device__ __forceinline__ int mt_ascending(const int32_t* __restrict__ F, int64
 __global__ __launch_bounds__(MT_BLOCK) void mt_adjacency_kernel(const int32_t* __restrict__ F, int64_t n_half,
                                                                 const int64_t* __restrict__ keys, const int64_t* __restrict__ order,
                                                                 int32_t* __restrict__ mate, int64_t* __restrict__ part) {
-  __shared__ int cnt[MT_STATS][MT_BLOCK];
+  __shared__ int64_t sh[MT_BLOCK];
   const int t = threadIdx.x;
   const int64_t i = (int64_t)blockIdx.x * MT_BLOCK + t;
   int c[MT_STATS] = {0, 0, 0, 0, 0, 0};
@@ -63,13 +63,13 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_adjacency_kernel(const int32_t* _
     const int64_t k = keys[i];
     const bool p1 = i >= 1 && keys[i - 1] == k, p2 = i >= 2 && keys[i - 2] == k;
     const bool n1 = i + 1 < n_half && keys[i + 1] == k, n2 = i + 2 < n_half && keys[i + 2] == k;
-    const int64_t h = mt_clampl(order[i], n_half);
+    const int64_t h = clamp_index(order[i], n_half);
     int64_t other = -1;
     if (k >= 0) {
       if (p1 && !p2 && !n1) other = i - 1;                    // the second of a run of exactly two
       else if (n1 && !p1 && !n2) other = i + 1;               // the first of one
     }
-    const int64_t ho = other >= 0 ? mt_clampl(order[other], n_half) : -1;
+    const int64_t ho = other >= 0 ? clamp_index(order[other], n_half) : -1;
     mate[h] = (int32_t)ho;
     if (k < 0) c[5] = 1;
     else if (!p1) {                                           // the first position of its run counts the edge
@@ -82,14 +82,11 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_adjacency_kernel(const int32_t* _
       }
     }
   }
-  for (int s = 0; s < MT_STATS; ++s) cnt[s][t] = c[s];
-  __syncthreads();
-  for (int w = MT_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w)
-      for (int s = 0; s < MT_STATS; ++s) cnt[s][t] += cnt[s][t + w];
-    __syncthreads();
-  }
-  if (t < MT_STATS) part[(int64_t)blockIdx.x * MT_STATS + t] = cnt[t][0];
+  // the six counts, each at most MT_BLOCK, ride in one sum: MT_STAT_BITS bits apiece
+  int64_t packed = 0;
+  for (int s = 0; s < MT_STATS; ++s) packed |= (int64_t)c[s] << (MT_STAT_BITS * s);
+  const int64_t tot = block_tree_sum<int64_t, MT_BLOCK>(packed, sh);
+  if (t < MT_STATS) part[(int64_t)blockIdx.x * MT_STATS + t] = (tot >> (MT_STAT_BITS * t)) & ((1 << MT_STAT_BITS) - 1);
 }
 
 __global__ __launch_bounds__(MT_BLOCK) void mt_stats_sum_kernel(const int64_t* __restrict__ part, int64_t n_part,
@@ -99,13 +96,8 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_stats_sum_kernel(const int64_t* _
   for (int s = 0; s < MT_STATS; ++s) {
     int64_t a = 0;
     for (int64_t b = t; b < n_part; b += MT_BLOCK) a += part[b * MT_STATS + s];
-    sh[t] = a;
-    __syncthreads();
-    for (int w = MT_BLOCK / 2; w > 0; w >>= 1) {
-      if (t < w) sh[t] += sh[t + w];
-      __syncthreads();
-    }
-    if (t == 0) stats[s] = sh[0];
+    const int64_t tot = block_tree_sum<int64_t, MT_BLOCK>(a, sh);
+    if (t == 0) stats[s] = tot;
     __syncthreads();
   }
 }
@@ -116,17 +108,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_cc_init_kernel(int32_t* __restric
   if (u < nf) f[u] = (int32_t)u;
 }
 
-__global__ __launch_bounds__(MT_BLOCK) void mt_cc_flags_kernel(int32_t* __restrict__ flags) {
-  if (threadIdx.x < MT_CC_GROUP) flags[threadIdx.x] = 0;
-}
-
-__global__ __launch_bounds__(MT_BLOCK) void mt_cc_grand_kernel(const int32_t* __restrict__ f, int nf, int32_t* __restrict__ gf) {
-  const int64_t u = (int64_t)blockIdx.x * MT_BLOCK + threadIdx.x;
-  if (u < nf) gf[u] = f[mt_clampi(f[u], nf)];
-}
-
-// f is read plainly while other lanes lower it: a stale value is a larger one, still a face of the same component, and costs at
-// most an atomic that changes nothing.  gf is constant during the launch.  *flag != 0 afterwards: some f went down.
+// *flag != 0 afterwards: some f went down.
 __global__ __launch_bounds__(MT_BLOCK) void mt_cc_hook_kernel(const int32_t* __restrict__ mate, int nf, int32_t* f,
                                                               const int32_t* __restrict__ gf, int32_t* __restrict__ flag) {
   const int64_t u = (int64_t)blockIdx.x * MT_BLOCK + threadIdx.x;
@@ -138,21 +120,11 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_cc_hook_kernel(const int32_t* __r
     const int m = mate[u * 3 + k];
     if (m < 0) continue;
     const int g = gf[mt_clampi(m / 3, nf)];
-    if (g < f[fu]) changed |= atomicMin(&f[fu], g) > g;
+    changed |= cc_lower(f, fu, g);
     best = g < best ? g : best;
   }
-  if (best < f[u]) changed |= atomicMin(&f[u], best) > best;
+  changed |= cc_lower(f, u, best);
   if (changed) *flag = 1;
-}
-
-__global__ __launch_bounds__(MT_BLOCK) void mt_cc_zero_kernel(int32_t* __restrict__ size, int nf) {
-  const int64_t u = (int64_t)blockIdx.x * MT_BLOCK + threadIdx.x;
-  if (u < nf) size[u] = 0;
-}
-
-__global__ __launch_bounds__(MT_BLOCK) void mt_cc_size_kernel(const int32_t* __restrict__ label, int nf, int32_t* __restrict__ size) {
-  const int64_t u = (int64_t)blockIdx.x * MT_BLOCK + threadIdx.x;
-  if (u < nf) atomicAdd(&size[mt_clampi(label[u], nf)], 1);
 }
 
 // ---- geometry -----------------------------------------------------------------------------------------------------------------
@@ -209,7 +181,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_vertex_kernel(const float* __rest
   hi = hi < lo ? lo : (hi > n_half ? n_half : hi);
   double s[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
   for (int64_t i = lo; i < hi; ++i) {
-    const int64_t c = mt_clampl(corner_order[i], n_half);
+    const int64_t c = clamp_index(corner_order[i], n_half);
     const int64_t f = c / 3;
     const MtTri t = mt_face(V, nv, F, f, (int)(c - f * 3));
     double bc[3];
@@ -229,18 +201,6 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_vertex_kernel(const float* __rest
     for (int x = 0; x < 3; ++x) vol_grad[v * 3 + x] = (float)(g[x] / 6.0);
 }
 
-// Sum of the workgroup's lane values in a fixed tree; valid in lane 0.
-__device__ __forceinline__ double mt_block_sum(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int w = MT_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w) sh[t] += sh[t + w];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 __global__ __launch_bounds__(MT_BLOCK) void mt_volume_part_kernel(const float* __restrict__ V, int nv, const int32_t* __restrict__ F,
                                                                   int64_t nf, int64_t slice, double* __restrict__ part) {
   __shared__ double sh[MT_BLOCK];
@@ -253,7 +213,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_volume_part_kernel(const float* _
     mt_cross(t.b, t.c, bc);
     s += mt_dot(t.a, bc);
   }
-  const double tot = mt_block_sum(s, sh);
+  const double tot = block_tree_sum<double, MT_BLOCK>(s, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -261,7 +221,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_volume_final_kernel(const double*
   __shared__ double sh[MT_BLOCK];
   double s = 0.0;
   for (int i = threadIdx.x; i < n_part; i += MT_BLOCK) s += part[i];
-  const double tot = mt_block_sum(s, sh);
+  const double tot = block_tree_sum<double, MT_BLOCK>(s, sh);
   if (threadIdx.x == 0) volume[0] = tot / 6.0;
 }
 

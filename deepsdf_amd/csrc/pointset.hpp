@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blockops.hpp"
 #include "common.hpp"
 
 namespace dsdf {
@@ -98,18 +99,6 @@ constexpr int MEAN_BLOCK = 256;
 constexpr int MEAN_MAX_BLOCKS = 1024;          // partial sums: the fixed workspace of dsdf_mean_f64 (DSDF_MEAN_WS_BYTES)
 constexpr int MEAN_MIN_SLICE = 4096;           // values per workgroup before a second workgroup is started
 
-// Sum of the calling workgroup's 256 lane values in a fixed tree; valid in lane 0.
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int w = MEAN_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w) sh[t] += sh[t + w];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // Workgroup b sums x[b * slice, min(n, (b + 1) * slice)): lane t takes elements t, t + 256, ... of the slice in order.
 __global__ __launch_bounds__(MEAN_BLOCK) void mean_partial_kernel(const float* __restrict__ x, int64_t n, int64_t slice,
                                                                   double* __restrict__ part) {
@@ -118,7 +107,7 @@ __global__ __launch_bounds__(MEAN_BLOCK) void mean_partial_kernel(const float* _
   const int64_t i1 = i0 + slice < n ? i0 + slice : n;
   double s = 0.0;
   for (int64_t i = i0 + threadIdx.x; i < i1; i += MEAN_BLOCK) s += (double)x[i];
-  const double tot = block_sum_f64(s, sh);
+  const double tot = block_tree_sum<double, MEAN_BLOCK>(s, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -127,7 +116,7 @@ __global__ __launch_bounds__(MEAN_BLOCK) void mean_final_kernel(const double* __
   __shared__ double sh[MEAN_BLOCK];
   double s = 0.0;
   for (int i = threadIdx.x; i < n_part; i += MEAN_BLOCK) s += part[i];
-  const double tot = block_sum_f64(s, sh);
+  const double tot = block_tree_sum<double, MEAN_BLOCK>(s, sh);
   if (threadIdx.x == 0) mean[0] = tot / (double)n;
 }
 
@@ -171,20 +160,6 @@ __global__ __launch_bounds__(SURF_BLOCK) void surf_area_kernel(const float* __re
   area[f] = 0.5f * sqrtf(nn);
 }
 
-// Inclusive scan of the workgroup's 256 lane values (Hillis-Steele in LDS); returns the lane's inclusive prefix.
-__device__ __forceinline__ double block_scan_f64(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int w = 1; w < SURF_BLOCK; w <<= 1) {
-    const double add = t >= w ? sh[t - w] : 0.0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  return sh[t];
-}
-
 // pass 1 (WRITE = false): tile[b] = sum of the tile's areas.  pass 3 (WRITE = true): cdf = tile scan + tile[b] (now the exclusive
 // prefix of the tile sums).  Both form the same sums in the same order: lane t owns faces [4 t, 4 t + 4) of the tile.
 template <bool WRITE>
@@ -197,7 +172,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void surf_scan_tile_kernel(SurfBuf s, i
     run += f0 + k < nf ? (double)s.area[f0 + k] : 0.0;
     v[k] = run;
   }
-  const double incl = block_scan_f64(run, sh);
+  const double incl = block_scan_incl<double, SURF_BLOCK>(run, sh);
   if (!WRITE) {
     if (threadIdx.x == SURF_BLOCK - 1) s.tile[blockIdx.x] = incl;
     return;
@@ -215,7 +190,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void surf_scan_tiles_kernel(double* __r
   double carry = 0.0;
   for (int i0 = 0; i0 < n_tiles; i0 += SURF_BLOCK) {
     const int i = i0 + threadIdx.x;
-    block_scan_f64(i < n_tiles ? tile[i] : 0.0, sh);
+    block_scan_incl<double, SURF_BLOCK>(i < n_tiles ? tile[i] : 0.0, sh);
     const double excl = threadIdx.x ? sh[threadIdx.x - 1] : 0.0;
     const double last = sh[SURF_BLOCK - 1];
     __syncthreads();                                     // sh is rewritten by the next round

@@ -26,13 +26,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blockops.hpp"
 #include "common.hpp"
 
 namespace dsdf {
 
 constexpr int SG_BLOCK = 256;
-constexpr int SG_SCAN_THREADS = 1024;
-constexpr int SG_SCAN_PER_THREAD = 8;
 constexpr int SG_MAX_CAPS = 6;
 
 struct SgGrid {
@@ -63,14 +62,6 @@ __device__ __forceinline__ int sg_cc(const SgGrid& g, int a, int m) {
   return x < g.n[a] - 1 ? x : g.n[a] - 1;
 }
 
-__device__ __forceinline__ void sg_point(int64_t p, const int* n, int* ijk) {
-  const int64_t syz = (int64_t)n[1] * n[2];
-  ijk[0] = (int)(p / syz);
-  const int r = (int)(p - (int64_t)ijk[0] * syz);
-  ijk[1] = r / n[2];
-  ijk[2] = r - ijk[1] * n[2];
-}
-
 // The blocks of axis a whose closed range holds coordinate x: lo, and lo + 1 as well when cnt == 2 (x is a shared coarse coordinate).
 __device__ __forceinline__ void sg_blocks_of(const SgGrid& g, int a, int x, int& lo, int& cnt) {
   int I = x / g.b;
@@ -89,20 +80,6 @@ __device__ __forceinline__ bool sg_in_new_block(const SgGrid& g, const uint8_t* 
       for (int dk = 0; dk < cnt[2]; ++dk)
         hit |= state[((int64_t)(lo[0] + di) * g.nb[1] + (lo[1] + dj)) * g.nb[2] + (lo[2] + dk)] == 1;
   return hit;
-}
-
-// Inclusive scan of one int per thread over the SG_BLOCK threads of a workgroup (Hillis-Steele in LDS, as mc_block_scan).
-__device__ __forceinline__ int sg_block_scan(int x, int* s) {
-  const int t = threadIdx.x;
-  s[t] = x;
-  __syncthreads();
-  for (int d = 1; d < SG_BLOCK; d <<= 1) {
-    const int y = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += y;
-    __syncthreads();
-  }
-  return s[t];
 }
 
 __global__ __launch_bounds__(SG_BLOCK) void sg_coarse_kernel(SgGrid g, int64_t* __restrict__ indices, uint8_t* __restrict__ have) {
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(SG_BLOCK) void sg_seed_kernel(SgGrid g, const float
     act = ((n_in != 0 && n_in != 8) || close) ? 1 : 0;
     state[blk] = (uint8_t)act;
   }
-  const int tot = sg_block_scan(act, s);
+  const int tot = block_scan_incl<int, SG_BLOCK>(act, s);
   if (threadIdx.x == SG_BLOCK - 1) part[blockIdx.x] = tot;
 }
 
@@ -193,23 +170,17 @@ __global__ __launch_bounds__(SG_BLOCK) void sg_grow_apply_kernel(int64_t nblk, u
     if (st == 1) state[blk] = 2;
     else if (st == 0 && pend[blk]) { state[blk] = 1; act = 1; }
   }
-  const int tot = sg_block_scan(act, s);
+  const int tot = block_scan_incl<int, SG_BLOCK>(act, s);
   if (threadIdx.x == SG_BLOCK - 1) part[blockIdx.x] = tot;
 }
 
 // One workgroup: *out = the sum of part[0 .. n) in 64 bits, a fixed order.
 __global__ __launch_bounds__(SG_BLOCK) void sg_sum_kernel(const int32_t* __restrict__ part, int64_t n, int64_t* __restrict__ out) {
   __shared__ int64_t s[SG_BLOCK];
-  const int t = threadIdx.x;
   int64_t x = 0;
-  for (int64_t q = t; q < n; q += SG_BLOCK) x += part[q];
-  s[t] = x;
-  __syncthreads();
-  for (int d = SG_BLOCK / 2; d > 0; d >>= 1) {
-    if (t < d) s[t] += s[t + d];
-    __syncthreads();
-  }
-  if (t == 0) *out = s[0];
+  for (int64_t q = threadIdx.x; q < n; q += SG_BLOCK) x += part[q];
+  const int64_t tot = block_tree_sum<int64_t, SG_BLOCK>(x, s);
+  if (threadIdx.x == 0) *out = tot;
 }
 
 __global__ __launch_bounds__(SG_BLOCK) void sg_points_count_kernel(SgGrid g, const uint8_t* __restrict__ state,
@@ -219,46 +190,11 @@ __global__ __launch_bounds__(SG_BLOCK) void sg_points_count_kernel(SgGrid g, con
   int f = 0;
   if (p < g.npts && !have[p]) {
     int ijk[3];
-    sg_point(p, g.n, ijk);
+    grid_ijk(p, g.n[1], g.n[2], ijk[0], ijk[1], ijk[2]);
     f = sg_in_new_block(g, state, ijk) ? 1 : 0;
   }
-  const int tot = sg_block_scan(f, s);
+  const int tot = block_scan_incl<int, SG_BLOCK>(f, s);
   if (threadIdx.x == SG_BLOCK - 1) part[blockIdx.x] = tot;
-}
-
-// One workgroup: the exclusive 64-bit scan of part[0 .. nb) into offs, the grand total into offs[nb] and *total (as mc_scan_kernel).
-__global__ __launch_bounds__(SG_SCAN_THREADS) void sg_scan_kernel(const int32_t* __restrict__ part, int64_t nb, int64_t* __restrict__ offs,
-                                                                  int64_t* __restrict__ total) {
-  __shared__ int64_t sv[SG_SCAN_THREADS];
-  const int t = threadIdx.x;
-  int64_t carry = 0;
-  for (int64_t base = 0; base < nb; base += (int64_t)SG_SCAN_THREADS * SG_SCAN_PER_THREAD) {
-    const int64_t b0 = base + (int64_t)t * SG_SCAN_PER_THREAD;
-    int64_t x = 0;
-    for (int q = 0; q < SG_SCAN_PER_THREAD; ++q)
-      if (b0 + q < nb) x += part[b0 + q];
-    sv[t] = x;
-    __syncthreads();
-    for (int d = 1; d < SG_SCAN_THREADS; d <<= 1) {
-      const int64_t y = t >= d ? sv[t - d] : 0;
-      __syncthreads();
-      sv[t] += y;
-      __syncthreads();
-    }
-    int64_t e = carry + sv[t] - x;
-    for (int q = 0; q < SG_SCAN_PER_THREAD; ++q) {
-      if (b0 + q < nb) {
-        offs[b0 + q] = e;
-        e += part[b0 + q];
-      }
-    }
-    carry += sv[SG_SCAN_THREADS - 1];
-    __syncthreads();     // every thread has read the last entry before the next chunk overwrites it
-  }
-  if (t == 0) {
-    offs[nb] = carry;
-    *total = carry;
-  }
 }
 
 // The count pass's flags again (state and have are unchanged in between), placed by scan + offset; nothing is written at or past n.
@@ -269,10 +205,10 @@ __global__ __launch_bounds__(SG_BLOCK) void sg_points_emit_kernel(SgGrid g, cons
   int f = 0;
   if (p < g.npts && !have[p]) {
     int ijk[3];
-    sg_point(p, g.n, ijk);
+    grid_ijk(p, g.n[1], g.n[2], ijk[0], ijk[1], ijk[2]);
     f = sg_in_new_block(g, state, ijk) ? 1 : 0;
   }
-  const int inc = sg_block_scan(f, s);
+  const int inc = block_scan_incl<int, SG_BLOCK>(f, s);
   if (!f) return;
   const int64_t at = offs[blockIdx.x] + inc - 1;
   if (at < n) {
@@ -287,7 +223,7 @@ __global__ __launch_bounds__(SG_BLOCK) void sg_coords_kernel(SgAxes g, const int
   const int64_t q = (int64_t)blockIdx.x * SG_BLOCK + threadIdx.x;
   if (q >= n) return;
   int ijk[3];
-  sg_point(indices[q], g.n, ijk);
+  grid_ijk(indices[q], g.n[1], g.n[2], ijk[0], ijk[1], ijk[2]);
   for (int a = 0; a < 3; ++a) xyz[q * 3 + a] = rn_add(rn_mul((float)ijk[a], g.vs[a]), g.org[a]);
 }
 
@@ -306,7 +242,7 @@ __global__ __launch_bounds__(SG_BLOCK) void sg_caps_kernel(SgCaps c, const int64
   const int64_t q = (int64_t)blockIdx.x * SG_BLOCK + threadIdx.x;
   if (q >= n) return;
   int ijk[3];
-  sg_point(indices[q], c.n, ijk);
+  grid_ijk(indices[q], c.n[1], c.n[2], ijk[0], ijk[1], ijk[2]);
   float xo[3];
   for (int a = 0; a < 3; ++a) xo[a] = rn_add(rn_mul((float)ijk[a], c.vs[a]), c.org[a]);
   float v = sdf[q];
@@ -332,7 +268,7 @@ __global__ __launch_bounds__(SG_BLOCK) void sg_fill_kernel(SgGrid g, const uint8
   const int64_t p = (int64_t)blockIdx.x * SG_BLOCK + threadIdx.x;
   if (p >= g.npts || have[p]) return;
   int ijk[3], lo[3], cnt;
-  sg_point(p, g.n, ijk);
+  grid_ijk(p, g.n[1], g.n[2], ijk[0], ijk[1], ijk[2]);
   for (int a = 0; a < 3; ++a) sg_blocks_of(g, a, ijk[a], lo[a], cnt);
   sdf[p] = sdf[((int64_t)(lo[0] * g.b) * g.n[1] + lo[1] * g.b) * g.n[2] + lo[2] * g.b];
 }

@@ -10,28 +10,27 @@
 // Passes (one thread per grid point, TET_BLOCK points per workgroup, linear order; the shape of mcubes.hpp):
 //   1. classify:  rec[p] = bit 0 inside, bits 1..7 crossing classes of p's edges; ne[p] / nb[p] = elements / boundary triangles of
 //                 the cell at p (0 off the cell range); per workgroup its three totals
-//   2. scan:      one workgroup turns the per-workgroup totals into 64-bit exclusive offsets (+ the three grand totals)
+//   2. scan:      one workgroup turns the per-workgroup totals into 64-bit exclusive offsets (+ the three grand totals):
+//                 blockops.hpp's offset_scan_kernel<3>
 //   3. vertices:  workgroup scan of popcount(rec) + offset -> vbase[p]; positions (and on request the (point, class) of every id)
 //   4. elements:  workgroup scan of ne | nb << 16 + offsets; the id of the grid vertex q is vbase[q], of edge vertex (q, c)
 //                 vbase[q] + popcount(rec[q] & ((1 << c) - 1)): no edge-id map, no atomics
-//   components:   min-label hooking with shortcutting over the 14-neighbour graph of the Kuhn edges (the shape of meshtopo.hpp's
-//                 mt_cc_*): the int32 atomicMin / atomicAdd there are the only atomics of this file and change the road, not the result
+//   components:   components.hpp's min-label hooking with shortcutting over the 14-neighbour graph of the Kuhn edges: its int32
+//                 atomicMin / atomicAdd are the only atomics this file uses and change the road, not the result
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blockops.hpp"
 #include "common.hpp"
+#include "components.hpp"
 #include "mcubes.hpp"
-#include "meshtopo.hpp"
 
 namespace dsdf {
 
-constexpr int TET_BLOCK = 256;           // = MC_BLOCK: mc_block_scan and mc_coords are shared
+constexpr int TET_BLOCK = 256;
 constexpr int TET_MAX_ELEMS = 18;        // elements of a cell (3 per Kuhn tetrahedron)
 constexpr int TET_MAX_BFACES = 36;       // boundary triangles of a cell (2 cut + 2 x 2 plane per Kuhn tetrahedron)
-constexpr int TET_CC_GROUP = 4;          // rounds enqueued between two reads of the change flags on the host
-static_assert(TET_BLOCK == MC_BLOCK, "the workgroup scan is mcubes.hpp's");
-static_assert(TET_CC_GROUP == MT_CC_GROUP, "the change flags are cleared by mt_cc_flags_kernel");
 static_assert(TET_BLOCK * TET_MAX_BFACES < (1 << 16) && TET_BLOCK * TET_MAX_ELEMS < (1 << 16), "two counts share one scanned int");
 
 struct TetWs {            // carved from the caller's workspace (tet_plan in dsdf_api.hip)
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(TET_BLOCK) void tet_classify_kernel(McGrid g, TetWs
   int nv = 0, ne = 0, nb = 0;
   if (p < g.npts) {
     int idx[3];
-    mc_coords(p, g, idx[0], idx[1], idx[2]);
+    grid_ijk(p, g.ny, g.nz, idx[0], idx[1], idx[2]);
     const int dims[3] = {g.nx, g.ny, g.nz};
     const int64_t syz = (int64_t)g.ny * g.nz;
     const bool h[3] = {idx[0] + 1 < g.nx, idx[1] + 1 < g.ny, idx[2] + 1 < g.nz};
@@ -118,53 +117,13 @@ __global__ __launch_bounds__(TET_BLOCK) void tet_classify_kernel(McGrid g, TetWs
     w.nb[p] = (uint8_t)nb;
     nv = __popc(rec);
   }
-  const int tv = mc_block_scan(nv, s);
+  const int tv = block_scan_incl<int, TET_BLOCK>(nv, s);
   __syncthreads();
-  const int tf = mc_block_scan(ne | (nb << 16), s);
+  const int tf = block_scan_incl<int, TET_BLOCK>(ne | (nb << 16), s);
   if (threadIdx.x == TET_BLOCK - 1) {
     w.bcount[0][blockIdx.x] = tv;
     w.bcount[1][blockIdx.x] = tf & 0xFFFF;
     w.bcount[2][blockIdx.x] = tf >> 16;
-  }
-}
-
-// One workgroup: exclusive 64-bit scans of the three per-workgroup counts (mc_scan_kernel's scheme, stream by stream); the grand
-// totals go to boff[s][nb] and totals[s].
-__global__ __launch_bounds__(MC_SCAN_THREADS) void tet_scan_kernel(TetWs w, int64_t* totals) {
-  __shared__ int64_t sh[MC_SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int64_t nb = w.nblocks;
-  for (int s = 0; s < 3; ++s) {
-    const int32_t* cnt = w.bcount[s];
-    int64_t* off = w.boff[s];
-    int64_t carry = 0;
-    for (int64_t base = 0; base < nb; base += (int64_t)MC_SCAN_THREADS * MC_SCAN_PER_THREAD) {
-      const int64_t b0 = base + (int64_t)t * MC_SCAN_PER_THREAD;
-      int64_t x = 0;
-      for (int q = 0; q < MC_SCAN_PER_THREAD; ++q)
-        if (b0 + q < nb) x += cnt[b0 + q];
-      sh[t] = x;
-      __syncthreads();
-      for (int d = 1; d < MC_SCAN_THREADS; d <<= 1) {
-        const int64_t y = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += y;
-        __syncthreads();
-      }
-      int64_t e = carry + sh[t] - x;                             // exclusive offset of element b0
-      for (int q = 0; q < MC_SCAN_PER_THREAD; ++q) {
-        if (b0 + q < nb) {
-          off[b0 + q] = e;
-          e += cnt[b0 + q];
-        }
-      }
-      carry += sh[MC_SCAN_THREADS - 1];
-      __syncthreads();     // every thread has read the last entry before the next chunk overwrites it
-    }
-    if (t == 0) {
-      off[nb] = carry;
-      totals[s] = carry;
-    }
   }
 }
 
@@ -173,13 +132,13 @@ __global__ __launch_bounds__(TET_BLOCK) void tet_vertex_kernel(McGrid g, TetWs w
   const int64_t p = (int64_t)blockIdx.x * TET_BLOCK + threadIdx.x;
   const uint32_t rec = p < g.npts ? w.rec[p] : 0u;
   const int n = __popc(rec);
-  const int inc = mc_block_scan(n, s);
+  const int inc = block_scan_incl<int, TET_BLOCK>(n, s);
   if (p >= g.npts) return;
   int64_t id = w.boff[0][blockIdx.x] + inc - n;
   w.vbase[p] = (int32_t)id;            // the host refuses totals above INT32_MAX before this launch
   if (!rec) return;
   int idx[3];
-  mc_coords(p, g, idx[0], idx[1], idx[2]);
+  grid_ijk(p, g.ny, g.nz, idx[0], idx[1], idx[2]);
   const int64_t syz = (int64_t)g.ny * g.nz;
   const float v0 = g.sdf[p];
   for (int c = 0; c < 8; ++c) {
@@ -301,14 +260,14 @@ __global__ __launch_bounds__(TET_BLOCK) void tet_element_kernel(McGrid g, TetWs 
   __shared__ int s[TET_BLOCK];
   const int64_t p = (int64_t)blockIdx.x * TET_BLOCK + threadIdx.x;
   const int ne = p < g.npts ? w.ne[p] : 0, nb = p < g.npts ? w.nb[p] : 0;
-  const int inc = mc_block_scan(ne | (nb << 16), s);
+  const int inc = block_scan_incl<int, TET_BLOCK>(ne | (nb << 16), s);
   if (p >= g.npts || (ne == 0 && nb == 0)) return;    // ne + nb > 0 only at the lower corner of a cell: p + d(7) is in the grid
   TetEmit E;
   E.tets = o.tets; E.bfaces = o.bfaces; E.kind = o.bface_kind; E.nt = o.nt; E.nb = o.nb;
   E.te = w.boff[1][blockIdx.x] + (inc & 0xFFFF) - ne;
   E.be = w.boff[2][blockIdx.x] + (inc >> 16) - nb;
   int idx[3];
-  mc_coords(p, g, idx[0], idx[1], idx[2]);
+  grid_ijk(p, g.ny, g.nz, idx[0], idx[1], idx[2]);
   const int dims[3] = {g.nx, g.ny, g.nz};
   const int64_t syz = (int64_t)g.ny * g.nz;
   int vb[8];
@@ -389,25 +348,16 @@ __global__ __launch_bounds__(TET_BLOCK) void tet_cc_init_kernel(McGrid g, int32_
   if (u < g.npts) f[u] = g.sdf[u] < g.level ? (int32_t)u : -1;
 }
 
-__global__ __launch_bounds__(TET_BLOCK) void tet_cc_grand_kernel(const int32_t* __restrict__ f, int64_t npts, int32_t* __restrict__ gf) {
-  const int64_t u = (int64_t)blockIdx.x * TET_BLOCK + threadIdx.x;
-  if (u >= npts) return;
-  const int fu = f[u];
-  gf[u] = fu < 0 ? -1 : f[mt_clampl(fu, npts)];
-}
-
-// mt_cc_hook_kernel over the grid: u's neighbours are u +- d(c), c = 1..7, inside the grid and inside the solid (gf >= 0).  f is
-// read plainly while other lanes lower it: a stale value is a larger one, still a point of the same component.  An inside point's f
-// never becomes negative: only values gf >= 0 are hooked in.
+// mt_cc_hook_kernel over the grid: u's neighbours are u +- d(c), c = 1..7, inside the grid and inside the solid (gf >= 0).
 __global__ __launch_bounds__(TET_BLOCK) void tet_cc_hook_kernel(McGrid g, int32_t* f, const int32_t* __restrict__ gf,
                                                                 int32_t* __restrict__ flag) {
   const int64_t u = (int64_t)blockIdx.x * TET_BLOCK + threadIdx.x;
   if (u >= g.npts) return;
   int best = gf[u];
   if (best < 0) return;
-  const int64_t fu = mt_clampl(f[u], g.npts);
+  const int64_t fu = clamp_index(f[u], g.npts);
   int idx[3];
-  mc_coords(u, g, idx[0], idx[1], idx[2]);
+  grid_ijk(u, g.ny, g.nz, idx[0], idx[1], idx[2]);
   const int64_t syz = (int64_t)g.ny * g.nz;
   bool changed = false;
   for (int c = 1; c < 8; ++c) {
@@ -417,22 +367,12 @@ __global__ __launch_bounds__(TET_BLOCK) void tet_cc_hook_kernel(McGrid g, int32_
       if (i < 0 || j < 0 || k < 0 || i >= g.nx || j >= g.ny || k >= g.nz) continue;
       const int gv = gf[u + sgn * tet_offset(c, syz, g.nz)];
       if (gv < 0) continue;
-      if (gv < f[fu]) changed |= atomicMin(&f[fu], gv) > gv;
+      changed |= cc_lower(f, fu, gv);
       best = gv < best ? gv : best;
     }
   }
-  if (best < f[u]) changed |= atomicMin(&f[u], best) > best;
+  changed |= cc_lower(f, u, best);
   if (changed) *flag = 1;
-}
-
-__global__ __launch_bounds__(TET_BLOCK) void tet_cc_zero_kernel(int32_t* __restrict__ size, int64_t npts) {
-  const int64_t u = (int64_t)blockIdx.x * TET_BLOCK + threadIdx.x;
-  if (u < npts) size[u] = 0;
-}
-
-__global__ __launch_bounds__(TET_BLOCK) void tet_cc_size_kernel(const int32_t* __restrict__ label, int64_t npts, int32_t* __restrict__ size) {
-  const int64_t u = (int64_t)blockIdx.x * TET_BLOCK + threadIdx.x;
-  if (u < npts && label[u] >= 0) atomicAdd(&size[mt_clampl(label[u], npts)], 1);
 }
 
 }  // namespace dsdf

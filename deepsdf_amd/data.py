@@ -124,7 +124,6 @@ class DeviceSampleCache:
         if self.device.type != "cuda":
             raise RuntimeError("DeviceSampleCache.sample_sequence runs on the GPU; there is no CPU path")
         from . import _lib
-        from .engine import _ptr, _stream
         scene_ids = torch.as_tensor(scene_ids, dtype=torch.int64)
         S = 2 * int(subsample / 2)
         self._check_ids(scene_ids, S)
@@ -135,9 +134,9 @@ class DeviceSampleCache:
         self._draws += int(n_draws)
 
         def launch():
-            _lib.check(_lib.lib().dsdf_sample_batch_seq(_ptr(self.data), self.G, _ptr(self.pos_start_d), _ptr(self.n_pos_d),
-                                                        _ptr(self.neg_start_d), _ptr(self.n_neg_d), _ptr(sid), B, int(subsample), key0,
-                                                        self.KEY_DRAW_MUL, _ptr(counter), _ptr(xyz_out), _ptr(sdf_out), _stream()))
+            _lib.check(_lib.lib().dsdf_sample_batch_seq(_lib.ptr(self.data), self.G, _lib.ptr(self.pos_start_d), _lib.ptr(self.n_pos_d),
+                                                        _lib.ptr(self.neg_start_d), _lib.ptr(self.n_neg_d), _lib.ptr(sid), B, int(subsample), key0,
+                                                        self.KEY_DRAW_MUL, _lib.ptr(counter), _lib.ptr(xyz_out), _lib.ptr(sdf_out), _lib.stream()))
         return launch
 
     def sample(self, scene_ids, subsample, generator=None, key=None, scene_ids_device=None):
@@ -147,7 +146,6 @@ class DeviceSampleCache:
         if self.device.type != "cuda":
             raise RuntimeError("DeviceSampleCache.sample runs on the GPU (libdsdf_hip.so dsdf_sample_batch); there is no CPU path")
         from . import _lib
-        from .engine import _ptr, _stream
         scene_ids = torch.as_tensor(scene_ids, dtype=torch.int64)
         S = 2 * int(subsample / 2)
         self._check_ids(scene_ids, S)
@@ -156,9 +154,9 @@ class DeviceSampleCache:
         xyz = torch.empty(B * S, self.G, dtype=torch.float32, device=self.device)
         sdf = torch.empty(B * S, dtype=torch.float32, device=self.device)
         key = self.draw_key(generator) if key is None else int(key) & ((1 << 64) - 1)
-        _lib.check(_lib.lib().dsdf_sample_batch(_ptr(self.data), self.G, _ptr(self.pos_start_d), _ptr(self.n_pos_d),
-                                                _ptr(self.neg_start_d), _ptr(self.n_neg_d), _ptr(sid), B, int(subsample), key,
-                                                _ptr(xyz), _ptr(sdf), _stream()))
+        _lib.check(_lib.lib().dsdf_sample_batch(_lib.ptr(self.data), self.G, _lib.ptr(self.pos_start_d), _lib.ptr(self.n_pos_d),
+                                                _lib.ptr(self.neg_start_d), _lib.ptr(self.n_neg_d), _lib.ptr(sid), B, int(subsample), key,
+                                                _lib.ptr(xyz), _lib.ptr(sdf), _lib.stream()))
         return xyz, sdf
 
 
@@ -223,7 +221,6 @@ class StagedSampleCache:
     def sample(self, scene_ids, subsample, generator=None, key=None, scene_ids_device=None):
         """As DeviceSampleCache.sample (scene_ids_device is accepted and ignored: the ids travel with the offsets)."""
         from . import _lib
-        from .engine import _ptr, _stream
         scene_ids = torch.as_tensor(scene_ids, dtype=torch.int64).cpu()
         S = 2 * int(subsample / 2)
         ids = scene_ids.tolist()
@@ -266,9 +263,9 @@ class StagedSampleCache:
         xyz = torch.empty(B * S, self.G, dtype=torch.float32, device=self.device)
         sdf = torch.empty(B * S, dtype=torch.float32, device=self.device)
         key = self.draw_key(generator) if key is None else int(key) & ((1 << 64) - 1)
-        _lib.check(_lib.lib().dsdf_sample_batch(_ptr(win), self.G, _ptr(self.pos_start_w[w]), _ptr(self.n_pos_d),
-                                                _ptr(self.neg_start_w[w]), _ptr(self.n_neg_d), _ptr(st_d[0]), B, int(subsample), key,
-                                                _ptr(xyz), _ptr(sdf), _stream()))
+        _lib.check(_lib.lib().dsdf_sample_batch(_lib.ptr(win), self.G, _lib.ptr(self.pos_start_w[w]), _lib.ptr(self.n_pos_d),
+                                                _lib.ptr(self.neg_start_w[w]), _lib.ptr(self.n_neg_d), _lib.ptr(st_d[0]), B, int(subsample), key,
+                                                _lib.ptr(xyz), _lib.ptr(sdf), _lib.stream()))
         fe = torch.cuda.Event()
         fe.record(compute)
         self.free[w] = fe

@@ -15,14 +15,6 @@ from . import _lib
 from .net import NetSpec, dropout_layer_key
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class Engine:
     def __init__(self, spec: NetSpec, device="cuda", params=None, grads=None):
         self.spec = spec
@@ -117,7 +109,7 @@ class Engine:
 
     # ---- weights -----------------------------------------------------------------------------------------
     def materialize(self):
-        _lib.check(self.lib.dsdf_materialize_weights(C.byref(self.cnet), _ptr(self.params), _ptr(self.packed), _stream()))
+        _lib.check(self.lib.dsdf_materialize_weights(C.byref(self.cnet), _lib.ptr(self.params), _lib.ptr(self.packed), _lib.stream()))
         self.weights_dirty = False
 
     def _fresh_weights(self):
@@ -141,9 +133,9 @@ class Engine:
         for s in range(0, n, max_chunk):
             e = min(n, s + max_chunk)
             xs = x[s:e]
-            _lib.check(self.lib.dsdf_decode(C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(xs),
-                                            xs.stride(0), e - s, C.c_void_p(out.data_ptr() + 4 * s), _ptr(ws),
-                                            ws.numel(), _stream()))
+            _lib.check(self.lib.dsdf_decode(C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(xs),
+                                            xs.stride(0), e - s, C.c_void_p(out.data_ptr() + 4 * s), _lib.ptr(ws),
+                                            ws.numel(), _lib.stream()))
         return out.view(n, 1)
 
     def decode_latent_supported(self):
@@ -168,9 +160,9 @@ class Engine:
         ws = self._workspace(max(b.value, 16384))
         for s in range(0, n, max_chunk):
             e = min(n, s + max_chunk)
-            _lib.check(self.lib.dsdf_decode_latent(C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(z),
+            _lib.check(self.lib.dsdf_decode_latent(C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(z),
                                                    C.c_void_p(x.data_ptr() + 4 * s * x.shape[1]), e - s,
-                                                   C.c_void_p(out.data_ptr() + 4 * s), _ptr(ws), ws.numel(), _stream()))
+                                                   C.c_void_p(out.data_ptr() + 4 * s), _lib.ptr(ws), ws.numel(), _lib.stream()))
         return out.view(n, 1)
 
     # ---- module path (autograd) -----------------------------------------------------------------------------
@@ -181,18 +173,18 @@ class Engine:
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         keys = (C.c_uint32 * _lib.MAX_LAYERS)(*[dropout_layer_key(seed, step, l) for l in range(_lib.MAX_LAYERS)])
         self._module_keys = keys          # module_backward of a latent_dropout net needs the same mask
-        _lib.check(self.lib.dsdf_module_forward(C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(x),
-                                                x.stride(0), n, int(training), keys, _ptr(out), _ptr(ws), ws.numel(),
-                                                _stream()))
+        _lib.check(self.lib.dsdf_module_forward(C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(x),
+                                                x.stride(0), n, int(training), keys, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                _lib.stream()))
         return out.view(n, 1)
 
     def module_backward(self, d_sdf, n, training, need_input_grad, accumulate):
         ws = self.train_workspace(n, 0)
         d_in = torch.empty(n, self.spec.in_dim[0], dtype=torch.float32, device=self.device) if need_input_grad else None
-        _lib.check(self.lib.dsdf_module_backward(C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(d_sdf), n,
-                                                 int(training), getattr(self, "_module_keys", None), _ptr(self.grads),
-                                                 int(accumulate), _ptr(d_in),
-                                                 self.spec.in_dim[0], _ptr(ws), ws.numel(), _stream()))
+        _lib.check(self.lib.dsdf_module_backward(C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(d_sdf), n,
+                                                 int(training), getattr(self, "_module_keys", None), _lib.ptr(self.grads),
+                                                 int(accumulate), _lib.ptr(d_in),
+                                                 self.spec.in_dim[0], _lib.ptr(ws), ws.numel(), _lib.stream()))
         return d_in
 
     def module_input_grad(self, d_sdf, n):
@@ -203,8 +195,8 @@ class Engine:
             raise ValueError(f"expected d_sdf with {n} values, got {d.numel()}")
         ws = self.train_workspace(n, 0)
         d_in = torch.empty(n, self.spec.in_dim[0], dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dsdf_module_input_grad(C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(d), n, _ptr(d_in),
-                                                   self.spec.in_dim[0], _ptr(ws), ws.numel(), _stream()))
+        _lib.check(self.lib.dsdf_module_input_grad(C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(d), n, _lib.ptr(d_in),
+                                                   self.spec.in_dim[0], _lib.ptr(ws), ws.numel(), _lib.stream()))
         return d_in
 
     def module_jvp(self, tangent, n, training):
@@ -216,9 +208,9 @@ class Engine:
             t = t.contiguous()
         ws = self.train_workspace(n, 0)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.dsdf_module_jvp(C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(t), t.stride(0), n,
-                                            int(training), getattr(self, "_module_keys", None), _ptr(out), _ptr(ws), ws.numel(),
-                                            _stream()))
+        _lib.check(self.lib.dsdf_module_jvp(C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(t), t.stride(0), n,
+                                            int(training), getattr(self, "_module_keys", None), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                            _lib.stream()))
         return out.view(n, 1)
 
     # ---- training --------------------------------------------------------------------------------------------
@@ -245,9 +237,9 @@ class Engine:
         for l in range(_lib.MAX_LAYERS):
             cfg.dropout_key[l] = dropout_layer_key(seed, st, l)
         _lib.check(self.lib.dsdf_train_forward_backward(
-            C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(latents), latents.shape[0], C.byref(b),
-            C.byref(cfg), _ptr(self.grads), _ptr(dlat), _ptr(self.loss if loss_out is None else loss_out), _ptr(sdf_out),
-            int(accumulate), _ptr(ws), ws.numel(), _stream()))
+            C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(latents), latents.shape[0], C.byref(b),
+            C.byref(cfg), _lib.ptr(self.grads), _lib.ptr(dlat), _lib.ptr(self.loss if loss_out is None else loss_out), _lib.ptr(sdf_out),
+            int(accumulate), _lib.ptr(ws), ws.numel(), _lib.stream()))
 
     def dw_phase_supported(self):
         """Whether this net's backward can run in phases (dsdf_dw_phase_supported: the library's own condition)."""
@@ -286,34 +278,34 @@ class Engine:
             cfg.dropout_key[l] = dropout_layer_key(seed, self.step, l)
         ad = _lib.DsdfAdamCfg(self.step + 1, float(lr_decoder), float(lr_latent), betas[0], betas[1], eps, None)
         _lib.check(self.lib.dsdf_train_step(
-            C.byref(self.cnet), _ptr(self.packed), _ptr(self.params), _ptr(self.grads), _ptr(self.exp_avg),
-            _ptr(self.exp_avg_sq), _ptr(latents), latents.shape[0], _ptr(dlat), _ptr(lat_m), _ptr(lat_v), C.byref(b),
-            C.byref(cfg), C.byref(ad), _ptr(self.loss if loss_out is None else loss_out), None, _ptr(ws), ws.numel(), _stream()))
+            C.byref(self.cnet), _lib.ptr(self.packed), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
+            _lib.ptr(self.exp_avg_sq), _lib.ptr(latents), latents.shape[0], _lib.ptr(dlat), _lib.ptr(lat_m), _lib.ptr(lat_v), C.byref(b),
+            C.byref(cfg), C.byref(ad), _lib.ptr(self.loss if loss_out is None else loss_out), None, _lib.ptr(ws), ws.numel(), _lib.stream()))
         self.step += 1                # only once the call was accepted: a rejected step must not advance Adam's bias correction
         self.weights_dirty = False
 
     def grad_norm(self, max_norm):
         """clip_grad_norm_ coefficient into self.clip[1] (device); returns the device tensor [norm, coef]."""
         ws = self._workspace(1 << 16)
-        _lib.check(self.lib.dsdf_grad_norm(_ptr(self.grads), self.spec.n_params, float(max_norm), _ptr(self.clip),
-                                           C.c_void_p(self.clip.data_ptr() + 4), _ptr(ws), ws.numel(), _stream()))
+        _lib.check(self.lib.dsdf_grad_norm(_lib.ptr(self.grads), self.spec.n_params, float(max_norm), _lib.ptr(self.clip),
+                                           C.c_void_p(self.clip.data_ptr() + 4), _lib.ptr(ws), ws.numel(), _lib.stream()))
         return self.clip
 
     def adam_latents(self, latents, dlat, lat_m, lat_v, lr_latent, *, betas=(0.9, 0.999), eps=1e-8):
         """Adam on the latent table alone, as step `self.step + 1` (the data-parallel step runs it under the decoder
         gradient's all-reduce; the following adam_step(None, ...) advances the shared step counter)."""
         cfg = _lib.DsdfAdamCfg(self.step + 1, 0.0, float(lr_latent), betas[0], betas[1], eps, None)
-        _lib.check(self.lib.dsdf_adam_latent_only(_ptr(latents), _ptr(dlat), _ptr(lat_m), _ptr(lat_v), latents.numel(),
-                                                  C.byref(cfg), _stream()))
+        _lib.check(self.lib.dsdf_adam_latent_only(_lib.ptr(latents), _lib.ptr(dlat), _lib.ptr(lat_m), _lib.ptr(lat_v), latents.numel(),
+                                                  C.byref(cfg), _lib.stream()))
 
     def adam_step(self, latents, dlat, lat_m, lat_v, lr_decoder, lr_latent, *, clip=False, betas=(0.9, 0.999), eps=1e-8):
         """Adam on the decoder arena (+ the latent table unless `latents` is None) and weight re-materialisation."""
         cfg = _lib.DsdfAdamCfg(self.step + 1, float(lr_decoder), float(lr_latent), betas[0], betas[1], eps,
                                (self.clip.data_ptr() + 4) if clip else None)
         nlat = latents.numel() if latents is not None else 0
-        _lib.check(self.lib.dsdf_adam_step(C.byref(self.cnet), _ptr(self.params), _ptr(self.grads), _ptr(self.exp_avg),
-                                           _ptr(self.exp_avg_sq), _ptr(latents), _ptr(dlat), _ptr(lat_m), _ptr(lat_v),
-                                           nlat, C.byref(cfg), _ptr(self.packed), _stream()))
+        _lib.check(self.lib.dsdf_adam_step(C.byref(self.cnet), _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
+                                           _lib.ptr(self.exp_avg_sq), _lib.ptr(latents), _lib.ptr(dlat), _lib.ptr(lat_m), _lib.ptr(lat_v),
+                                           nlat, C.byref(cfg), _lib.ptr(self.packed), _lib.stream()))
         self.step += 1
         self.weights_dirty = False
 

@@ -40,21 +40,6 @@ logger = logging.getLogger(__name__)
 INT32_MAX = 2 ** 31 - 1
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _triple(x, what):
-    t = [float(v) for v in (x if isinstance(x, (list, tuple, np.ndarray, torch.Tensor)) else [x] * 3)]
-    if len(t) != 3:
-        raise ValueError(f"{what} needs 3 values, got {len(t)}")
-    return t
-
-
 # ---- marching cubes ---------------------------------------------------------------------------------------------------
 def marching_cubes(sdf_grid, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), return_edges=False):
     """Surface {sdf == level} of a dense device grid sdf_grid [nx, ny, nz] (z fastest; 2 <= n <= 1024 per axis).
@@ -70,25 +55,25 @@ def marching_cubes(sdf_grid, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.
     g = g.to(torch.float32).contiguous()
     nx, ny, nz = g.shape
     lib = _lib.lib()
-    sp, org = (C.c_float * 3)(*_triple(spacing, "spacing")), (C.c_float * 3)(*_triple(origin, "origin"))
+    sp, org = (C.c_float * 3)(*_lib.triple(spacing, "spacing")), (C.c_float * 3)(*_lib.triple(origin, "origin"))
     b = C.c_size_t()
     _lib.check(lib.dsdf_mc_workspace_bytes(nx, ny, nz, C.byref(b)))
     with torch.cuda.device(g.device):
         ws = torch.empty(b.value, dtype=torch.uint8, device=g.device)
         totals = torch.empty(2, dtype=torch.int64, device=g.device)
-        _lib.check(lib.dsdf_mc_count(_ptr(g), nx, ny, nz, float(level), _ptr(totals), _ptr(ws), ws.numel(), _stream()))
+        _lib.check(lib.dsdf_mc_count(_lib.ptr(g), nx, ny, nz, float(level), _lib.ptr(totals), _lib.ptr(ws), ws.numel(), _lib.stream()))
         nv, nf = totals.tolist()                            # the one host sync of a mesh
         if nv > INT32_MAX or nf > INT32_MAX:                # the library refuses before writing anything: raise its error
-            _lib.check(lib.dsdf_mc_emit(_ptr(g), nx, ny, nz, float(level), sp, org, nv, nf, None, None, _ptr(ws), ws.numel(),
-                                        _stream()))
+            _lib.check(lib.dsdf_mc_emit(_lib.ptr(g), nx, ny, nz, float(level), sp, org, nv, nf, None, None, _lib.ptr(ws), ws.numel(),
+                                        _lib.stream()))
         verts = torch.empty(nv, 3, dtype=torch.float32, device=g.device)
         faces = torch.empty(nf, 3, dtype=torch.int32, device=g.device)
-        _lib.check(lib.dsdf_mc_emit(_ptr(g), nx, ny, nz, float(level), sp, org, nv, nf, _ptr(verts), _ptr(faces), _ptr(ws),
-                                    ws.numel(), _stream()))
+        _lib.check(lib.dsdf_mc_emit(_lib.ptr(g), nx, ny, nz, float(level), sp, org, nv, nf, _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(ws),
+                                    ws.numel(), _lib.stream()))
         if return_edges:
             edge_point = torch.empty(nv, dtype=torch.int64, device=g.device)
             edge_axis = torch.empty(nv, dtype=torch.int32, device=g.device)
-            _lib.check(lib.dsdf_mc_edges(nx, ny, nz, nv, _ptr(edge_point), _ptr(edge_axis), _ptr(ws), ws.numel(), _stream()))
+            _lib.check(lib.dsdf_mc_edges(nx, ny, nz, nv, _lib.ptr(edge_point), _lib.ptr(edge_axis), _lib.ptr(ws), ws.numel(), _lib.stream()))
             return verts, faces, edge_point, edge_axis
     return verts, faces
 
@@ -179,7 +164,7 @@ def _check_sparse(block, lipschitz):
 def sparse_threshold(block, spacing, lipschitz):
     """The seeding distance: lipschitz x half the diagonal of a full block, spacing[a] the grid spacing of axis a in the coordinates
     the decoder sees; computed in double and rounded to fp32 once."""
-    return float(np.float32(float(lipschitz) * 0.5 * math.sqrt(sum((block * float(x)) ** 2 for x in _triple(spacing, "spacing")))))
+    return float(np.float32(float(lipschitz) * 0.5 * math.sqrt(sum((block * float(x)) ** 2 for x in _lib.triple(spacing, "spacing")))))
 
 
 _SPARSE = [(None, 1.0)]
@@ -213,10 +198,10 @@ def grid_coords_at(dims, voxel_size, origin, indices):
     each rounded on its own -- bit for bit grid_coords at those indices (dsdf_sg_coords)."""
     dims = _int_triple(dims, "dims")
     idx = indices.contiguous()
-    vs, org = (C.c_float * 3)(*_triple(voxel_size, "voxel_size")), (C.c_float * 3)(*_triple(origin, "origin"))
+    vs, org = (C.c_float * 3)(*_lib.triple(voxel_size, "voxel_size")), (C.c_float * 3)(*_lib.triple(origin, "origin"))
     with torch.cuda.device(idx.device):
         xyz = torch.empty(idx.numel(), 3, dtype=torch.float32, device=idx.device)
-        _lib.check(_lib.lib().dsdf_sg_coords(*dims, vs, org, _ptr(idx), idx.numel(), _ptr(xyz), _stream()))
+        _lib.check(_lib.lib().dsdf_sg_coords(*dims, vs, org, _lib.ptr(idx), idx.numel(), _lib.ptr(xyz), _lib.stream()))
     return xyz
 
 
@@ -229,7 +214,7 @@ def ms_caps_at(values, N, indices, cap_border_dict=None):
     if values.dtype != torch.float32 or not values.is_contiguous() or values.numel() != idx.numel() or values.device.type != "cuda":
         raise ValueError("ms_caps_at expects a contiguous fp32 device tensor with one value per index")
     with torch.cuda.device(values.device):
-        _lib.check(_lib.lib().dsdf_sg_caps_at(C.byref(g), _ptr(idx), idx.numel(), recs, n, _ptr(values), _stream()))
+        _lib.check(_lib.lib().dsdf_sg_caps_at(C.byref(g), _lib.ptr(idx), idx.numel(), recs, n, _lib.ptr(values), _lib.stream()))
     return values
 
 
@@ -287,7 +272,7 @@ def follow_surface(dims, block, thr, level, values_at, caps_at=None, *, device=N
         capped = torch.empty(npts, dtype=torch.float32, device=device) if caps_at is not None else None
         seen = grid if capped is None else capped           # the grid that is meshed decides the states
         at = (*dims, int(block))
-        wsa = (_ptr(ws), ws.numel(), _stream())
+        wsa = (_lib.ptr(ws), ws.numel(), _lib.stream())
 
         def step(name, indices=None):
             if on_step is not None:
@@ -297,19 +282,19 @@ def follow_surface(dims, block, thr, level, values_at, caps_at=None, *, device=N
             vals = values_at(idx).to(torch.float32).reshape(-1).contiguous()
             if vals.numel() != idx.numel():
                 raise ValueError(f"values_at returned {vals.numel()} values for {idx.numel()} indices")
-            _lib.check(lib.dsdf_sg_scatter(_ptr(idx), idx.numel(), _ptr(vals), _ptr(grid), npts, _stream()))
+            _lib.check(lib.dsdf_sg_scatter(_lib.ptr(idx), idx.numel(), _lib.ptr(vals), _lib.ptr(grid), npts, _lib.stream()))
             if capped is not None:
                 cv = caps_at(idx, vals).to(torch.float32).reshape(-1).contiguous()
-                _lib.check(lib.dsdf_sg_scatter(_ptr(idx), idx.numel(), _ptr(cv), _ptr(capped), npts, _stream()))
+                _lib.check(lib.dsdf_sg_scatter(_lib.ptr(idx), idx.numel(), _lib.ptr(cv), _lib.ptr(capped), npts, _lib.stream()))
 
         step("start")
         idx = torch.empty(plan.n_coarse, dtype=torch.int64, device=device)
-        _lib.check(lib.dsdf_sg_coarse(*at, _ptr(idx), *wsa))
+        _lib.check(lib.dsdf_sg_coarse(*at, _lib.ptr(idx), *wsa))
         step("coarse", idx)
         decode_into(idx)
         step("coarse_decode")
         decoded = plan.n_coarse
-        _lib.check(lib.dsdf_sg_seed(_ptr(seen), *at, level, thr, n_new, *wsa))
+        _lib.check(lib.dsdf_sg_seed(_lib.ptr(seen), *at, level, thr, n_new, *wsa))
         _lib.check(lib.dsdf_sg_points_count(*at, n_pts, *wsa))
         step("seed")
         new, pts = counts.tolist()                          # the one stream wait of a round
@@ -319,20 +304,20 @@ def follow_surface(dims, block, thr, level, values_at, caps_at=None, *, device=N
             rounds += 1
             active += new
             idx = torch.empty(pts, dtype=torch.int64, device=device)
-            _lib.check(lib.dsdf_sg_points_emit(*at, pts, _ptr(idx), *wsa))
+            _lib.check(lib.dsdf_sg_points_emit(*at, pts, _lib.ptr(idx), *wsa))
             step("emit", idx)
             if pts > 0:
                 decode_into(idx)
                 decoded += pts
             step("decode")
-            _lib.check(lib.dsdf_sg_grow(_ptr(seen), *at, level, n_new, *wsa))
+            _lib.check(lib.dsdf_sg_grow(_lib.ptr(seen), *at, level, n_new, *wsa))
             _lib.check(lib.dsdf_sg_points_count(*at, n_pts, *wsa))
             step("grow")
             new, pts = counts.tolist()
             step("wait")
-        _lib.check(lib.dsdf_sg_fill(_ptr(grid), *at, *wsa))
+        _lib.check(lib.dsdf_sg_fill(_lib.ptr(grid), *at, *wsa))
         if capped is not None:
-            _lib.check(lib.dsdf_sg_fill(_ptr(capped), *at, *wsa))
+            _lib.check(lib.dsdf_sg_fill(_lib.ptr(capped), *at, *wsa))
         step("fill")
     stats = dict(blocks=int(plan.n_blocks), seeds=seeds, active=active, rounds=rounds, points=decoded, total=int(npts))
     return grid.view(*dims), None if capped is None else capped.view(*dims), stats
@@ -434,7 +419,7 @@ def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_s
     lo, hi = (float(x) for x in torch.aminmax(g.float()))
     if not lo <= 0.0 <= hi:
         raise ValueError("Surface level must be within volume data range.")
-    verts, faces = marching_cubes(g, 0.0, _triple(voxel_size, "voxel_size"), _triple(voxel_grid_origin, "voxel_grid_origin"))
+    verts, faces = marching_cubes(g, 0.0, _lib.triple(voxel_size, "voxel_size"), _lib.triple(voxel_grid_origin, "voxel_grid_origin"))
     if scale is not None:
         verts = verts / torch.as_tensor(scale, dtype=torch.float32, device=verts.device)
     if offset is not None:
@@ -509,7 +494,7 @@ def ms_grid_rows(field, tiling, N, start, end, device=None):
     with torch.cuda.device(device):
         s, _keep = field.c_spline(device)
         rows = torch.empty(max(end - start, 0), s.L + 3, dtype=torch.float32, device=device)
-        _lib.check(_lib.lib().dsdf_ms_rows(C.byref(s), C.byref(g), start, end, None, 1, 1, _ptr(rows), _stream()))
+        _lib.check(_lib.lib().dsdf_ms_rows(C.byref(s), C.byref(g), start, end, None, 1, 1, _lib.ptr(rows), _lib.stream()))
     return rows
 
 
@@ -526,8 +511,8 @@ def ms_point_rows(field, tiling, points, inside_test=False, with_xyz=True):
         s, _keep = field.c_spline(pts.device)
         rows = torch.empty(pts.shape[0], s.L + (3 if with_xyz else 0), dtype=torch.float32, device=pts.device)
         if pts.shape[0] > 0:
-            _lib.check(_lib.lib().dsdf_ms_rows(C.byref(s), C.byref(g), 0, pts.shape[0], _ptr(pts), int(bool(inside_test)),
-                                               int(bool(with_xyz)), _ptr(rows), _stream()))
+            _lib.check(_lib.lib().dsdf_ms_rows(C.byref(s), C.byref(g), 0, pts.shape[0], _lib.ptr(pts), int(bool(inside_test)),
+                                               int(bool(with_xyz)), _lib.ptr(rows), _lib.stream()))
     return rows
 
 
@@ -548,8 +533,8 @@ def ms_rows_at(field, tiling, N, indices):
         weights = torch.empty(n, _lib.MS_WEIGHTS, dtype=torch.float32, device=idx.device)
         base = torch.empty(n, dtype=torch.int32, device=idx.device)
         if n > 0:
-            _lib.check(_lib.lib().dsdf_ms_rows_at(C.byref(s), C.byref(g), _ptr(idx), n, _ptr(rows), _ptr(weights), _ptr(base),
-                                                  _stream()))
+            _lib.check(_lib.lib().dsdf_ms_rows_at(C.byref(s), C.byref(g), _lib.ptr(idx), n, _lib.ptr(rows), _lib.ptr(weights), _lib.ptr(base),
+                                                  _lib.stream()))
     return rows, weights, base
 
 
@@ -560,7 +545,7 @@ def ms_apply_caps(sdf, N, start, end, cap_border_dict=None):
     if sdf.dtype != torch.float32 or not sdf.is_contiguous() or sdf.numel() != end - start or sdf.device.type != "cuda":
         raise ValueError("ms_apply_caps expects a contiguous fp32 device tensor of end - start values")
     with torch.cuda.device(sdf.device):
-        _lib.check(_lib.lib().dsdf_ms_caps(C.byref(g), start, end, recs, n, _ptr(sdf), _stream()))
+        _lib.check(_lib.lib().dsdf_ms_caps(C.byref(g), start, end, recs, n, _lib.ptr(sdf), _lib.stream()))
     return sdf
 
 
@@ -655,11 +640,11 @@ def microstructure_sdf_grid(tiling, decoder, field, N, max_batch=32 ** 3, cap_bo
         for b in range(0, n, max_batch):
             e = min(n, b + max_batch)
             r = rows[:e - b]
-            _lib.check(lib.dsdf_ms_rows(C.byref(s), C.byref(g), b, e, None, 1, 1, _ptr(r), _stream()))
+            _lib.check(lib.dsdf_ms_rows(C.byref(s), C.byref(g), b, e, None, 1, 1, _lib.ptr(r), _lib.stream()))
             y = eng.decode(r) if hip else dec(r)
             out[b:e] = y.reshape(-1)
             if apply_caps:
-                _lib.check(lib.dsdf_ms_caps(C.byref(g), b, e, recs, n_caps, C.c_void_p(out.data_ptr() + 4 * b), _stream()))
+                _lib.check(lib.dsdf_ms_caps(C.byref(g), b, e, recs, n_caps, C.c_void_p(out.data_ptr() + 4 * b), _lib.stream()))
     return out.view(*dims)
 
 
@@ -765,7 +750,7 @@ class MicrostructureMeshDiff:
             jac = torch.empty(shape, dtype=torch.float32, device=self.device)
             axis = torch.empty(V, dtype=torch.int32, device=self.device)
             m, b = self._structs()
-            _lib.check(_lib.lib().dsdf_msd_jacobian(C.byref(m), C.byref(b), int(bool(dense)), _ptr(jac), _ptr(axis), _stream()))
+            _lib.check(_lib.lib().dsdf_msd_jacobian(C.byref(m), C.byref(b), int(bool(dense)), _lib.ptr(jac), _lib.ptr(axis), _lib.stream()))
         return jac if dense else (jac, axis)
 
     def vjp_plan(self):
@@ -786,7 +771,7 @@ class MicrostructureMeshDiff:
             ws = torch.empty(max(self.vjp_plan()[0], 256), dtype=torch.uint8, device=self.device)
             out = torch.empty(self.n_control_points, self.latent_size, dtype=torch.float32, device=self.device)
             m, b = self._structs()
-            _lib.check(lib.dsdf_msd_vjp(C.byref(m), C.byref(b), _ptr(gv), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+            _lib.check(lib.dsdf_msd_vjp(C.byref(m), C.byref(b), _lib.ptr(gv), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream()))
         return out
 
     def jvp(self, d_cp):
@@ -797,7 +782,7 @@ class MicrostructureMeshDiff:
         with torch.cuda.device(self.device):
             out = torch.empty(self.verts.shape[0], 3, dtype=torch.float32, device=self.device)
             m, b = self._structs()
-            _lib.check(_lib.lib().dsdf_msd_jvp(C.byref(m), C.byref(b), _ptr(d), _ptr(out), _stream()))
+            _lib.check(_lib.lib().dsdf_msd_jvp(C.byref(m), C.byref(b), _lib.ptr(d), _lib.ptr(out), _lib.stream()))
         return out
 
 

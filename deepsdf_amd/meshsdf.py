@@ -25,14 +25,6 @@ from . import _lib
 INT32_MAX = 2 ** 31 - 1
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 # ---- readers ----------------------------------------------------------------------------------------------------------------
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
               "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
@@ -272,8 +264,8 @@ class TriangleMesh:
         _lib.check(lib.dsdf_msdf_plan(self.n_faces, 0, C.byref(tb), None, None))
         with torch.cuda.device(device):
             self.tri = torch.empty(tb.value, dtype=torch.uint8, device=device)
-            _lib.check(lib.dsdf_msdf_prepare(_ptr(self.V), self.V.shape[0], _ptr(self.F), self.n_faces, _ptr(self.tri),
-                                             self.tri.numel(), _stream()))
+            _lib.check(lib.dsdf_msdf_prepare(_lib.ptr(self.V), self.V.shape[0], _lib.ptr(self.F), self.n_faces, _lib.ptr(self.tri),
+                                             self.tri.numel(), _lib.stream()))
         self._surf = None              # (buffer, total area, area offset): dsdf_surf_prepare, on first use
 
     @property
@@ -310,8 +302,8 @@ class TriangleMesh:
                 wb, _ = self.plan(nq)
                 ws = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.device)
                 _lib.check(_lib.lib().dsdf_msdf_query(
-                    _ptr(self.tri), self.n_faces, _ptr(Q), nq, _ptr(out.get("sdf")), _ptr(out.get("d2")), _ptr(out.get("face")),
-                    _ptr(out.get("closest")), _ptr(out.get("w")), int(bool(flip_sign)), _ptr(ws), ws.numel(), _stream()))
+                    _lib.ptr(self.tri), self.n_faces, _lib.ptr(Q), nq, _lib.ptr(out.get("sdf")), _lib.ptr(out.get("d2")), _lib.ptr(out.get("face")),
+                    _lib.ptr(out.get("closest")), _lib.ptr(out.get("w")), int(bool(flip_sign)), _lib.ptr(ws), ws.numel(), _lib.stream()))
         if numpy_out:
             return {k: v.cpu().numpy() for k, v in out.items()}
         return {k: v.to(out_dev) for k, v in out.items()}
@@ -337,8 +329,8 @@ class TriangleMesh:
             _lib.check(lib.dsdf_surf_plan(self.n_faces, C.byref(sb), C.byref(ao), None))
             with torch.cuda.device(self.device):
                 buf = torch.empty(sb.value, dtype=torch.uint8, device=self.device)
-                rc = lib.dsdf_surf_prepare(_ptr(self.V), self.V.shape[0], _ptr(self.F), self.n_faces, _ptr(buf), buf.numel(),
-                                           C.byref(total), _stream())
+                rc = lib.dsdf_surf_prepare(_lib.ptr(self.V), self.V.shape[0], _lib.ptr(self.F), self.n_faces, _lib.ptr(buf), buf.numel(),
+                                           C.byref(total), _lib.stream())
             if rc != 0 and total.value == 0.0:
                 raise ValueError("the mesh has no surface area: nothing to sample")
             _lib.check(rc)
@@ -370,8 +362,8 @@ class TriangleMesh:
             pts = torch.empty(count, 3, dtype=torch.float32, device=self.device)
             face = torch.empty(count, dtype=torch.int32, device=self.device)
             bary = torch.empty(count, 2, dtype=torch.float32, device=self.device) if return_bary else None
-            _lib.check(_lib.lib().dsdf_surf_sample(_ptr(self.V), self.V.shape[0], _ptr(self.F), self.n_faces, _ptr(buf), buf.numel(),
-                                                   count, offset, seed, float(std), _ptr(pts), _ptr(face), _ptr(bary), _stream()))
+            _lib.check(_lib.lib().dsdf_surf_sample(_lib.ptr(self.V), self.V.shape[0], _lib.ptr(self.F), self.n_faces, _lib.ptr(buf), buf.numel(),
+                                                   count, offset, seed, float(std), _lib.ptr(pts), _lib.ptr(face), _lib.ptr(bary), _lib.stream()))
         return (pts, face, bary) if return_bary else (pts, face)
 
 

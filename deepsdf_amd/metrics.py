@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .meshsdf import INT32_MAX, TriangleMesh, _as_host_or_device, _mesh_device, _ptr, _stream
+from .meshsdf import INT32_MAX, TriangleMesh, _as_host_or_device, _mesh_device
 
 
 def _device(*xs):
@@ -41,7 +41,7 @@ def _nn(Q, R, want_d2=True, want_idx=True):
             wb = C.c_size_t()
             _lib.check(lib.dsdf_nn_plan(nq, nr, C.byref(wb), None))
             ws = torch.empty(wb.value, dtype=torch.uint8, device=Q.device) if wb.value else None
-            _lib.check(lib.dsdf_nn_query(_ptr(Q), nq, _ptr(R), nr, _ptr(d2), _ptr(idx), _ptr(ws), wb.value, _stream()))
+            _lib.check(lib.dsdf_nn_query(_lib.ptr(Q), nq, _lib.ptr(R), nr, _lib.ptr(d2), _lib.ptr(idx), _lib.ptr(ws), wb.value, _lib.stream()))
     return d2, idx
 
 
@@ -74,7 +74,7 @@ def mean_f64(x):
     with torch.cuda.device(x.device):
         out = torch.empty((), dtype=torch.float64, device=x.device)
         ws = torch.empty(_lib.MEAN_WS_BYTES, dtype=torch.uint8, device=x.device)
-        _lib.check(_lib.lib().dsdf_mean_f64(_ptr(x), x.numel(), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+        _lib.check(_lib.lib().dsdf_mean_f64(_lib.ptr(x), x.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream()))
     return out
 
 

@@ -13,7 +13,7 @@ fused Adam on the table.
 import torch
 
 from . import _lib
-from .engine import Engine, _ptr, _stream
+from .engine import Engine
 
 
 def reconstruct(engine: Engine, samples_xyz, samples_sdf, *, num_iterations=800, clamp_dist=0.1, lr=5e-3,
@@ -77,8 +77,8 @@ def reconstruct(engine: Engine, samples_xyz, samples_sdf, *, num_iterations=800,
         # every shape has its OWN mean over its S points: normalise by S, then the B losses are independent
         engine.train_forward_backward(z, dz, seg_scene, seg_off, x, s, n_norm=S, clamp_dist=clamp_dist, reg_coef=0.0,
                                       code_bound=None, training=False, accumulate=False, seg_len=S, frozen_decoder=True)
-        _lib.check(engine.lib.dsdf_adam_latent_sched(_ptr(z), _ptr(dz), _ptr(m), _ptr(v), z.numel(), _ptr(sched), num_iterations,
-                                                     _ptr(counter), b1, b2, eps, l2c, _stream()))
+        _lib.check(engine.lib.dsdf_adam_latent_sched(_lib.ptr(z), _lib.ptr(dz), _lib.ptr(m), _lib.ptr(v), z.numel(), _lib.ptr(sched), num_iterations,
+                                                     _lib.ptr(counter), b1, b2, eps, l2c, _lib.stream()))
 
     if graph is None:
         graph = callback is None and os.environ.get("DSDF_GRAPH") == "1"

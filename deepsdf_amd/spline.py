@@ -15,10 +15,6 @@ from . import _lib
 MAX_DEGREE = 3
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 class BSplineField:
     def __init__(self, degrees, knot_vectors, control_points):
         degrees = [int(d) for d in degrees]

@@ -24,14 +24,6 @@ MAX_FACES = INT32_MAX // 3
 STATS = ("edges", "boundary", "nonmanifold", "paired", "same_direction", "degenerate_halfedges")
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class SurfaceMesh:
     def __init__(self, verts, faces, device=None, _checked=False):
         if device is None:
@@ -106,11 +98,11 @@ class SurfaceMesh:
                 if nf:
                     lib = _lib.lib()
                     keys = torch.empty(3 * nf, dtype=torch.int64, device=self.device)
-                    _lib.check(lib.dsdf_mt_edge_keys(_ptr(self.F), nf, self.n_verts, _ptr(keys), _stream()))
+                    _lib.check(lib.dsdf_mt_edge_keys(_lib.ptr(self.F), nf, self.n_verts, _lib.ptr(keys), _lib.stream()))
                     skeys, order = torch.sort(keys, stable=True)
                     ws = self._ws()
-                    _lib.check(lib.dsdf_mt_adjacency(_ptr(self.F), nf, _ptr(skeys), _ptr(order), _ptr(mate), _ptr(stats), _ptr(ws),
-                                                     ws.numel(), _stream()))
+                    _lib.check(lib.dsdf_mt_adjacency(_lib.ptr(self.F), nf, _lib.ptr(skeys), _lib.ptr(order), _lib.ptr(mate), _lib.ptr(stats), _lib.ptr(ws),
+                                                     ws.numel(), _lib.stream()))
             self._cache["adj"] = (mate, stats.tolist())
         return self._cache["adj"]
 
@@ -144,8 +136,8 @@ class SurfaceMesh:
                 if nf:
                     mate = self.half_edge_mates()
                     ws = self._ws()
-                    _lib.check(_lib.lib().dsdf_mt_components(_ptr(mate), nf, _ptr(label), _ptr(size), C.byref(rounds), _ptr(ws), ws.numel(),
-                                                             _stream()))
+                    _lib.check(_lib.lib().dsdf_mt_components(_lib.ptr(mate), nf, _lib.ptr(label), _lib.ptr(size), C.byref(rounds), _lib.ptr(ws), ws.numel(),
+                                                             _lib.stream()))
             self.component_rounds = rounds.value
             self._cache["cc"] = (label, size)
         return self._cache["cc"]
@@ -178,7 +170,7 @@ class SurfaceMesh:
             with torch.cuda.device(self.device):
                 out = torch.zeros(self.n_faces, dtype=torch.uint8, device=self.device)
                 if self.n_faces:
-                    _lib.check(_lib.lib().dsdf_mt_face_degenerate(_ptr(self.V), self.n_verts, _ptr(self.F), self.n_faces, _ptr(out), _stream()))
+                    _lib.check(_lib.lib().dsdf_mt_face_degenerate(_lib.ptr(self.V), self.n_verts, _lib.ptr(self.F), self.n_faces, _lib.ptr(out), _lib.stream()))
             self._cache["deg"] = out.bool()
         return self._cache["deg"]
 
@@ -193,8 +185,8 @@ class SurfaceMesh:
                 vstart = torch.searchsorted(corners, torch.arange(self.n_verts + 1, dtype=torch.int64, device=self.device))
                 normals = torch.empty(self.n_verts, 3, dtype=torch.float32, device=self.device)
                 grad = torch.empty(self.n_verts, 3, dtype=torch.float32, device=self.device)
-                _lib.check(_lib.lib().dsdf_mt_vertex_geometry(_ptr(self.V), self.n_verts, _ptr(self.F), self.n_faces, _ptr(order), _ptr(vstart),
-                                                              _ptr(normals), _ptr(grad), _stream()))
+                _lib.check(_lib.lib().dsdf_mt_vertex_geometry(_lib.ptr(self.V), self.n_verts, _lib.ptr(self.F), self.n_faces, _lib.ptr(order), _lib.ptr(vstart),
+                                                              _lib.ptr(normals), _lib.ptr(grad), _lib.stream()))
             self._cache["vg"] = (normals, grad)
         return self._cache["vg"]
 
@@ -215,8 +207,8 @@ class SurfaceMesh:
             if self.n_faces:
                 with torch.cuda.device(self.device):
                     ws = self._ws()
-                    _lib.check(_lib.lib().dsdf_mt_volume(_ptr(self.V), self.n_verts, _ptr(self.F), self.n_faces, _ptr(vol), _ptr(ws), ws.numel(),
-                                                         _stream()))
+                    _lib.check(_lib.lib().dsdf_mt_volume(_lib.ptr(self.V), self.n_verts, _lib.ptr(self.F), self.n_faces, _lib.ptr(vol), _lib.ptr(ws), ws.numel(),
+                                                         _lib.stream()))
             self._cache["vol"] = float(vol)
         return self._cache["vol"]
 
@@ -259,5 +251,5 @@ class SurfaceMesh:
         with torch.cuda.device(self.device):
             out = torch.empty(V, 3, R, dtype=torch.float32, device=self.device)
             st = (C.c_float * 3)(*self.stretch)
-            _lib.check(_lib.lib().dsdf_mt_project(_ptr(jac), _ptr(axis), _ptr(self.vertex_normals()), V, R, st, float(clip), _ptr(out), _stream()))
+            _lib.check(_lib.lib().dsdf_mt_project(_lib.ptr(jac), _lib.ptr(axis), _lib.ptr(self.vertex_normals()), V, R, st, float(clip), _lib.ptr(out), _lib.stream()))
         return out

@@ -14,25 +14,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib      # and nothing from mesh.py, which re-exports this module: either can be imported first
 
 INT32_MAX = 2 ** 31 - 1
-
-
-# this module imports nothing from mesh.py, which re-exports it: either can be imported first
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _triple(x, what):
-    t = [float(v) for v in (x if isinstance(x, (list, tuple, np.ndarray, torch.Tensor)) else [x] * 3)]
-    if len(t) != 3:
-        raise ValueError(f"{what} needs 3 values, got {len(t)}")
-    return t
 
 
 def _check_grid(sdf_grid, what):
@@ -61,8 +45,8 @@ def solid_components(sdf_grid, level=0.0):
         label = torch.empty(g.shape, dtype=torch.int32, device=g.device)
         size = torch.empty(g.shape, dtype=torch.int32, device=g.device)
         rounds = C.c_int32()
-        _lib.check(_lib.lib().dsdf_tet_components(_ptr(g), nx, ny, nz, float(level), _ptr(label), _ptr(size), C.byref(rounds),
-                                                  _ptr(ws), ws.numel(), _stream()))
+        _lib.check(_lib.lib().dsdf_tet_components(_lib.ptr(g), nx, ny, nz, float(level), _lib.ptr(label), _lib.ptr(size), C.byref(rounds),
+                                                  _lib.ptr(ws), ws.numel(), _lib.stream()))
     return label, size, rounds.value
 
 
@@ -96,24 +80,24 @@ def tetrahedralize(sdf_grid, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.
         g = largest_component_only(g, level)
     nx, ny, nz = g.shape
     lib = _lib.lib()
-    sp, org = (C.c_float * 3)(*_triple(spacing, "spacing")), (C.c_float * 3)(*_triple(origin, "origin"))
+    sp, org = (C.c_float * 3)(*_lib.triple(spacing, "spacing")), (C.c_float * 3)(*_lib.triple(origin, "origin"))
     dev = g.device
     with torch.cuda.device(dev):
         ws = _workspace(g)
         totals = torch.empty(3, dtype=torch.int64, device=dev)
-        _lib.check(lib.dsdf_tet_count(_ptr(g), nx, ny, nz, float(level), _ptr(totals), _ptr(ws), ws.numel(), _stream()))
+        _lib.check(lib.dsdf_tet_count(_lib.ptr(g), nx, ny, nz, float(level), _lib.ptr(totals), _lib.ptr(ws), ws.numel(), _lib.stream()))
         nv, nt, nb = totals.tolist()                        # the one host sync of a mesh
         if max(nv, nt, nb) > INT32_MAX:                     # the library refuses before writing anything: raise its error
-            _lib.check(lib.dsdf_tet_emit(_ptr(g), nx, ny, nz, float(level), sp, org, t_clamp, nv, nt, nb, None, None, None, None,
-                                         None, None, _ptr(ws), ws.numel(), _stream()))
+            _lib.check(lib.dsdf_tet_emit(_lib.ptr(g), nx, ny, nz, float(level), sp, org, t_clamp, nv, nt, nb, None, None, None, None,
+                                         None, None, _lib.ptr(ws), ws.numel(), _lib.stream()))
         verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
         tets = torch.empty(nt, 4, dtype=torch.int32, device=dev)
         bfaces = torch.empty(nb, 3, dtype=torch.int32, device=dev)
         kind = torch.empty(nb, dtype=torch.int8, device=dev)
         vp = torch.empty(nv, dtype=torch.int64, device=dev) if return_edges else None
         vc = torch.empty(nv, dtype=torch.int32, device=dev) if return_edges else None
-        _lib.check(lib.dsdf_tet_emit(_ptr(g), nx, ny, nz, float(level), sp, org, t_clamp, nv, nt, nb, _ptr(verts), _ptr(tets),
-                                     _ptr(bfaces), _ptr(kind), _ptr(vp), _ptr(vc), _ptr(ws), ws.numel(), _stream()))
+        _lib.check(lib.dsdf_tet_emit(_lib.ptr(g), nx, ny, nz, float(level), sp, org, t_clamp, nv, nt, nb, _lib.ptr(verts), _lib.ptr(tets),
+                                     _lib.ptr(bfaces), _lib.ptr(kind), _lib.ptr(vp), _lib.ptr(vc), _lib.ptr(ws), ws.numel(), _lib.stream()))
     m = TetMesh(verts, tets, bfaces, kind, vp, vc)
     m._indices_checked = True                               # the kernels' own ids: boundary_surface need not range-check them
     return m
@@ -174,8 +158,8 @@ class TetMesh:
 
     def transformed(self, scale=1.0, shift=0.0):
         """A TetMesh with vertices verts * scale + shift (three values each, or one), in the vertices' dtype; scale > 0."""
-        s = torch.tensor(_triple(scale, "scale"), dtype=self.verts.dtype, device=self.device)
-        d = torch.tensor(_triple(shift, "shift"), dtype=self.verts.dtype, device=self.device)
+        s = torch.tensor(_lib.triple(scale, "scale"), dtype=self.verts.dtype, device=self.device)
+        d = torch.tensor(_lib.triple(shift, "shift"), dtype=self.verts.dtype, device=self.device)
         if not bool((s > 0).all()):
             raise ValueError("scale must be positive on every axis (a negative factor would turn the elements inside out)")
         m = TetMesh(self.verts * s + d, self.tets, self.bfaces, self.bface_kind, self.vert_point, self.vert_class)

@@ -127,6 +127,22 @@ def test_machinery_equals_the_oracle_array_for_array(name, dims, b, lip, min_rou
         assert r.stats["seeds"] > sg.follow_surface(np.where(field == 0, np.float32(1e-6), field), b, thr).stats["seeds"]
 
 
+def test_emitted_points_on_both_sides_of_the_offset_scan_pass_border():
+    """The points pass has more per-workgroup totals than one pass of offset_scan_kernel takes, and the emitted indices lie on both
+    sides of that border: their offsets are right only if the scan's carry is."""
+    k = G.constants()
+    dims, b, h = (132, 128, 128), 8, 2.0 / 127
+    i, j, kk = np.meshgrid(*[np.arange(n, dtype=np.float32) for n in dims], indexing="ij")
+    r2 = (i - np.float32(125.25)) ** 2 + (j - np.float32(64.5)) ** 2 + (kk - np.float32(63.75)) ** 2
+    field = ((np.sqrt(r2) - np.float32(6)) * np.float32(h)).astype(np.float32)
+    r = _compare(("small sphere at the far end", dims, b, 1), field, b, sg.threshold(b, (h, h, h), 1))
+    print(f"{dims} b={b}: {r.stats}, indices {[(int(x.min()), int(x.max())) for x in r.indices]}")
+    assert r.stats["rounds"] == 1 and r.stats["seeds"] > 0
+    per_pass = k["MC_SCAN_THREADS"] * k["MC_SCAN_PER_THREAD"]             # totals per pass; one total per SG_BLOCK points
+    assert -(-field.size // k["SG_BLOCK"]) > per_pass
+    assert r.indices[0].min() // k["SG_BLOCK"] < per_pass <= r.indices[0].max() // k["SG_BLOCK"]
+
+
 def _cases(grid):
     inside = grid < 0
     nx, ny, nz = grid.shape

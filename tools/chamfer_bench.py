@@ -24,7 +24,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from deepsdf_amd import _lib, metrics  # noqa: E402
-from deepsdf_amd.meshsdf import TriangleMesh, _ptr, _stream  # noqa: E402
+from deepsdf_amd._lib import ptr as _ptr, stream as _stream  # noqa: E402
+from deepsdf_amd.meshsdf import TriangleMesh  # noqa: E402
 
 
 def best_ms(call, reps):

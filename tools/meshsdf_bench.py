@@ -30,7 +30,8 @@ import torch  # noqa: E402
 from deepsdf_amd import _lib, asmcheck  # noqa: E402
 from deepsdf_amd.build import LIB  # noqa: E402
 from deepsdf_amd.mesh import marching_cubes  # noqa: E402
-from deepsdf_amd.meshsdf import TriangleMesh, _ptr, _stream  # noqa: E402
+from deepsdf_amd._lib import ptr as _ptr, stream as _stream  # noqa: E402
+from deepsdf_amd.meshsdf import TriangleMesh  # noqa: E402
 from deepsdf_amd.sdf_sampler import SDFfromMesh, SDFSampler  # noqa: E402
 from tests.meshsdf_numpy import icosphere  # noqa: E402
 

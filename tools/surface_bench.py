@@ -28,7 +28,8 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from deepsdf_amd import _lib  # noqa: E402
 from deepsdf_amd.mesh import marching_cubes, microstructure_mesh_diff, sdf_grid  # noqa: E402
-from deepsdf_amd.surface import SurfaceMesh, _ptr, _stream  # noqa: E402
+from deepsdf_amd._lib import ptr as _ptr, stream as _stream  # noqa: E402
+from deepsdf_amd.surface import SurfaceMesh  # noqa: E402
 from tools import mesh_bench, ms_bench  # noqa: E402
 
 STEPS = ("edge_keys", "edge_sort", "adjacency", "components", "degenerate", "corner_sort", "vertex_geometry", "volume")
