@@ -88,6 +88,12 @@ class DsdfSgPlan(C.Structure):
                 ("ws_bytes", C.c_size_t), ("state_offset", C.c_size_t), ("have_offset", C.c_size_t)]
 
 
+class DsdfFemOp(C.Structure):
+    _fields_ = [("tets", C.c_void_p), ("corner_order", C.c_void_p), ("vstart", C.c_void_p), ("geom", C.c_void_p),
+                ("dinv", C.c_void_p), ("mask", C.c_void_p), ("n_verts", C.c_int64), ("n_tets", C.c_int64),
+                ("lam", C.c_double), ("mu", C.c_double)]
+
+
 class DsdfWsRegion(C.Structure):      # debug only: one row of dsdf_debug_ws_regions
     _fields_ = [("name", C.c_char * 24), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
 
@@ -111,6 +117,7 @@ class DsdfError(RuntimeError):
 
 _P, _I64, _I32, _F, _SZ = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
 _NET = C.POINTER(DsdfNet)
+_D, _FEM = C.c_double, C.POINTER(DsdfFemOp)
 
 # name -> argtypes; every function returns int except dsdf_last_error
 PROTOTYPES = {
@@ -193,6 +200,13 @@ PROTOTYPES = {
     "dsdf_tet_emit": [_P, _I32, _I32, _I32, _F, C.POINTER(_F), C.POINTER(_F), _F, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ,
                       _P],
     "dsdf_tet_components": [_P, _I32, _I32, _I32, _F, _P, _P, C.POINTER(_I32), _P, _SZ, _P],
+    "dsdf_fem_plan": [_I64, _I64, _I64, C.POINTER(_SZ)],
+    "dsdf_fem_setup": [_FEM, _P, _P, _P, _P, _P, _SZ, _P],
+    "dsdf_fem_apply": [_FEM, _P, _P, _P, _SZ, _P],
+    "dsdf_fem_load": [_P, _I64, _P, _I64, _P, _P, _P, C.POINTER(_D), _P, _P, _P],
+    "dsdf_fem_solve": [_FEM, _P, _P, _D, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_D), _P, _SZ, _P],
+    "dsdf_fem_energy": [_FEM, _P, _P, _I32, _P, _P, _P, _SZ, _P],
+    "dsdf_fem_boundary_gradient": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -30,6 +30,7 @@
 #include "meshtopo.hpp"
 #include "sparsegrid.hpp"
 #include "tetmesh.hpp"
+#include "fem.hpp"
 
 using namespace dsdf;
 
@@ -3220,6 +3221,195 @@ int dsdf_tet_components(const float* sdf, int32_t nx, int32_t ny, int32_t nz, fl
     LAUNCH_OK("tet_cc_hook_kernel");
     return 0;
   }, size, n_rounds);
+}
+
+// ---- P1 linear elasticity (fem.hpp) -----------------------------------------------------------------------------------
+namespace {
+struct FemPlan {
+  int64_t nbv, nbe, npart;
+  size_t sig, r, z, p, ap, part[2], cnt, scal, total;
+};
+
+int fem_plan(int64_t nv, int64_t nt, int64_t nb, FemPlan* P, WsTable* rec = nullptr) {
+  if (nv < 1 || nt < 1 || nb < 0 || nv > INT32_MAX || nt > INT32_MAX / 4 || nb > INT32_MAX / 3)
+    return fail(DSDF_E_INVALID, "fem: %lld vertices / %lld elements / %lld boundary triangles (need >= 1 vertex and element; corners fit int32)",
+                (long long)nv, (long long)nt, (long long)nb);
+  P->nbv = (nv + FEM_BLOCK - 1) / FEM_BLOCK;
+  P->nbe = (nt + FEM_BLOCK - 1) / FEM_BLOCK;
+  P->npart = std::max(P->nbv, P->nbe);
+  WsCarver c(rec);
+  P->sig = c.take("fem_sigma", -1, (size_t)nt * 6 * 8);
+  P->r = c.take("fem_r", -1, (size_t)nv * 3 * 8);
+  P->z = c.take("fem_z", -1, (size_t)nv * 3 * 8);
+  P->p = c.take("fem_p", -1, (size_t)nv * 3 * 8);
+  P->ap = c.take("fem_ap", -1, (size_t)nv * 3 * 8);
+  P->part[0] = c.take("fem_part0", -1, (size_t)P->npart * 8);
+  P->part[1] = c.take("fem_part1", -1, (size_t)P->npart * 8);
+  P->cnt = c.take("fem_cnt", -1, (size_t)P->npart * 4);
+  P->scal = c.take("fem_scal", -1, sizeof(FemScal));
+  P->total = c.finish(c.o);
+  return 0;
+}
+
+// The checks every entry that takes an operator shares, the plan it records, and the kernels' view of the operator.
+int fem_op(const char* what, const DsdfFemOp* op, void* ws, size_t ws_bytes, FemPlan* P, FemMesh* m) {
+  if (!op) return fail(DSDF_E_INVALID, "%s: NULL operator", what);
+  TRY(fem_plan(op->n_verts, op->n_tets, 0, P, &t_last_plan));
+  if (!op->tets || !op->corner_order || !op->vstart || !op->geom || !op->dinv || !op->mask)
+    return fail(DSDF_E_INVALID, "%s: NULL tets, corner_order, vstart, geom, dinv or mask", what);
+  if (!aligned16(op->tets)) return fail(DSDF_E_INVALID, "%s: tets not 16-byte aligned (an element is read as one int4)", what);
+  if (!std::isfinite(op->lam) || !std::isfinite(op->mu) || !(op->mu > 0.0) || !(op->lam + 2.0 * op->mu > 0.0))
+    return fail(DSDF_E_INVALID, "%s: lam %g, mu %g (need finite values, mu > 0, lam + 2 mu > 0)", what, op->lam, op->mu);
+  if (!ws) return fail(DSDF_E_INVALID, "%s: NULL workspace", what);
+  if (ws_bytes < P->total) return fail(DSDF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, P->total);
+  if (((uintptr_t)ws & 255) != 0) return fail(DSDF_E_INVALID, "%s: workspace not 256-byte aligned", what);
+  m->tets = op->tets; m->corder = op->corner_order; m->vstart = op->vstart; m->geom = op->geom; m->mask = op->mask;
+  m->nt = op->n_tets; m->nv = op->n_verts; m->lam = op->lam; m->mu = op->mu;
+  return 0;
+}
+
+int fem_boundary_args(const char* what, const double* verts, int64_t nv, const int32_t* bfaces, int64_t nb, const int64_t* border,
+                      const int64_t* bvstart, const double* out) {
+  if (nv < 1 || nb < 0 || nv > INT32_MAX || nb > INT32_MAX / 3)
+    return fail(DSDF_E_INVALID, "%s: %lld vertices / %lld boundary triangles", what, (long long)nv, (long long)nb);
+  if (!verts || !bvstart || !out || (nb > 0 && (!bfaces || !border)))
+    return fail(DSDF_E_INVALID, "%s: NULL verts, bfaces, bcorner_order, bvstart or output", what);
+  return 0;
+}
+
+inline dim3 fem_grid(int64_t n) { return dim3((unsigned)((n + FEM_BLOCK - 1) / FEM_BLOCK)); }
+
+// y = A x on the stream: the two passes; part / scal as in fem_gather_kernel
+int fem_apply_launch(const FemMesh& m, const FemPlan& P, char* b, const double* x, double* y, double* part, const FemScal* scal,
+                     hipStream_t st) {
+  double* sig = (double*)(b + P.sig);
+  hipLaunchKernelGGL(fem_stress_kernel, fem_grid(m.nt), dim3(FEM_BLOCK), 0, st, m, x, sig, scal);
+  LAUNCH_OK("fem_stress_kernel");
+  hipLaunchKernelGGL(fem_gather_kernel, fem_grid(m.nv), dim3(FEM_BLOCK), 0, st, m, (const double*)sig, x, y, part, scal);
+  LAUNCH_OK("fem_gather_kernel");
+  return 0;
+}
+}  // namespace
+
+int dsdf_fem_plan(int64_t n_verts, int64_t n_tets, int64_t n_bfaces, size_t* ws_bytes) {
+  FemPlan P;
+  TRY(fem_plan(n_verts, n_tets, n_bfaces, &P, &t_last_plan));
+  if (!ws_bytes) return fail(DSDF_E_INVALID, "fem plan: NULL ws_bytes");
+  *ws_bytes = P.total;
+  return 0;
+}
+
+int dsdf_fem_setup(const DsdfFemOp* op, const double* verts, const uint8_t* fixed, double* diag, int64_t* counts, void* ws,
+                   size_t ws_bytes, void* stream) {
+  FemPlan P; FemMesh m;
+  TRY(fem_op("fem setup", op, ws, ws_bytes, &P, &m));
+  if (!verts || !diag || !counts) return fail(DSDF_E_INVALID, "fem setup: NULL verts, diag or counts");
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* cnt = (int32_t*)((char*)ws + P.cnt);
+  hipLaunchKernelGGL(fem_geom_kernel, fem_grid(m.nt), dim3(FEM_BLOCK), 0, st, verts, m.nv, m.tets, m.nt, (double*)op->geom, cnt);
+  LAUNCH_OK("fem_geom_kernel");
+  hipLaunchKernelGGL(fem_count_final_kernel, dim3(1), dim3(FEM_BLOCK), 0, st, (const int32_t*)cnt, P.nbe, counts);
+  LAUNCH_OK("fem_count_final_kernel");
+  hipLaunchKernelGGL(fem_diag_kernel, fem_grid(m.nv), dim3(FEM_BLOCK), 0, st, m, fixed, diag, (double*)op->dinv, (uint8_t*)op->mask, cnt);
+  LAUNCH_OK("fem_diag_kernel");
+  hipLaunchKernelGGL(fem_count_final_kernel, dim3(1), dim3(FEM_BLOCK), 0, st, (const int32_t*)cnt, P.nbv, counts + 1);
+  LAUNCH_OK("fem_count_final_kernel");
+  return 0;
+}
+
+int dsdf_fem_apply(const DsdfFemOp* op, const double* x, double* y, void* ws, size_t ws_bytes, void* stream) {
+  FemPlan P; FemMesh m;
+  TRY(fem_op("fem apply", op, ws, ws_bytes, &P, &m));
+  if (!x || !y || x == y) return fail(DSDF_E_INVALID, "fem apply: NULL x or y, or x == y");
+  return fem_apply_launch(m, P, (char*)ws, x, y, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int dsdf_fem_load(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
+                  const int64_t* bvstart, const uint8_t* face_sel, const double* traction, const uint8_t* mask, double* f, void* stream) {
+  TRY(fem_boundary_args("fem load", verts, n_verts, bfaces, n_bfaces, bcorner_order, bvstart, f));
+  if (!traction || !std::isfinite(traction[0]) || !std::isfinite(traction[1]) || !std::isfinite(traction[2]))
+    return fail(DSDF_E_INVALID, "fem load: NULL or non-finite traction");
+  hipLaunchKernelGGL(fem_boundary_kernel<true>, fem_grid(n_verts), dim3(FEM_BLOCK), 0, (hipStream_t)stream, verts, n_verts, bfaces, n_bfaces,
+                     bcorner_order, bvstart, face_sel, traction[0], traction[1], traction[2], mask, (const double*)nullptr, f);
+  LAUNCH_OK("fem_boundary_kernel<load>");
+  return 0;
+}
+
+int dsdf_fem_boundary_gradient(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
+                               const int64_t* bvstart, const double* weight, double* grad, void* stream) {
+  TRY(fem_boundary_args("fem boundary gradient", verts, n_verts, bfaces, n_bfaces, bcorner_order, bvstart, grad));
+  hipLaunchKernelGGL(fem_boundary_kernel<false>, fem_grid(n_verts), dim3(FEM_BLOCK), 0, (hipStream_t)stream, verts, n_verts, bfaces, n_bfaces,
+                     bcorner_order, bvstart, (const uint8_t*)nullptr, 0.0, 0.0, 0.0, (const uint8_t*)nullptr, weight, grad);
+  LAUNCH_OK("fem_boundary_kernel<gradient>");
+  return 0;
+}
+
+int dsdf_fem_solve(const DsdfFemOp* op, const double* f, double* u, double rel_tol, int32_t max_iter, int32_t check_every,
+                   int32_t* iterations, int32_t* converged, double* ratio, void* ws, size_t ws_bytes, void* stream) {
+  FemPlan P; FemMesh m;
+  if (iterations) *iterations = 0;
+  if (converged) *converged = 0;
+  if (ratio) *ratio = 0.0;
+  TRY(fem_op("fem solve", op, ws, ws_bytes, &P, &m));
+  if (!f || !u || f == u) return fail(DSDF_E_INVALID, "fem solve: NULL f or u, or f == u");
+  if (!(rel_tol >= 0.0) || !std::isfinite(rel_tol)) return fail(DSDF_E_INVALID, "fem solve: rel_tol %g must be finite and >= 0", rel_tol);
+  if (max_iter < 0 || check_every < 1) return fail(DSDF_E_INVALID, "fem solve: max_iter %d < 0 or check_every %d < 1", max_iter, check_every);
+  hipStream_t st = (hipStream_t)stream;
+  char* b = (char*)ws;
+  double *r = (double*)(b + P.r), *z = (double*)(b + P.z), *p = (double*)(b + P.p), *ap = (double*)(b + P.ap);
+  double *part0 = (double*)(b + P.part[0]), *part1 = (double*)(b + P.part[1]);
+  FemScal* s = (FemScal*)(b + P.scal);
+  const dim3 gv = fem_grid(m.nv), one(1), blk(FEM_BLOCK);
+  hipLaunchKernelGGL(fem_cg_start_kernel, gv, blk, 0, st, m.nv, m.mask, op->dinv, f, u, r, z, p, part1);
+  LAUNCH_OK("fem_cg_start_kernel");
+  hipLaunchKernelGGL(fem_cg_init_kernel, one, blk, 0, st, (const double*)part1, P.nbv, s, rel_tol * rel_tol);
+  LAUNCH_OK("fem_cg_init_kernel");
+  FemScal h;
+  for (int32_t i = 0; i < max_iter; ++i) {
+    TRY(fem_apply_launch(m, P, b, p, ap, part0, s, st));
+    hipLaunchKernelGGL(fem_cg_alpha_kernel, one, blk, 0, st, (const double*)part0, P.nbv, s);
+    LAUNCH_OK("fem_cg_alpha_kernel");
+    hipLaunchKernelGGL(fem_cg_update_kernel, gv, blk, 0, st, m.nv, op->dinv, (const FemScal*)s, (const double*)p, (const double*)ap, u, r, z, part1);
+    LAUNCH_OK("fem_cg_update_kernel");
+    hipLaunchKernelGGL(fem_cg_beta_kernel, one, blk, 0, st, (const double*)part1, P.nbv, s);
+    LAUNCH_OK("fem_cg_beta_kernel");
+    hipLaunchKernelGGL(fem_cg_dir_kernel, fem_grid(m.nv * 3), blk, 0, st, m.nv * 3, (const FemScal*)s, (const double*)z, p);
+    LAUNCH_OK("fem_cg_dir_kernel");
+    if ((i + 1) % check_every == 0 && i + 1 < max_iter) {
+      HIP_OK(hipMemcpyAsync(&h, s, sizeof(h), hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+      if (h.done) break;
+    }
+  }
+  HIP_OK(hipMemcpyAsync(&h, s, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (iterations) *iterations = h.it;
+  if (converged) *converged = h.converged;
+  if (ratio) *ratio = h.rho0 > 0.0 ? h.rho / h.rho0 : 0.0;
+  return 0;
+}
+
+int dsdf_fem_energy(const DsdfFemOp* op, const double* u, double* we, int32_t nodal, double* wv, double* totals, void* ws,
+                    size_t ws_bytes, void* stream) {
+  FemPlan P; FemMesh m;
+  TRY(fem_op("fem energy", op, ws, ws_bytes, &P, &m));
+  if (!u || !we || !totals) return fail(DSDF_E_INVALID, "fem energy: NULL u, we or totals");
+  if (nodal < 0 || nodal > FEM_NODAL_LAST || (nodal != 0) != (wv != nullptr))
+    return fail(DSDF_E_INVALID, "fem energy: nodal %d (0: none, 1: mean, 2: last) and wv must come together", nodal);
+  hipStream_t st = (hipStream_t)stream;
+  char* b = (char*)ws;
+  double *part0 = (double*)(b + P.part[0]), *part1 = (double*)(b + P.part[1]);
+  hipLaunchKernelGGL(fem_energy_elem_kernel, fem_grid(m.nt), dim3(FEM_BLOCK), 0, st, m, u, we, part0, part1);
+  LAUNCH_OK("fem_energy_elem_kernel");
+  hipLaunchKernelGGL(fem_sum_final_kernel, dim3(1), dim3(FEM_BLOCK), 0, st, (const double*)part0, P.nbe, totals);
+  LAUNCH_OK("fem_sum_final_kernel");
+  hipLaunchKernelGGL(fem_sum_final_kernel, dim3(1), dim3(FEM_BLOCK), 0, st, (const double*)part1, P.nbe, totals + 1);
+  LAUNCH_OK("fem_sum_final_kernel");
+  if (nodal) {
+    hipLaunchKernelGGL(fem_energy_vertex_kernel, fem_grid(m.nv), dim3(FEM_BLOCK), 0, st, m, (const double*)we, (int)nodal, wv);
+    LAUNCH_OK("fem_energy_vertex_kernel");
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -156,6 +156,13 @@ class TetMesh:
         from .surface import SurfaceMesh
         return SurfaceMesh(self.verts, self.bfaces, self.device, _checked=self._indices_checked)
 
+    def to(self, device):
+        """The same mesh with every array on `device`."""
+        m = TetMesh(*[None if t is None else t.to(device)
+                      for t in (self.verts, self.tets, self.bfaces, self.bface_kind, self.vert_point, self.vert_class)])
+        m._indices_checked = self._indices_checked
+        return m
+
     def transformed(self, scale=1.0, shift=0.0):
         """A TetMesh with vertices verts * scale + shift (three values each, or one), in the vertices' dtype; scale > 0."""
         s = torch.tensor(_lib.triple(scale, "scale"), dtype=self.verts.dtype, device=self.device)
@@ -176,6 +183,42 @@ class TetMesh:
         top = self.verts[:, 2].max() - tolerance
         three = torch.full_like(x_max, 3, dtype=torch.int32)
         return torch.where(x_max < tolerance, torch.ones_like(three), torch.where(z_max > top, 2 * torch.ones_like(three), three))
+
+    @classmethod
+    def read_mfem(cls, path):
+        """(TetMesh on the host with fp64 vertices, attributes [M] int32) of an MFEM mesh v1.0 text file as write_mfem writes it:
+        tetrahedra (geometry 4) and boundary triangles (geometry 2) only; anything else is a ValueError that names it.  bface_kind
+        is not in the file and comes back 0."""
+        with open(path) as fh:
+            body = [ln.strip() for ln in fh.read().splitlines()]
+        if not body or body[0] != "MFEM mesh v1.0":
+            raise ValueError(f"{path}: not an 'MFEM mesh v1.0' file")
+        body = [ln for ln in body[1:] if ln and not ln.startswith("#")]
+        try:
+            at = {name: body.index(name) for name in ("dimension", "elements", "boundary", "vertices")}
+        except ValueError:
+            raise ValueError(f"{path}: needs the sections dimension, elements, boundary and vertices") from None
+        if body[at["dimension"] + 1] != "3":
+            raise ValueError(f"{path}: dimension {body[at['dimension'] + 1]}, only 3 is read")
+
+        def block(name, skip, cols, dtype, what):
+            n = int(body[at[name] + 1])
+            rows = body[at[name] + 1 + skip:at[name] + 1 + skip + n]
+            arr = np.array([r.split() for r in rows] if n else np.empty((0, cols)), dtype=object)
+            if len(rows) != n or arr.ndim != 2 or arr.shape[1] != cols:
+                raise ValueError(f"{path}: the {name} section holds something else than {n} {what}")
+            return arr.astype(dtype)
+        el = block("elements", 1, 6, np.int64, "tetrahedra `attribute 4 v0 v1 v2 v3`")
+        bd = block("boundary", 1, 5, np.int64, "triangles `attribute 2 v0 v1 v2`")
+        if len(el) and not (el[:, 1] == 4).all():
+            raise ValueError(f"{path}: element geometry {sorted(set(el[:, 1].tolist()) - {4})}, only tetrahedra (4) are read")
+        if len(bd) and not (bd[:, 1] == 2).all():
+            raise ValueError(f"{path}: boundary geometry {sorted(set(bd[:, 1].tolist()) - {2})}, only triangles (2) are read")
+        if body[at["vertices"] + 2] != "3":
+            raise ValueError(f"{path}: vertices of dimension {body[at['vertices'] + 2]} (a nodes grid function is not read), only 3 is")
+        vx = block("vertices", 2, 3, np.float64, "vertices of 3 coordinates")
+        m = cls(vx, el[:, 2:].astype(np.int32), bd[:, 2:].astype(np.int32), np.zeros(len(bd), dtype=np.int8))
+        return m, torch.from_numpy(bd[:, 0].astype(np.int32))
 
     def write_mfem(self, path, attributes=None):
         """MFEM mesh v1.0 text: elements `1 4 v0 v1 v2 v3` (attribute 1, geometry 4 = tetrahedron), boundary `attr 2 v0 v1 v2`

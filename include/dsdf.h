@@ -727,6 +727,69 @@ int dsdf_tet_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float le
 int dsdf_tet_components(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float level, int32_t* label, int32_t* size,
                         int32_t* n_rounds /*[host]*/, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- P1 linear elasticity on a tetrahedral mesh (csrc/fem.hpp; numpy / scipy restatement: tests/fem_numpy.py) ------
+ * Replaces, for order-1 tetrahedra and constant Lame coefficients, what the reference does through mfem in
+ * analysis/MFEMLinearElasticity.py.  fp64 throughout; no floating-point atomics; every sum over the mesh runs in a fixed order, so
+ * two identical calls give identical bytes.  Additions only: DSDF_ABI_VERSION is unchanged.
+ *
+ * Mesh: verts [n_verts][3] fp64, tets [n_tets][4] int32 (16-byte aligned), bfaces [n_bfaces][3] int32 (outward); counts fit int32.
+ *   corner_order [4 n_tets] int64: the corners c = 4 e + a stably sorted by their vertex tets[e][a]; vstart [n_verts + 1] int64: the
+ *   first sorted corner of every vertex (dsdf_mt_vertex_geometry's pair, on the elements); bcorner_order [3 n_bfaces] / bvstart
+ *   the same for the boundary triangles.  Every index read from memory is clamped into its range before it is used as an address.
+ * Element: e_k = x_k - x_0, c1 = e2 x e3, c2 = e3 x e1, c3 = e1 x e2, det = (e1.x c1.x + e1.y c1.y) + e1.z c1.z, V = det / 6,
+ *   g_k = c_k / det (k = 1..3), every operation rounded on its own; g_0 = -((g_1 + g_2) + g_3).  geom [10][n_tets] holds g_1, g_2,
+ *   g_3 and V.  An element with V <= 0 or a non-finite gradient is skipped: stored as zeros, counted, and absent from everything below.
+ *   K_ab[i][j] = V (lam g_a,i g_b,j + mu g_b,i g_a,j + mu (g_a . g_b) delta_ij).
+ * Operator: A = P K P + (I - P); P zeroes the three components of every masked vertex: the fixed ones and the held ones (a vertex
+ *   left with no element that counts).  y = A x as V sigma(P x) per element (sigma = lam tr(H) I + mu (H + H^T), H = sum_b x_b g_b^T),
+ *   then per vertex the sum of (V sigma)_e g_a over its corners in corner_order's order.
+ * Preconditioner: per vertex D = sum of K_aa over its corners, six values (xx, yy, zz, xy, xz, yz), and its inverse; masked vertices
+ *   carry the identity in both. */
+typedef struct {
+  const int32_t* tets;          /* [n_tets][4] */
+  const int64_t* corner_order;  /* [4 n_tets] */
+  const int64_t* vstart;        /* [n_verts + 1] */
+  const double* geom;           /* [10][n_tets]   dsdf_fem_setup's */
+  const double* dinv;           /* [n_verts][6]   dsdf_fem_setup's */
+  const uint8_t* mask;          /* [n_verts]      dsdf_fem_setup's */
+  int64_t n_verts, n_tets;
+  double lam, mu;
+} DsdfFemOp;
+/* One workspace (256-byte aligned; planner conventions, regions fem_*) serves every dsdf_fem_* call on a mesh of these sizes.
+ * Replaces nothing in the reference: mfem allocates as it goes. */
+int dsdf_fem_plan(int64_t n_verts, int64_t n_tets, int64_t n_bfaces, size_t* ws_bytes);                 /* [host] */
+/* Element geometry, preconditioner and mask of `op` (its geom, dinv and mask are WRITTEN here: pass the buffers; lam, mu finite,
+ * mu > 0, lam + 2 mu > 0); fixed [n_verts] uint8 or NULL; diag [n_verts][6]; counts [2] int64 on the device: skipped
+ * elements, held vertices.  Replaces ElasticityIntegrator's assembly and FormLinearSystem's elimination of the essential dofs
+ * (MFEMLinearElasticity.py:308-315) and the smoother's set-up (:318). */
+int dsdf_fem_setup(const DsdfFemOp* op, const double* verts, const uint8_t* fixed, double* diag, int64_t* counts, void* ws,
+                   size_t ws_bytes, void* stream);
+/* y = A x, x and y [n_verts][3], x != y.  The operator the CG of MFEMLinearElasticity.py:319-326 multiplies by. */
+int dsdf_fem_apply(const DsdfFemOp* op, const double* x, double* y, void* ws, size_t ws_bytes, void* stream);
+/* f [n_verts][3] = sum over the vertex's boundary triangles with face_sel[f] != 0 (NULL: all) of area_f / 3 * traction ([host] 3
+ * doubles), 0 at vertices with mask[v] != 0 (NULL: none): VectorBoundaryLFIntegrator with a constant coefficient on the marked
+ * attributes (MFEMLinearElasticity.py:304-306), on P1. */
+int dsdf_fem_load(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
+                  const int64_t* bvstart, const uint8_t* face_sel, const double* traction, const uint8_t* mask, double* f, void* stream);
+/* Preconditioned CG for A u = P f from u = 0 with MFEM's CGSolver rule (MFEMLinearElasticity.py:319-326: rel_tol 1e-10, 10000
+ * iterations): stop when <z, r> <= rel_tol^2 <z0, r0>.  rho, alpha, beta, the iteration count and a done flag live on the device; the
+ * kernel that updates them sets done on convergence, on p . A p <= 0 and on a <z, r> that is negative or not a number, and every
+ * later kernel returns at once, so u and the count do not depend on check_every (>= 1: the host reads the flag every check_every
+ * iterations).  *iterations, *converged, *ratio = <z, r> / <z0, r0> are [host]; waits for the stream. */
+int dsdf_fem_solve(const DsdfFemOp* op, const double* f, double* u, double rel_tol, int32_t max_iter, int32_t check_every,
+                   int32_t* iterations, int32_t* converged, double* ratio, void* ws, size_t ws_bytes, void* stream);
+/* we [n_tets]: w_e = lam tr(H)^2 + mu sum_ij H_ij (H_ij + H_ji), H = grad u (StrainEnergyDensityCoefficient.Eval,
+ * MFEMLinearElasticity.py:255-266), 0 for a skipped element; wv [n_verts] (NULL with nodal = 0): nodal = 1 the volume-weighted mean
+ * over the vertex's elements that count, nodal = 2 the value of the one with the highest index (what ProjectCoefficient, :340, is
+ * believed to leave); totals [2] on the device: sum V_e w_e (clcTotCompliance, :371-385) and sum V_e (clcVolume, :387-403). */
+int dsdf_fem_energy(const DsdfFemOp* op, const double* u, double* we, int32_t nodal, double* wv, double* totals, void* ws,
+                    size_t ws_bytes, void* stream);
+/* grad [n_verts][3] = (weight[v], NULL: 1) * sum over the vertex's boundary triangles of (1 / 2) (b - a) x (c - a) / 3: what
+ * BoundaryNormalLFIntegrator summed over a P1 space pairs a nodal field with (clcVolumeShapeDerivative, :405-424; with weight = -w_v
+ * clcComplianceShapeDerivative, :343-369). */
+int dsdf_fem_boundary_gradient(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
+                               const int64_t* bvstart, const double* weight, double* grad, void* stream);
+
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */
 int dsdf_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
