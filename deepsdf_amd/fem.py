@@ -108,8 +108,9 @@ class LinearElasticity:
         return self
 
     def load(self):
-        """P f [V, 3]: the load with the masked (fixed and held) vertices zeroed, as the solve uses it."""
-        return self.f * (self.mask == 0).to(torch.float64)[:, None]
+        """P f [V, 3]: the load with the masked (fixed and held) vertices zeroed, as the solve uses it: selected, not multiplied, so
+        that a value that is not finite at a masked vertex is dropped as fem_cg_start_kernel drops it."""
+        return torch.where((self.mask != 0)[:, None], torch.zeros_like(self.f), self.f)
 
     def apply(self, x):
         """A x for x [V, 3]."""

@@ -775,7 +775,14 @@ int dsdf_fem_load(const double* verts, int64_t n_verts, const int32_t* bfaces, i
  * iterations): stop when <z, r> <= rel_tol^2 <z0, r0>.  rho, alpha, beta, the iteration count and a done flag live on the device; the
  * kernel that updates them sets done on convergence, on p . A p <= 0 and on a <z, r> that is negative or not a number, and every
  * later kernel returns at once, so u and the count do not depend on check_every (>= 1: the host reads the flag every check_every
- * iterations).  *iterations, *converged, *ratio = <z, r> / <z0, r0> are [host]; waits for the stream. */
+ * iterations).  *iterations, *converged, *ratio = <z, r> / <z0, r0> are [host]; waits for the stream.
+ * What comes back (tests/test_gpu_fem_cg.py): f = 0 at every unmasked vertex: (0, 1, 0.0), u = 0.  <z0, r0> not a
+ * positive number (a NaN in f at an unmasked vertex): (0, 0, 0.0), u = 0.  p . A p <= 0 after j iterations: (j, 0, ratio of iteration
+ * j), u iterate j.  max_iter reached: (max_iter, 0, ratio), u that iterate; max_iter = 0: (0, 0, 1.0), u = 0.  A finite f so large
+ * that <z0, r0> and p . A p overflow to +inf: alpha is inf / inf, the solve ends after ONE iteration with (1, 0, NaN) and u is NaN at
+ * every vertex, the masked ones included -- check *converged before using u.  f at a masked vertex is dropped by selection, not by a product:
+ * a value there that is not finite changes nothing.  Every call starts from nothing: the workspace may come from any earlier solve,
+ * however it ended.  The three outputs are zeroed before an argument is refused. */
 int dsdf_fem_solve(const DsdfFemOp* op, const double* f, double* u, double rel_tol, int32_t max_iter, int32_t check_every,
                    int32_t* iterations, int32_t* converged, double* ratio, void* ws, size_t ws_bytes, void* stream);
 /* we [n_tets]: w_e = lam tr(H)^2 + mu sum_ij H_ij (H_ij + H_ji), H = grad u (StrainEnergyDensityCoefficient.Eval,

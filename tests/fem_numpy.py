@@ -2,7 +2,8 @@
 geometry with every operation rounded on its own (the kernels store the same bits), K assembled as a scipy.sparse CSR from
 K_ab[i][j] = V (lam g_a,i g_b,j + mu g_b,i g_a,j + mu (g_a . g_b) delta_ij), the masked operator, spsolve, a numpy restatement of the
 same preconditioned CG with the same preconditioner and stopping rule, every post-processing quantity, the term-wise absolute values
-the rounding bounds are stated against, and the wrong variants the discrimination tests evaluate.  Degrees of freedom are interleaved:
+the rounding bounds are stated against, the wrong variants the discrimination tests evaluate, and the same CG with its whole path kept,
+in four correct restatements and four wrong ones, on the solves the CG tests share (cg_problem).  Degrees of freedom are interleaved:
 dof 3 v + i is component i of vertex v."""
 import math
 
@@ -197,6 +198,153 @@ def pcg(A, Dinv, b, rel_tol=1e-10, max_iter=10000):
     return x.reshape(-1, 3), it, conv, rho / rho0
 
 
+# ---- the same CG, followed step by step (tests/test_gpu_fem_cg.py; DESIGN 4.21.5) ----------------------------------------------------
+CG_WRONG = ("stale_rho", "steepest", "rho0", "dir_from_r")
+
+
+def block_inverse_adjugate(d):
+    """[V, 6] -> [V, 3, 3] inverses by cofactors over the determinant: the kernels' route, another rounding than numpy's LU."""
+    xx, yy, zz, xy, xz, yz = (d[:, k] for k in range(6))
+    c = np.stack([yy * zz - yz * yz, xx * zz - xz * xz, xx * yy - xy * xy, xz * yz - xy * zz, xy * yz - xz * yy, xy * xz - xx * yz], 1)
+    det = (xx * c[:, 0] + xy * c[:, 3]) + xz * c[:, 4]
+    return sym3(c / det[:, None])
+
+
+def free_operator(verts, tets, lam, mu, mask):
+    """x [3V] -> A x [3V] without the assembled matrix: every element's 12 x 12 block times its own twelve values, then the elements'
+    forces summed per vertex -- the kernels' grouping (within the element first), where the CSR adds a row's entries one by one."""
+    tets = np.asarray(tets, dtype=np.int64)
+    Ke = element_matrices(*gradients(geometry(verts, tets)[0]), lam, mu).reshape(len(tets), 12, 12)
+    keep = ~np.asarray(mask, dtype=bool)
+    nv, flat = len(verts), tets.reshape(-1)
+
+    def op(x):
+        x = x.reshape(-1, 3)
+        F = np.matmul(Ke, np.where(keep[:, None], x, 0.0)[tets].reshape(-1, 12, 1)).reshape(-1, 3)
+        y = np.stack([np.bincount(flat, weights=F[:, i], minlength=nv) for i in range(3)], 1)
+        return np.where(keep[:, None], y, x).reshape(-1)
+    return op
+
+
+def _dot(order):
+    if order == "blas":
+        return lambda a, b: float(a @ b)
+    if order == "reversed":                      # the products summed pairwise from the far end: another grouping than the BLAS kernel's
+        return lambda a, b: float(np.add.reduce((a * b)[::-1].copy()))
+    raise ValueError(order)
+
+
+def pcg_trace(A, Dinv, b, rel_tol=1e-10, max_iter=10000, dot="blas", wrong=None):
+    """pcg, keeping the path.  A: a matrix or a callable x [3V] -> A x; dot: 'blas' or 'reversed'; wrong: None or one of CG_WRONG --
+    'stale_rho' (beta = rho' / the rho of the iteration before), 'steepest' (beta = 0), 'rho0' (beta = rho' / rho0), 'dir_from_r'
+    (p = r + beta p).  With a matrix, 'blas' and wrong=None every operation is pcg's: identical bytes.
+    Returns a dict: x [V, 3], it, conv, ratio as pcg; xs [it + 1, V, 3], xs[k] iterate k; ratios [it + 1], rho_k / rho0 (the recursive
+    one); scal [(rho', alpha, beta, pap)] per completed iteration; paps, ps: every p . A p computed and its p, the one that ended the
+    solve included; rho0."""
+    op = A if callable(A) else (lambda v: A @ v)
+    dt = _dot(dot)
+
+    def prec(r):
+        return np.einsum("vij,vj->vi", Dinv, r.reshape(-1, 3)).reshape(-1)
+    b = b.reshape(-1)
+    x = np.zeros_like(b)
+    r = b.copy()
+    z = prec(r)
+    p = z.copy()
+    with np.errstate(all="ignore"):
+        rho0 = rho = dt(z, r)
+    out = dict(xs=[x.reshape(-1, 3).copy()], ratios=[1.0], scal=[], paps=[], ps=[], rho0=rho0)
+
+    def done(it, conv, ratio):
+        out.update(x=x.reshape(-1, 3), it=it, conv=conv, ratio=ratio, xs=np.stack(out["xs"]), ratios=np.array(out["ratios"]))
+        return out
+    if not rho0 > 0.0:
+        out["ratios"] = [0.0]
+        return done(0, rho0 == 0.0, 0.0)
+    it, conv, rho_before = 0, False, rho0
+    with np.errstate(all="ignore"):
+        while it < max_iter:
+            ap = op(p)
+            pap = dt(p, ap)
+            out["paps"].append(pap)
+            out["ps"].append(p.copy())
+            if not pap > 0.0:
+                break
+            alpha = rho / pap
+            x += alpha * p
+            r -= alpha * ap
+            z = prec(r)
+            rn = dt(z, r)
+            it += 1
+            beta = {None: rn / rho, "dir_from_r": rn / rho, "stale_rho": rn / rho_before, "steepest": 0.0, "rho0": rn / rho0}[wrong]
+            rho_before, rho = rho, rn
+            out["xs"].append(x.reshape(-1, 3).copy())
+            out["ratios"].append(rho / rho0)
+            out["scal"].append((rn, alpha, beta, pap))
+            if rn <= rel_tol * rel_tol * rho0:
+                conv = rn >= 0.0
+                break
+            if not rn > 0.0:
+                break
+            p = (r if wrong == "dir_from_r" else z) + beta * p
+        return done(it, conv, rho / rho0)
+
+
+def iterate(tr, k):
+    """Iterate k of a trace; the last one from its end on (what solve(max_iter=k) returns)."""
+    return tr["xs"][min(k, tr["it"])]
+
+
+def cg_variants(verts, tets, lam, mu, mask, f, **kw):
+    """Four correct restatements of one solve, differing pairwise in what the kernels differ from any of them in: the operator's sum
+    order (assembled CSR / element by element), the dot products' order, and the route to the block inverses (LU / adjugate).
+    (A, Dinv by LU, {name: trace}); the first, 'csr', is pcg itself."""
+    A = masked(assemble(verts, tets, lam, mu), mask)
+    d = diag_blocks(A)
+    inv, adj = block_inverse(d), block_inverse_adjugate(d)
+    free = free_operator(verts, tets, lam, mu, mask)
+    runs = {"csr": (A, inv, "blas"), "csr reversed adjugate": (A, adj, "reversed"), "free adjugate": (free, adj, "blas"),
+            "free reversed": (free, inv, "reversed")}
+    return A, inv, {k: pcg_trace(op, Di, f, dot=dt, **kw) for k, (op, Di, dt) in runs.items()}
+
+
+def energy_norm(A, d):
+    d = d.reshape(-1)
+    return math.sqrt(max(float(d @ (A @ d)), 0.0))
+
+
+def cg_spread(A, traces, ref, k_max):
+    """s [k_max + 1]: s[k] the largest pairwise ||x_j^a - x_j^b||_A / ||ref||_A over the traces and j <= k."""
+    tr = list(traces.values())
+    nref = energy_norm(A, ref)
+    s = np.zeros(k_max + 1)
+    for k in range(k_max + 1):
+        xs = [iterate(t, k) for t in tr]
+        s[k] = max(energy_norm(A, xs[a] - xs[b]) for a in range(len(tr)) for b in range(a)) / nref
+    return np.maximum.accumulate(s)
+
+
+def cg_ratio_spread(traces, k_max):
+    """q [k_max + 1]: the same for the scalar rho_j / rho0, relative to the first trace's."""
+    tr = list(traces.values())
+    q = np.zeros(k_max + 1)
+    for k in range(k_max + 1):
+        rs = [t["ratios"][min(k, t["it"])] for t in tr]
+        q[k] = (max(rs) - min(rs)) / abs(rs[0]) if rs[0] != 0.0 else 0.0
+    return np.maximum.accumulate(q)
+
+
+def cg_iterate_bound(s):
+    """What tests/test_gpu_fem_cg.py holds the kernels' iterate k to, in relative energy norm: 16 times the restatements' own spread --
+    the kernels differ from a restatement in one more respect (contraction) than the restatements among themselves -- floored at 16 U."""
+    return 16.0 * np.maximum(s, U)
+
+
+def cg_ratio_bound(q):
+    """The same for the returned ratio, relative: 16 times the restatements' spread in rho_k / rho0, floored at 64 U."""
+    return np.maximum(16.0 * q, 64.0 * U)
+
+
 def true_residual(A, Dinv, b, u):
     """<D^-1 (b - A u), b - A u> / <D^-1 b, b>."""
     b = b.reshape(-1)
@@ -338,3 +486,63 @@ def largest_component(m):
     bf = np.asarray(m.bfaces, dtype=np.int64)
     kb = keep[bf[:, 0]]
     return m.verts[keep], new[te].astype(np.int32), new[bf[kb]].astype(np.int32), np.asarray(m.bface_kind)[kb]
+
+
+# ---- the solves the CG tests follow (tests/test_fem_cpu.py proves them, tests/test_gpu_fem_cg.py runs them on the kernels) -----------
+CG_LAM, CG_MU, CG_TRACTION = 0.7, 1.3, (0.0, 0.0, -0.01)
+CG_TRAJECTORY = ("2x2x2", "3x3x3", "cut")
+OVERFLOW_SCALE, OVERFLOW_DIRECTION = 1e160, (0.3, -0.2, 0.5)
+# name: (mesh, lam, mu, load, iterations before the ending)
+CG_ENDINGS = {"zero load": ("2x2x2", CG_LAM, CG_MU, "zero", 0), "nan load": ("2x2x2", CG_LAM, CG_MU, "nan", 0),
+              "pap after 0": ("2x2x2", -1.9, 1.0, "random", 0), "pap after 1": ("2x2x2", -1.2, 1.0, "random", 1),
+              "pap after 3": ("3x3x3", -1.0, 1.0, "random", 3), "overflow": ("2x2x2", CG_LAM, CG_MU, "overflow", 1),
+              "one free vertex 0.7": ("one tet", CG_LAM, CG_MU, "vertex", 1), "one free vertex -1.0": ("one tet", -1.0, 1.0, "vertex", 1),
+              "one free vertex -1.2": ("one tet", -1.2, 1.0, "vertex", 1), "one free vertex -1.9": ("one tet", -1.9, 1.0, "vertex", 1)}
+_cg_cache = {}
+
+
+def cg_load(kind, verts, bfaces, mask):
+    """The loads of CG_ENDINGS and of the trajectories ('traction'), [V, 3], zero at the masked vertices."""
+    nv = len(verts)
+    first_free = int(np.flatnonzero(~mask)[0])
+    if kind in ("traction", "nan"):
+        f = load(verts, bfaces, attributes(verts, bfaces) == 2, CG_TRACTION, mask)
+        if kind == "nan":
+            f[first_free, 1] = np.nan
+        return f
+    if kind == "random":
+        f = np.random.default_rng(5).standard_normal((nv, 3))
+        f[mask] = 0.0
+        return f
+    f = np.zeros((nv, 3))
+    if kind == "vertex":
+        f[first_free] = OVERFLOW_DIRECTION
+    elif kind == "overflow":            # one vertex: every product of <z, r> and <p, A p> is zero or of one sign, whatever the order
+        f[first_free] = OVERFLOW_SCALE * np.asarray(OVERFLOW_DIRECTION)
+    elif kind != "zero":
+        raise ValueError(kind)
+    return f
+
+
+def cg_problem(name):
+    """The solve `name` (of CG_TRAJECTORY or CG_ENDINGS) on the CPU meshes, with its four restatements: computed once, never changed.
+    dict: mesh (the four arrays), lam, mu, mask, f, A, Dinv, traces, q (cg_ratio_spread); for a trajectory also ref (spsolve), s
+    (cg_spread) and it_max, all up to k_max = the longest restatement + 2."""
+    if name in _cg_cache:
+        return _cg_cache[name]
+    if "meshes" not in _cg_cache:
+        _cg_cache["meshes"] = cpu_meshes()
+    mesh, lam, mu, kind, _ = CG_ENDINGS[name] if name in CG_ENDINGS else (name, CG_LAM, CG_MU, "traction", None)
+    v, t, bf, bk = _cg_cache["meshes"][mesh]
+    nv = len(v)
+    mask = held_vertices(t, geometry(v, t)[1], nv) | fixed_vertices(bf, clamped_faces(v, bf), nv)
+    f = cg_load(kind, v, bf, mask)
+    A, Dinv, traces = cg_variants(v, t, lam, mu, mask, f)
+    k_max = max(tr["it"] for tr in traces.values()) + 2
+    out = dict(name=name, mesh=(v, t, bf, bk), lam=lam, mu=mu, mask=mask, f=f, A=A, Dinv=Dinv, traces=traces, k_max=k_max,
+               q=cg_ratio_spread(traces, k_max))
+    if name in CG_TRAJECTORY:
+        out["ref"] = spsolve(A, f)
+        out["s"] = cg_spread(A, traces, out["ref"], k_max)
+    _cg_cache[name] = out
+    return out

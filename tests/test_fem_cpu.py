@@ -1,6 +1,7 @@
 """CPU: the oracle of the elasticity solver (tests/fem_numpy.py) proves itself -- symmetry, rigid-body motions, linear
 fields, the exact bar -- the MFEM reader, the dsdf_fem_* argument checks without a device, and the discrimination of every tolerance
-tests/test_gpu_fem.py uses: each wrong variant misses the truth by far more than the bound the GPU result is held to."""
+tests/test_gpu_fem.py and tests/test_gpu_fem_cg.py use: each wrong variant misses the truth by far more than the bound the GPU result
+is held to; the spread of the CG's four restatements, and every ending of the CG reached by the oracle on the inputs the GPU tests use."""
 import ctypes as C
 
 import numpy as np
@@ -171,6 +172,14 @@ def test_fem_argument_errors_come_before_any_launch():
     assert lib.dsdf_fem_load(P, 0, P, 50, P, P, N, t3, N, P, N) == bad and lib.dsdf_fem_load(P, 100, N, 50, P, P, N, t3, N, P, N) == bad
     assert lib.dsdf_fem_load(P, 100, P, 50, P, P, N, (C.c_double * 3)(0.0, float("inf"), 0.0), N, P, N) == bad
     assert lib.dsdf_fem_boundary_gradient(P, 100, P, 50, P, P, N, N, N) == bad and lib.dsdf_fem_boundary_gradient(P, 100, P, -1, P, P, N, P, N) == bad
+    # dsdf_fem_solve's own arguments: each refused, and the three outputs zeroed before the refusal
+    Q, nan, inf = C.c_void_p(0x2000), float("nan"), float("inf")
+    for f, u, rel_tol, max_iter, check_every in ((P, Q, -1.0, 10, 1), (P, Q, -1e-300, 10, 1), (P, Q, nan, 10, 1), (P, Q, inf, 10, 1),
+                                                 (P, Q, -inf, 10, 1), (P, Q, 1e-10, -1, 1), (P, Q, 1e-10, 10, 0), (P, Q, 1e-10, 10, -5),
+                                                 (P, P, 1e-10, 10, 1), (N, Q, 1e-10, 10, 1), (P, N, 1e-10, 10, 1)):
+        it, cv, ratio = C.c_int32(-3), C.c_int32(-3), C.c_double(-3.0)
+        rc = lib.dsdf_fem_solve(o, f, u, rel_tol, max_iter, check_every, C.byref(it), C.byref(cv), C.byref(ratio), P, big, N)
+        assert rc == bad and (it.value, cv.value, ratio.value) == (0, 0, 0.0), (rel_tol, max_iter, check_every)
 
 
 def test_linear_elasticity_needs_a_device_mesh(meshes):
@@ -227,3 +236,106 @@ def test_every_wrong_variant_misses_the_truth_by_far_more_than_the_gpu_bounds(me
         nfc = int(F.corner_counts(bf, nv).max())
         gbound = (2 * nfc + 2) * U * F.boundary_gradient(v, bf, absolute=True)
         assert (np.abs(g - gf) / np.maximum(gbound, 1e-300)).max() > 1e9, name
+
+
+# ---- the CG step by step: the restatements' spread, the wrong variants, and every ending (tests/test_gpu_fem_cg.py runs the kernels) ---
+def _window(traces):
+    its = [t["it"] for t in traces.values()]
+    return 0.9 * min(its) - 2, 1.1 * max(its) + 2
+
+
+@pytest.mark.parametrize("name", F.CG_TRAJECTORY)
+def test_cg_restatements_stay_together_and_every_wrong_variant_leaves_at_once(name):
+    pr = F.cg_problem(name)
+    A, ref, tr = pr["A"], pr["ref"], pr["traces"]
+    u, it, conv, ratio = F.pcg(A, pr["Dinv"], pr["f"])
+    base = tr["csr"]
+    assert u.tobytes() == base["x"].tobytes() and (it, conv, ratio) == (base["it"], base["conv"], base["ratio"])    # pcg_trace is pcg
+    assert all(t["conv"] for t in tr.values())
+    K = pr["k_max"]
+    s, q = pr["s"], pr["q"]
+    bs, bq = F.cg_iterate_bound(s), F.cg_ratio_bound(q)
+    err = [F.energy_distance(A, F.iterate(base, k), ref) for k in range(K + 1)]
+    ks = sorted({1, 2, 3, 5, 8, 13, 21, 34, 55, 89, K // 2, base["it"], K} & set(range(K + 1)))
+    print(f"{name}: iterations {[t['it'] for t in tr.values()]}; error {err[0]:.2e} -> {err[base['it']]:.2e}")
+    print("  k: spread s_k / ratio spread q_k / error: " + "; ".join(f"{k}: {s[k]:.1e} / {q[k]:.1e} / {err[k]:.1e}" for k in ks))
+    # the energy-norm error of CG falls at every step: where it stands above 1e3 x the GPU bound the oracle's own must not rise
+    assert all(err[k + 1] <= err[k] for k in range(K) if err[k] > 1e3 * bs[k]), name
+    lo, hi = _window(tr)
+    for w in F.CG_WRONG:
+        wt = F.pcg_trace(A, pr["Dinv"], pr["f"], wrong=w, max_iter=int(hi) + 1)       # past the window is all that is asked
+        k = next(k for k in range(1, 4) if F.iterate(wt, k).tobytes() != F.iterate(base, k).tobytes())
+        assert k == (2 if w in ("steepest", "dir_from_r") else 3)           # beta_1 enters x_2; the rho before rho_1 is rho0 in all three
+        miss = F.energy_norm(A, F.iterate(wt, k) - F.iterate(base, k)) / F.energy_norm(A, ref) / bs[k]
+        miss_q = abs(wt["ratios"][k] - base["ratios"][k]) / base["ratios"][k] / bq[k]
+        print(f"  {w}: {wt['it']} iterations, converged {wt['conv']}; iterate {k} misses by {miss:.2e} x the GPU bound, its ratio by {miss_q:.2e} x")
+        assert miss > 1e9 and miss_q > 1e9, (name, w, miss, miss_q)
+        assert not (wt["conv"] and lo <= wt["it"] <= hi), (name, w, wt["it"])       # ... and its count, if it has one, falls outside
+
+
+def test_pcg_trace_takes_the_operator_as_a_callable_and_keeps_every_scalar():
+    pr = F.cg_problem("3x3x3")
+    A, f = pr["A"], pr["f"]
+    a, b = pr["traces"]["csr"], F.pcg_trace(lambda x: A @ x, pr["Dinv"], f)
+    assert a["x"].tobytes() == b["x"].tobytes() and a["scal"] == b["scal"] and len(a["scal"]) == a["it"] == len(a["xs"]) - 1
+    rho, x, p = a["rho0"], np.zeros(A.shape[0]), a["ps"][0]
+    for k, (rn, alpha, beta, pap) in enumerate(a["scal"]):                  # the recorded scalars rebuild the iterates
+        assert pap == a["paps"][k] and alpha == rho / pap and beta == rn / rho and a["ratios"][k + 1] == rn / a["rho0"]
+        x = x + alpha * a["ps"][k]
+        assert x.tobytes() == a["xs"][k + 1].tobytes()
+        rho = rn
+    for k in (0, 1, 5, a["it"]):                                            # max_iter = k returns iterate k
+        c = F.pcg_trace(A, pr["Dinv"], f, max_iter=k)
+        assert c["it"] == k and c["x"].tobytes() == a["xs"][k].tobytes() and c["conv"] == (k == a["it"])
+    assert F.iterate(a, a["it"] + 7).tobytes() == a["x"].tobytes()
+
+
+@pytest.mark.parametrize("name", list(F.CG_ENDINGS))
+def test_the_oracle_reaches_every_ending_by_a_margin(name):
+    pr = F.cg_problem(name)
+    mesh, lam, mu, kind, j = F.CG_ENDINGS[name]
+    assert mu > 0 and lam + 2 * mu > 0                                      # dsdf_fem_* accepts the material
+    tr, A, mask = pr["traces"], pr["A"], pr["mask"]
+    v, t, bf, _ = pr["mesh"]
+    triples = [(x["it"], x["conv"], x["ratio"]) for x in tr.values()]
+    print(f"{name}: {triples}")
+    if kind == "zero":
+        assert all(x == (0, True, 0.0) for x in triples) and all((x["x"] == 0).all() for x in tr.values())
+    elif kind == "nan":
+        assert np.isnan(pr["f"][~mask]).sum() == 1 and not np.isnan(pr["f"][mask]).any()
+        assert all(x == (0, False, 0.0) for x in triples) and all((x["x"] == 0).all() for x in tr.values())
+    elif kind == "vertex":
+        # one free vertex: block Jacobi is the inverse.  alpha A p = r (1 + d), |d| <= c U cond(D) for the c <= 64 roundings through
+        # the operator, the preconditioner and the update, so rho' / rho0 <= cond(D) (c U cond(D))^2
+        assert (~mask).sum() == 1
+        cond = np.linalg.cond(np.linalg.inv(pr["Dinv"][~mask][0]))
+        bound = cond * (64 * U * cond) ** 2
+        print(f"  cond(D) {cond:.3f}, ratio bound {bound:.2e}")
+        assert all(x[0] == 1 and x[1] and 0.0 <= x[2] <= bound for x in triples) and bound < 1e-20
+    elif kind == "random":
+        assert 3 * lam + 2 * mu < 0                                          # K is indefinite ...
+        blocks = np.linalg.eigvalsh(F.sym3(F.diag_blocks(A))).min()
+        assert blocks > 0.2                                                  # ... its diagonal blocks are not
+        Aabs = F.masked(F.assemble(v, t, lam, mu, absolute=True), mask)
+        for k, x in tr.items():
+            assert (x["it"], x["conv"]) == (j, False) and len(x["paps"]) == j + 1, (name, k)
+            margin = [pap / (U * float(np.abs(p) @ (Aabs @ np.abs(p)))) for pap, p in zip(x["paps"], x["ps"])]
+            print(f"  {k}: p.Ap / (U |p|^T |A| |p|) = {[f'{m:.2e}' for m in margin]}, smallest block eigenvalue {blocks:.3f}")
+            assert all(m > 1e6 for m in margin[:-1]) and margin[-1] < -1e6, (name, k, margin)      # rounding cannot move the stop
+        assert triples[0][2] == 1.0 if j == 0 else abs(triples[0][2] - 1.0) > 0.1
+    elif kind == "overflow":
+        # at scale 1 the three products of <z, r> and of <p, A p> at the loaded vertex are positive and of order 0.01 to 1; everywhere
+        # else p is exactly 0.  Times 1e320 each of them is +inf (the largest double is 1.8e308) in any order and with any contraction
+        one = F.cg_variants(v, t, lam, mu, mask, pr["f"] / F.OVERFLOW_SCALE, max_iter=1)[2]["csr"]
+        p = one["ps"][0].reshape(-1, 3)
+        ap = (A @ p.reshape(-1)).reshape(-1, 3)
+        loaded = np.abs(pr["f"]).sum(1) > 0
+        assert loaded.sum() == 1 and (p[~loaded] == 0).all() and np.isfinite(pr["f"]).all()
+        terms = np.concatenate([(p * pr["f"] / F.OVERFLOW_SCALE)[loaded], (p * ap)[loaded]]).reshape(-1)
+        print(f"  products at scale 1: {terms}; the load's scale {F.OVERFLOW_SCALE:g} enters each twice")
+        assert (terms > 1e-3).all() and np.abs(A @ p.reshape(-1)).max() * F.OVERFLOW_SCALE < 1e300       # A p itself stays finite
+        for k, x in tr.items():
+            assert x["rho0"] == np.inf and x["paps"] == [np.inf] and (x["it"], x["conv"]) == (1, False) and np.isnan(x["ratio"]), k
+            assert np.isnan(x["x"]).all()
+    else:
+        raise AssertionError(kind)
