@@ -48,7 +48,7 @@ class DeepSDFMesh:
         field = BSplineField(degrees, knots, np.zeros((n_initial, self.latent.shape[1])))      # zero codes at every control point
         field.uniform_refine(self.options["refinement"])
         self.latent_vec_interpolation = field
-        self.surface_mesh = self.jacobian = self.diff = self.volume_mesh = None
+        self.surface_mesh = self.jacobian = self.diff = self.volume_mesh = self.volume_diff = None
         self.logger = logging.getLogger(__name__)
         self.logger.debug(f"Initialied latent vector with {field.control_mesh_resolutions} control points")
 
@@ -111,7 +111,9 @@ class DeepSDFMesh:
         """The tetrahedral mesh of the solid the surface bounds, after generate_surface_mesh: the capped grid the surface came from
         (``diff.grid``) meshed at the voxel size, in the surface's coordinates ((v - voxel_size) / 2 in float64, x stretched by 2);
         only the largest solid component when ``remove_orphans``.  Sets and returns ``volume_mesh`` (a TetMesh); its axis-class
-        boundary vertices are the surface's vertices bit for bit.  t_clamp: deepsdf_amd.tetmesh.tetrahedralize."""
+        boundary vertices are the surface's vertices bit for bit.  t_clamp: deepsdf_amd.tetmesh.tetrahedralize.  Also sets
+        ``volume_diff`` (a deepsdf_amd.mesh.VolumeMeshDiff: the derivative of every moving vertex of the volume mesh, unstretched;
+        get_dTheta and shape_gradient apply the stretch)."""
         self._mesh()
         vs = self.diff.voxel_size
         m = tetrahedralize(self.diff.grid, 0.0, vs, t_clamp=t_clamp, keep_largest=bool(self.options["remove_orphans"]),
@@ -120,7 +122,52 @@ class DeepSDFMesh:
         verts = (m.verts.double() - torch.tensor(vs, dtype=torch.float64, device=dev)) / 2      # microstructure_mesh_diff's transform
         m.verts = verts * torch.tensor(STRETCH, dtype=torch.float64, device=dev)                 # SurfaceMesh.from_diff's stretch
         self.volume_mesh = m
+        self.volume_diff = self.diff.for_tetmesh(m, t_clamp)
         return m
+
+    def _volume(self):
+        if self.volume_mesh is None or self.volume_diff is None:
+            raise RuntimeError("call generate_volume_mesh() first")
+        return self.volume_mesh, self.volume_diff
+
+    def volume_normals(self):
+        """[V_vol, 3] fp32: the vertex normals of the volume mesh's boundary (zero at interior vertices)."""
+        return self._volume()[0].boundary_surface().vertex_normals()
+
+    def get_dTheta(self):
+        """The reference's get_dTheta (analysis/geometry.py:176-197) on the volume mesh: [V_vol, 3, ncp * L] fp32 on the device,
+        every column of the Jacobian of every vertex stretched by STRETCH, entries outside [-CLIP, CLIP] zeroed, projected onto the
+        vertex normal of ``volume_mesh.boundary_surface()``.  Rows of vertices that do not move (grid vertices, vertices the clamp
+        holds) are zero.  Raises MemoryError, stating the size, when the array would not fit the device."""
+        mesh, vd = self._volume()
+        V, R = mesh.n_verts, vd.n_control_points * vd.latent_size
+        need = 4 * V * 3 * R
+        free = torch.cuda.mem_get_info(vd.device)[0]
+        if need + 4 * vd.moving.numel() * 3 * R > free:
+            raise MemoryError(f"dTheta [{V}, 3, {R}] fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB) besides the moving vertices' "
+                              f"{4 * vd.moving.numel() * 3 * R}, the device has {free} bytes free: use shape_gradient, or a coarser grid")
+        normals = self.volume_normals()
+        n_zero = int((normals[vd.moving.long()] == 0).all(1).sum())
+        if n_zero > 0:
+            self.logger.debug(f"{n_zero} 0-Normal vectors detected")
+        out = torch.zeros(V, 3, R, dtype=torch.float32, device=vd.device)
+        out[vd.moving.long()] = vd.dtheta_moving(normals, STRETCH, CLIP)
+        return out
+
+    def shape_gradient(self, grad_verts, project=True):
+        """grad_verts [V_vol, 3] -> [ncp, L] fp32 on the device: sum_v grad_verts[v] . dTheta[v, :, (k, l)] without the dense array.
+        project=True: the adjoint of get_dTheta with clip = 0, i.e. the vjp of STRETCH * n (n . g) / (n . n); project=False: the
+        adjoint of the plain stretched Jacobian, the vjp of STRETCH * g.  This path has NO outlier clipping: the reference's rule
+        zeroes single entries of the dense Jacobian, which the adjoint never forms."""
+        mesh, vd = self._volume()
+        g = torch.as_tensor(grad_verts).to(vd.device, torch.float32)
+        if g.shape != (mesh.n_verts, 3):
+            raise ValueError(f"grad_verts must be [{mesh.n_verts}, 3], got {tuple(g.shape)}")
+        if project:
+            n = self.volume_normals()
+            nn = (n * n).sum(1, keepdim=True)
+            g = torch.where(nn > 0, n * ((n * g).sum(1, keepdim=True) / nn.clamp_min(1e-30)), torch.zeros_like(g))
+        return vd.vjp(g * torch.tensor(STRETCH, dtype=torch.float32, device=vd.device))
 
     def export_mfem_mesh(self, filename):
         """Write ``volume_mesh`` as an MFEM mesh v1.0 file with the reference's boundary attributes (1: x = 0, 2: the top in z,

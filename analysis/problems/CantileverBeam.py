@@ -86,3 +86,19 @@ class CantileverBeam:
         s = self.ElasticitySolver
         vol_der = None if dTheta is None else self._contract(s.volume_shape_gradient(), dTheta)
         return s.volume(), np.array(vol_der)
+
+    def compute_volume_gradient(self, geometry):
+        """d volume / d control points [ncp * L] fp64 through ``geometry.shape_gradient`` (a DeepSDFMesh whose volume_mesh is this
+        problem's mesh): the adjoint of compute_volume(dTheta)[1] with dTheta = geometry.get_dTheta(), without the dense array and
+        without its outlier clipping."""
+        if self.ElasticitySolver is None:
+            raise ValueError("No solver found. Call set_up first.")
+        g = geometry.shape_gradient(self.ElasticitySolver.volume_shape_gradient())
+        return g.double().reshape(-1).cpu().numpy()
+
+    def compute_compliance_gradient(self, geometry, nodal="mean"):
+        """d compliance / d control points [ncp * L] fp64, the adjoint counterpart of compute_compliance(dTheta)[1]."""
+        if self.u_data is None:
+            raise ValueError("No solution found. Compute solution first to get Compliance.")
+        g = geometry.shape_gradient(self.ElasticitySolver.compliance_shape_gradient(nodal))
+        return g.double().reshape(-1).cpu().numpy()

@@ -83,6 +83,12 @@ class DsdfMsdBand(C.Structure):
                 ("L", C.c_int32)]
 
 
+class DsdfVdMesh(C.Structure):
+    _fields_ = [("grid", C.c_void_p), ("vert_point", C.c_void_p), ("vert_class", C.c_void_p), ("vert_index", C.c_void_p),
+                ("band_of", C.c_void_p), ("n_verts", C.c_int64), ("n_moving", C.c_int64), ("dims", C.c_int32 * 3),
+                ("scale", C.c_float * 3), ("level", C.c_float), ("t_clamp", C.c_float)]
+
+
 class DsdfSgPlan(C.Structure):
     _fields_ = [("blocks", C.c_int32 * 3), ("n_blocks", C.c_int64), ("n_coarse", C.c_int64), ("n_points", C.c_int64),
                 ("ws_bytes", C.c_size_t), ("state_offset", C.c_size_t), ("have_offset", C.c_size_t)]
@@ -171,6 +177,10 @@ PROTOTYPES = {
     "dsdf_msd_jacobian": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _I32, _P, _P, _P],
     "dsdf_msd_jvp": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P],
     "dsdf_msd_vjp": [C.POINTER(DsdfMsdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P, _SZ, _P],
+    "dsdf_vd_vjp_workspace_bytes": [_I64, _I64, _I32, C.POINTER(_SZ), C.POINTER(_I32)],
+    "dsdf_vd_jvp": [C.POINTER(DsdfVdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P],
+    "dsdf_vd_vjp": [C.POINTER(DsdfVdMesh), C.POINTER(DsdfMsdBand), _P, _P, _P, _SZ, _P],
+    "dsdf_vd_dtheta": [C.POINTER(DsdfVdMesh), C.POINTER(DsdfMsdBand), _P, C.POINTER(_F), _F, _P, _P],
     "dsdf_nn_plan": [_I64, _I64, C.POINTER(_SZ), C.POINTER(_I32)],
     "dsdf_nn_query": [_P, _I64, _P, _I64, _P, _P, _P, _SZ, _P],
     "dsdf_mean_f64": [_P, _I64, _P, _P, _SZ, _P],

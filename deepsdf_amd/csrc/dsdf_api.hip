@@ -26,6 +26,7 @@
 #include "meshsdf.hpp"
 #include "msgrid.hpp"
 #include "msdiff.hpp"
+#include "voldiff.hpp"
 #include "pointset.hpp"
 #include "meshtopo.hpp"
 #include "sparsegrid.hpp"
@@ -2698,6 +2699,112 @@ int dsdf_msd_vjp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* 
   hipLaunchKernelGGL(msd_vjp_sum_kernel, dim3((unsigned)((P.per + MSD_BLOCK - 1) / MSD_BLOCK)), dim3(MSD_BLOCK), 0, st, (const float*)ws,
                      P.n_parts, P.per, grad_cp);
   LAUNCH_OK("msd_vjp_sum_kernel");
+  return 0;
+}
+
+// ---- volume mesh derivatives (voldiff.hpp) -------------------------------------------------------------------
+namespace {
+int vd_plan(int64_t n_moving, int64_t ncp, int32_t L, MsdPlan* P, WsTable* rec = nullptr) {
+  if (n_moving < 0 || n_moving > INT32_MAX) return fail(DSDF_E_INVALID, "volume derivative: %lld moving vertices (0 .. %d)", (long long)n_moving, INT32_MAX);
+  if (L < 1) return fail(DSDF_E_INVALID, "volume derivative: %d latent columns", L);
+  if (ncp < 1 || ncp * (int64_t)L > INT32_MAX)
+    return fail(DSDF_E_INVALID, "volume derivative: control net of %lld x %d floats (1 .. %d)", (long long)ncp, L, INT32_MAX);
+  P->per = ncp * L;
+  P->n_parts = (int32_t)((n_moving + MSD_VJP_VERTS - 1) / MSD_VJP_VERTS);
+  P->n_tiles = (int32_t)((P->per + MSD_VJP_TILE - 1) / MSD_VJP_TILE);
+  if (P->n_tiles > 65535) return fail(DSDF_E_INVALID, "volume derivative: control net of %lld floats (the adjoint takes at most %lld)", (long long)P->per, 65535ll * MSD_VJP_TILE);
+  P->part = (size_t)P->n_parts * (size_t)P->per * 4;
+  WsCarver c(rec);
+  c.take("vd_vjp_part", -1, P->part);
+  P->ws = c.finish(c.o);
+  return 0;
+}
+
+// grid, scale and band through msd_setup (the same checks and messages), then the volume mesh's own arrays
+int vd_setup(const DsdfVdMesh* mesh, const DsdfMsdBand* band, VdMesh* M, MsdBand* B) {
+  if (!mesh || !band) return fail(DSDF_E_INVALID, "volume derivative: NULL mesh or band");
+  if (mesh->n_moving < 0 || mesh->n_moving > INT32_MAX)
+    return fail(DSDF_E_INVALID, "volume derivative: %lld moving vertices (0 .. %d)", (long long)mesh->n_moving, INT32_MAX);
+  if (!(mesh->t_clamp >= 0.f && mesh->t_clamp < 0.5f)) return fail(DSDF_E_INVALID, "volume derivative: t_clamp %g outside [0, 0.5)", (double)mesh->t_clamp);
+  DsdfMsdMesh m;
+  m.grid = mesh->grid; m.edge_point = mesh->vert_point; m.edge_axis = mesh->vert_class; m.band_of = mesh->band_of;
+  m.n_verts = mesh->n_verts; m.level = mesh->level;
+  for (int a = 0; a < 3; ++a) { m.dims[a] = mesh->dims[a]; m.scale[a] = mesh->scale[a]; }
+  MsdMesh S;
+  TRY(msd_setup(&m, band, &S, B));
+  if (mesh->n_moving > 0 && (!mesh->vert_index || mesh->n_verts == 0))
+    return fail(DSDF_E_INVALID, "volume derivative: NULL vert_index, or moving vertices of an empty mesh");
+  M->grid = S.grid; M->vert_point = S.edge_point; M->vert_class = S.edge_axis; M->vert_index = mesh->vert_index; M->band_of = S.band_of;
+  M->npts = S.npts; M->V = S.V; M->Vm = mesh->n_moving; M->level = S.level; M->t_clamp = mesh->t_clamp;
+  for (int a = 0; a < 3; ++a) { M->stride[a] = S.stride[a]; M->dims[a] = mesh->dims[a]; M->scale[a] = S.scale[a]; }
+  return 0;
+}
+}  // namespace
+
+int dsdf_vd_vjp_workspace_bytes(int64_t n_moving, int64_t n_control_points, int32_t L, size_t* bytes, int32_t* n_parts) {
+  MsdPlan P;
+  TRY(vd_plan(n_moving, n_control_points, L, &P, &t_last_plan));
+  if (!bytes && !n_parts) return fail(DSDF_E_INVALID, "volume derivative: every output is NULL");
+  if (bytes) *bytes = P.ws;
+  if (n_parts) *n_parts = P.n_parts;
+  return 0;
+}
+
+int dsdf_vd_jvp(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* d_cp, float* d_verts, void* stream) {
+  VdMesh M; MsdBand B;
+  TRY(vd_setup(mesh, band, &M, &B));
+  if (M.V == 0) return 0;
+  if (!d_verts) return fail(DSDF_E_INVALID, "volume derivative: NULL d_verts");
+  if (M.Vm > 0 && !d_cp) return fail(DSDF_E_INVALID, "volume derivative: NULL d_cp");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_OK(hipMemsetAsync(d_verts, 0, (size_t)M.V * 3 * sizeof(float), st));
+  if (M.Vm == 0) return 0;
+  const int per = MSD_BLOCK / 64;
+  hipLaunchKernelGGL(vd_jvp_kernel, dim3((unsigned)((M.Vm + per - 1) / per)), dim3(MSD_BLOCK), 0, st, M, B, d_cp, d_verts);
+  LAUNCH_OK("vd_jvp_kernel");
+  return 0;
+}
+
+int dsdf_vd_vjp(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* grad_verts, float* grad_cp, void* ws, size_t ws_bytes,
+                void* stream) {
+  VdMesh M; MsdBand B;
+  TRY(vd_setup(mesh, band, &M, &B));
+  MsdPlan P;
+  TRY(vd_plan(M.Vm, B.ncp_total, B.L, &P, &t_last_plan));
+  if (!grad_cp) return fail(DSDF_E_INVALID, "volume derivative: NULL grad_cp");
+  if (M.Vm > 0 && (!grad_verts || !ws)) return fail(DSDF_E_INVALID, "volume derivative: NULL grad_verts or workspace");
+  if (M.Vm > 0 && ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "volume derivative: workspace %zu < %zu bytes", ws_bytes, P.ws);
+  hipStream_t st = (hipStream_t)stream;
+  if (P.n_parts > 0) {
+    hipLaunchKernelGGL(vd_vjp_part_kernel, dim3((unsigned)P.n_parts, (unsigned)P.n_tiles), dim3(MSD_BLOCK), 0, st, M, B, grad_verts,
+                       (float*)ws);
+    LAUNCH_OK("vd_vjp_part_kernel");
+  }
+  hipLaunchKernelGGL(msd_vjp_sum_kernel, dim3((unsigned)((P.per + MSD_BLOCK - 1) / MSD_BLOCK)), dim3(MSD_BLOCK), 0, st, (const float*)ws,
+                     P.n_parts, P.per, grad_cp);
+  LAUNCH_OK("msd_vjp_sum_kernel");
+  return 0;
+}
+
+int dsdf_vd_dtheta(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* normals, const float* stretch, float clip, float* out,
+                   void* stream) {
+  VdMesh M; MsdBand B;
+  TRY(vd_setup(mesh, band, &M, &B));
+  if (!stretch) return fail(DSDF_E_INVALID, "volume derivative: NULL stretch");
+  VdProject P;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(stretch[a])) return fail(DSDF_E_INVALID, "volume derivative: stretch %d is not finite", a);
+    P.stretch[a] = stretch[a];
+  }
+  if (std::isnan(clip)) return fail(DSDF_E_INVALID, "volume derivative: clip is NaN");
+  P.clip = clip;
+  if (M.Vm == 0) return 0;
+  if (!normals || !out) return fail(DSDF_E_INVALID, "volume derivative: NULL normals or out");
+  const int64_t R = (int64_t)B.ncp_total * B.L;
+  const int vpw = R >= VD_DENSE_COLS ? 1 : (int)std::min<int64_t>(VD_DENSE_VERTS, VD_DENSE_COLS / R);
+  hipLaunchKernelGGL(vd_dtheta_kernel, dim3((unsigned)((M.Vm + vpw - 1) / vpw)), dim3(MSD_BLOCK), 0, (hipStream_t)stream, M, B, normals, P,
+                     out, vpw);
+  LAUNCH_OK("vd_dtheta_kernel");
   return 0;
 }
 

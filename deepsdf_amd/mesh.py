@@ -14,6 +14,8 @@ convert_sdf_samples_to_ply :86-155) with every step on the GPU.
                             form (csrc/msdiff.hpp) from one input-gradient pass over the band of grid points that carry a vertex
     volume tetrahedralize / solid_components / TetMesh (deepsdf_amd/tetmesh.py, re-exported here): the solid {sdf < level} of the
                             same grid as a conforming tetrahedral mesh with its boundary triangles (csrc/tetmesh.hpp)
+           MicrostructureMeshDiff.for_tetmesh / VolumeMeshDiff: d vertices / d control points of every moving vertex of that mesh,
+                            the face and body diagonals included, on a band of its own (csrc/voldiff.hpp)
 
     sparse follow_surface   surface following on blocks of the same dense grid (csrc/sparsegrid.hpp): the coarse lattice
                             is decoded, blocks near the surface are seeded and grown across mixed-sign faces, only their points
@@ -719,10 +721,18 @@ class MicrostructureMeshDiff:
         self._degrees = [int(d) for d in field.degrees]
         self._n_cp = [int(n) for n in field.control_mesh_resolutions]
         self._scale = scale
+        self._rows_of = None                                # microstructure_mesh_diff: band -> its rows, for for_tetmesh
 
     @property
     def device(self):
         return self.grid.device
+
+    def for_tetmesh(self, tet, t_clamp=0.0):
+        """-> VolumeMeshDiff: the derivative of every moving vertex of `tet`, a TetMesh made from self.grid with
+        tetrahedralize(..., t_clamp=t_clamp, return_edges=True).  Grid values are read from self.grid: with keep_largest the mesh
+        came from a grid whose dropped points were overwritten with the level, and no crossing edge of it has a dropped endpoint,
+        so self.grid holds the values both meshes used.  Decodes the volume mesh's own band (one more pass of the band loop)."""
+        return _volume_mesh_diff(self, tet, t_clamp)
 
     def _structs(self):
         m, b = _lib.DsdfMsdMesh(), _lib.DsdfMsdBand()
@@ -824,6 +834,23 @@ def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_b
         verts = (verts.double() - vs) / 2
         stride = torch.tensor([dims[1] * dims[2], dims[2], 1], dtype=torch.int64, device=device)
         band = torch.unique(torch.cat([edge_point, edge_point + stride[edge_axis.long()]]))      # sorted
+
+        def rows_of(band):
+            return _band_rows(band, dec, hip, field, tiling, n, max_batch, raw, grid)
+        band_of, G, weights, base, mask = rows_of(band)
+    scale = [float(np.float32(v / 2)) for v in voxel_size]
+    d = MicrostructureMeshDiff(verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale,
+                               voxel_size)
+    d._rows_of = rows_of                                   # for_tetmesh: the volume mesh's band goes through the same loop
+    return d
+
+
+def _band_rows(band, dec, hip, field, tiling, n, max_batch, raw, grid):
+    """band [nb] sorted grid indices -> (band_of [npts] int32, G [nb, L], weights [nb, 64], base [nb], mask [nb] uint8): per chunk of
+    max_batch band points the rows at the band indices, the decoder's forward and its input gradient; mask = inside and capped
+    value == raw value (microstructure_mesh_diff's band loop; the volume mesh's band runs it again on its own points)."""
+    device, npts, L = raw.device, raw.numel(), int(field.latent_size)
+    with torch.cuda.device(device):
         nb = band.numel()
         band_of = torch.full((npts,), -1, dtype=torch.int32, device=device)
         band_of[band] = torch.arange(nb, dtype=torch.int32, device=device)
@@ -848,9 +875,134 @@ def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_b
                     G[b:e] = torch.autograd.grad(y.sum(), x)[0][:, :L]
         flat_raw, flat = raw.view(-1), grid.view(-1)
         mask = ((base >= 0) & (flat[band] == flat_raw[band])).to(torch.uint8)
-    scale = [float(np.float32(v / 2)) for v in voxel_size]
-    return MicrostructureMeshDiff(verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale,
-                                  voxel_size)
+    return band_of, G, weights, base, mask
+
+
+class VolumeMeshDiff:
+    """The derivative of a volume mesh's vertices with respect to the spline's control points (csrc/voldiff.hpp, dsdf_vd_*;
+    DESIGN 4.22): every class >= 1 vertex of tetmesh.tetrahedralize's mesh -- the marching-cubes vertices and those on the face and
+    body diagonals -- moves along its edge; grid vertices do not.  Built by MicrostructureMeshDiff.for_tetmesh.
+
+    moving [Vm] int32: the ids of the class >= 1 vertices, ascending (a vertex the clamp holds is in the list and has a zero
+    derivative).  band: the sorted unique endpoints of their edges, with its own G / weights / base / mask: an endpoint of a
+    crossing diagonal need not be an endpoint of a crossing axis edge, so the surface's band is not enough.  Unstretched, in the
+    coordinates of MicrostructureMeshDiff.verts (scale = voxel_size / 2)."""
+
+    def __init__(self, diff, tet, t_clamp, band, band_of, G, weights, base, mask):
+        self.diff, self.t_clamp = diff, float(t_clamp)
+        self.grid = diff.grid
+        self.vert_point, self.vert_class = tet.vert_point, tet.vert_class
+        self.n_verts = int(tet.verts.shape[0])
+        self.moving = torch.nonzero(self.vert_class > 0).reshape(-1).to(torch.int32)          # ascending
+        self.band, self.band_of, self.G, self.weights, self.base, self.mask = band, band_of, G, weights, base, mask
+        self.n_control_points, self.latent_size = diff.n_control_points, diff.latent_size
+
+    @property
+    def device(self):
+        return self.grid.device
+
+    def _structs(self, index=None):
+        index = self.moving if index is None else index
+        m, b = _lib.DsdfVdMesh(), _lib.DsdfMsdBand()
+        m.grid, m.vert_point, m.vert_class, m.vert_index, m.band_of = (t.data_ptr() for t in (self.grid, self.vert_point, self.vert_class,
+                                                                                            index, self.band_of))
+        m.n_verts, m.n_moving, m.level, m.t_clamp = self.n_verts, index.numel(), 0.0, self.t_clamp
+        b.G, b.weights, b.base, b.mask = (t.data_ptr() for t in (self.G, self.weights, self.base, self.mask))
+        b.n_band, b.ld_g, b.L = self.G.shape[0], self.G.stride(0) if self.G.shape[0] > 0 else self.latent_size, self.latent_size
+        for a in range(3):
+            m.dims[a], m.scale[a] = self.grid.shape[a], self.diff._scale[a]
+            b.degree[a], b.n_cp[a] = self.diff._degrees[a], self.diff._n_cp[a]
+        return m, b
+
+    def vjp_plan(self):
+        """(scratch bytes, partial sums of the first stage) of vjp (dsdf_vd_vjp_workspace_bytes)."""
+        nbytes, parts = C.c_size_t(), C.c_int32()
+        _lib.check(_lib.lib().dsdf_vd_vjp_workspace_bytes(self.moving.numel(), self.n_control_points, self.latent_size,
+                                                          C.byref(nbytes), C.byref(parts)))
+        return nbytes.value, parts.value
+
+    def vjp(self, grad_verts):
+        """grad_verts [V, 3] -> grad_cp [ncp, L] fp32 = sum_v sum_b grad_verts[v, b] * J[v, b]: a fixed-order two-stage sum over
+        the moving vertices; rows of grid vertices are never read."""
+        gv = torch.as_tensor(grad_verts).to(self.device, torch.float32).contiguous()
+        if gv.shape != (self.n_verts, 3):
+            raise ValueError(f"grad_verts must be [{self.n_verts}, 3], got {tuple(gv.shape)}")
+        with torch.cuda.device(self.device):
+            ws = torch.empty(max(self.vjp_plan()[0], 256), dtype=torch.uint8, device=self.device)
+            out = torch.empty(self.n_control_points, self.latent_size, dtype=torch.float32, device=self.device)
+            m, b = self._structs()
+            _lib.check(_lib.lib().dsdf_vd_vjp(C.byref(m), C.byref(b), _lib.ptr(gv), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream()))
+        return out
+
+    def jvp(self, d_cp):
+        """d_cp [ncp, L] -> d_verts [V, 3] fp32: every flagged coordinate of a moving vertex, zero everywhere else."""
+        d = torch.as_tensor(d_cp).to(self.device, torch.float32).contiguous()
+        if d.shape != (self.n_control_points, self.latent_size):
+            raise ValueError(f"d_cp must be [{self.n_control_points}, {self.latent_size}], got {tuple(d.shape)}")
+        with torch.cuda.device(self.device):
+            out = torch.empty(self.n_verts, 3, dtype=torch.float32, device=self.device)
+            m, b = self._structs()
+            _lib.check(_lib.lib().dsdf_vd_jvp(C.byref(m), C.byref(b), _lib.ptr(d), _lib.ptr(out), _lib.stream()))
+        return out
+
+    def dtheta_moving(self, normals, stretch=(1.0, 1.0, 1.0), clip=0.0):
+        """[Vm, 3, ncp * L] fp32: the (stretched, clipped) Jacobian of every moving vertex projected onto its normal
+        (dsdf_vd_dtheta); normals [V, 3].  Raises MemoryError, stating the size, when the array would not fit the device."""
+        n = torch.as_tensor(normals).to(self.device, torch.float32).contiguous()
+        if n.shape != (self.n_verts, 3):
+            raise ValueError(f"normals must be [{self.n_verts}, 3], got {tuple(n.shape)}")
+        Vm, R = self.moving.numel(), self.n_control_points * self.latent_size
+        need = 4 * Vm * 3 * R
+        free = _free_device_memory(self.device)
+        if need > free:
+            raise MemoryError(f"dtheta [{Vm}, 3, {R}] fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB), the device has {free} bytes "
+                              f"free: use vjp / jvp, or a coarser grid")
+        with torch.cuda.device(self.device):
+            out = torch.empty(Vm, 3, R, dtype=torch.float32, device=self.device)
+            m, b = self._structs()
+            st = (C.c_float * 3)(*[float(s) for s in stretch])
+            _lib.check(_lib.lib().dsdf_vd_dtheta(C.byref(m), C.byref(b), _lib.ptr(n), st, float(clip), _lib.ptr(out), _lib.stream()))
+        return out
+
+    def jacobian(self):
+        """[V, 3, ncp, L] fp32, for small meshes: one tangent (jvp) per column, so ncp * L launches.  Raises MemoryError, stating
+        the size, when the array would not fit the free device memory."""
+        V, ncp, L = self.n_verts, self.n_control_points, self.latent_size
+        need = 4 * V * 3 * ncp * L
+        free = _free_device_memory(self.device)
+        if need > free:
+            raise MemoryError(f"the Jacobian {[V, 3, ncp, L]} fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB), the device has {free} "
+                              f"bytes free: use vjp / jvp")
+        jac = torch.empty(V, 3, ncp * L, dtype=torch.float32, device=self.device)
+        unit = torch.zeros(ncp * L, dtype=torch.float32, device=self.device)
+        for r in range(ncp * L):
+            unit[r] = 1.0
+            jac[:, :, r] = self.jvp(unit.view(ncp, L))
+            unit[r] = 0.0
+        return jac.view(V, 3, ncp, L)
+
+
+def _volume_mesh_diff(diff, tet, t_clamp=0.0):
+    if tet.vert_point is None or tet.vert_class is None:
+        raise ValueError("the TetMesh carries no vertex edges: build it with tetrahedralize(..., return_edges=True)")
+    if diff._rows_of is None:
+        raise ValueError("this MicrostructureMeshDiff cannot decode a band: build it with microstructure_mesh_diff")
+    t_clamp = float(t_clamp)
+    if not 0.0 <= t_clamp < 0.5:
+        raise ValueError(f"t_clamp must lie in [0, 0.5), got {t_clamp}")
+    device = diff.device
+    tet = tet.to(device)
+    dims = list(diff.grid.shape)
+    with torch.cuda.device(device):
+        c = tet.vert_class.long()
+        mv = c > 0
+        p, c = tet.vert_point[mv], c[mv]
+        q = p + (c & 1) * (dims[1] * dims[2]) + ((c >> 1) & 1) * dims[2] + ((c >> 2) & 1)
+        band = torch.unique(torch.cat([p, q]))                                                  # sorted
+        if band.numel() and (int(band[0]) < 0 or int(band[-1]) >= diff.grid.numel()):
+            raise ValueError("the TetMesh's vertex edges leave the grid of this MicrostructureMeshDiff")
+        band_of, G, weights, base, mask = diff._rows_of(band)
+    return VolumeMeshDiff(diff, tet, t_clamp, band, band_of, G, weights, base, mask)
 
 
 def create_mesh_microstructure_diff(tiling, decoder, latent_vec_interpolation, N=256, max_batch=32 ** 3, offset=None, scale=None,

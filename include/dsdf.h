@@ -797,6 +797,64 @@ int dsdf_fem_energy(const DsdfFemOp* op, const double* u, double* we, int32_t no
 int dsdf_fem_boundary_gradient(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
                                const int64_t* bvstart, const double* weight, double* grad, void* stream);
 
+/* ---- derivative of a volume mesh with respect to the spline's control points (csrc/voldiff.hpp; fp64 restatement:
+ * tests/voldiff_numpy.py).  The reference differentiates its volume mesh through the surface's Jacobian only
+ * (analysis/geometry.py:176-197 get_dTheta, from deep_sdf/mesh.py:346-454); here every moving vertex of dsdf_tet_emit's mesh is
+ * differentiated in closed form, the face and body diagonals included.  Additions only: DSDF_ABI_VERSION is unchanged.
+ *
+ * Vertex v = (p, c) = (vert_point[v], vert_class[v]) as dsdf_tet_emit reports it; d = (c & 1, (c >> 1) & 1, (c >> 2) & 1),
+ * q = p + sum_b d[b] * stride[b], s0 = grid[p], s1 = grid[q] (the capped grid the mesh was made from).  A class-0 vertex does not
+ * move.  For c >= 1 every coordinate b with d[b] = 1 moves by the same t:
+ *   d verts[v][b] / d cp[k][l] = d[b] * scale[b] * sum_{e in {0, 1}} dt/ds_e * mask_e * G_e[l] * weight_e(k)
+ * with dt/ds_e, the band and its rows exactly dsdf_msd_*'s (above); the band must hold both endpoints of every class >= 1 vertex
+ * (an endpoint of a crossing diagonal need not lie on a crossing axis edge: the surface's band is not enough).
+ * t_clamp = tau: t = (level - s0) / (s1 - s0) in dsdf_tet_emit's fp32 sequence; when tau > 0 the vertex moves iff
+ * tau <= t <= 1 - tau (1 - tau in fp32), i.e. iff the clamp left t unchanged; otherwise its derivative is exactly zero.  tau = 0
+ * zeroes nothing.
+ * The entries work on a compacted list vert_index [n_moving] int32 of ids into the mesh's n_verts vertices (any subset, ascending
+ * for a reproducible order; deepsdf_amd passes the class >= 1 vertices): grid vertices, most of a volume mesh, cost nothing.
+ * grad_verts / d_verts / normals are [n_verts][3] and are addressed through vert_index.  A list entry outside 0 .. n_verts - 1, a
+ * class outside 1 .. 7, a point outside the grid, a far endpoint past the grid, a band row or base out of range contributes
+ * nothing; nothing is read or written out of bounds for in-range arrays.
+ *   dsdf_vd_jvp     d_cp [ncp][L] -> d_verts [n_verts][3]: the entry zeroes all of d_verts, then one wave per list entry writes
+ *                   its row: coordinate b = fma(scale[b] * dt1, dot1, fma(scale[b] * dt0, dot0, 0)) where d[b] = 1 (dot_e: the
+ *                   endpoint's (slot, l) products over the lanes and a fixed xor-shuffle tree, as dsdf_msd_jvp), 0 elsewhere.  A
+ *                   class-1/2/4 vertex has dsdf_msd_jvp's bits.
+ *   dsdf_vd_vjp     grad_verts [n_verts][3] -> grad_cp [ncp][L].  Per list entry gs = sum over b with d[b] = 1, in increasing b,
+ *                   of scale[b] * grad_verts[v][b] (every product and sum rounded on its own); endpoint e adds
+ *                   fma(gs * dt_e, weight * G[l], acc).  Two stages as dsdf_msd_vjp: ceil(n_moving / 512) partial sums in list
+ *                   order, then their sum in part order; ws from dsdf_vd_vjp_workspace_bytes (256-byte aligned, planner
+ *                   conventions, region vd_vjp_part).
+ *   dsdf_vd_dtheta  out [n_moving][3][R], R = ncp * L: the reference's get_dTheta (analysis/geometry.py:176-197: stretch,
+ *                   jac[jac > 1] = 0, jac[jac < -1] = 0, dot_prod with the normal) for list entry i, normal n = normals[v],
+ *                   column r = (k, l), fp32, every operation rounded once:
+ *                     T    = (0 + (dt0 * weight0(k)) * G0[l]) + (dt1 * weight1(k)) * G1[l]   (no fused multiply-add; an endpoint
+ *                            that contributes nothing, or whose support does not hold k, is left out)
+ *                     j[b] = (stretch[b] * scale[b]) * T where d[b] = 1, 0 elsewhere; if clip > 0 and |j[b]| > clip: j[b] = 0
+ *                     nj   = ((0 + n[0] j[0]) + n[1] j[1]) + n[2] j[2],   nn = (n[0] n[0] + n[1] n[1]) + n[2] n[2]
+ *                     out[i][b][r] = n[b] * (nj / nn);  a vertex with nn = 0 or one that does not move: +0.
+ *                   dsdf_mt_project's rule carried to several coordinates.  stretch [host] 3 floats.
+ * No atomics; two identical calls give identical bytes.  Every argument error returns DSDF_E_INVALID before anything is launched. */
+typedef struct DsdfVdMesh {
+  const float* grid;               /* device, capped sdf [dims[0]][dims[1]][dims[2]] */
+  const int64_t* vert_point;       /* device [n_verts] */
+  const int32_t* vert_class;       /* device [n_verts] */
+  const int32_t* vert_index;       /* device [n_moving] */
+  const int32_t* band_of;          /* device [grid points]: band row of a grid index, < 0: none */
+  int64_t n_verts, n_moving;
+  int32_t dims[3];                 /* 2 .. 1024 */
+  float scale[3];                  /* voxel_size / 2 of the returned vertices */
+  float level;
+  float t_clamp;                   /* dsdf_tet_emit's, [0, 0.5) */
+} DsdfVdMesh;
+
+int dsdf_vd_vjp_workspace_bytes(int64_t n_moving, int64_t n_control_points, int32_t L, size_t* bytes, int32_t* n_parts); /* [host] */
+int dsdf_vd_jvp(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* d_cp, float* d_verts, void* stream);
+int dsdf_vd_vjp(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* grad_verts, float* grad_cp, void* ws,
+                size_t ws_bytes, void* stream);
+int dsdf_vd_dtheta(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* normals, const float* stretch /*[host]*/,
+                   float clip, float* out, void* stream);
+
 /* ---- building blocks (exported for the parity tests and profiling; not needed by a trainer) --------- */
 /* C[M,N] = A[M,K] * B[N,K]^T (+bias) */
 int dsdf_gemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
