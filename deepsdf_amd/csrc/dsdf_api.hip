@@ -2591,35 +2591,57 @@ int dsdf_ms_rows_at(const DsdfMsSpline* spline, const DsdfMsGrid* grid, const in
 namespace {
 struct MsdPlan { int64_t per; int32_t n_parts, n_tiles; size_t part, ws; };
 
-int msd_plan(int64_t n_verts, int64_t ncp, int32_t L, MsdPlan* P, WsTable* rec = nullptr) {
-  if (n_verts < 0 || n_verts > INT32_MAX) return fail(DSDF_E_INVALID, "mesh derivative: %lld vertices (0 .. %d)", (long long)n_verts, INT32_MAX);
-  if (L < 1) return fail(DSDF_E_INVALID, "mesh derivative: %d latent columns", L);
+// What the surface's and the volume's adjoint call things: the messages' prefix and their word for the list, the workspace region
+// of the partial sums, the first-stage kernel.
+struct MsdNames { const char *what, *verts, *region, *part_kernel; };
+constexpr MsdNames MSD_NAMES = {"mesh derivative", "vertices", "msd_vjp_part", "msd_vjp_part_kernel"};
+constexpr MsdNames VD_NAMES = {"volume derivative", "moving vertices", "vd_vjp_part", "vd_vjp_part_kernel"};
+
+// The adjoint's workspace for a list of n vertices.
+int msd_plan(const MsdNames& N, int64_t n, int64_t ncp, int32_t L, MsdPlan* P, WsTable* rec = nullptr) {
+  const char* what = N.what;
+  if (n < 0 || n > INT32_MAX) return fail(DSDF_E_INVALID, "%s: %lld %s (0 .. %d)", what, (long long)n, N.verts, INT32_MAX);
+  if (L < 1) return fail(DSDF_E_INVALID, "%s: %d latent columns", what, L);
   if (ncp < 1 || ncp * (int64_t)L > INT32_MAX)
-    return fail(DSDF_E_INVALID, "mesh derivative: control net of %lld x %d floats (1 .. %d)", (long long)ncp, L, INT32_MAX);
+    return fail(DSDF_E_INVALID, "%s: control net of %lld x %d floats (1 .. %d)", what, (long long)ncp, L, INT32_MAX);
   P->per = ncp * L;
-  P->n_parts = (int32_t)((n_verts + MSD_VJP_VERTS - 1) / MSD_VJP_VERTS);
+  P->n_parts = (int32_t)((n + MSD_VJP_VERTS - 1) / MSD_VJP_VERTS);
   P->n_tiles = (int32_t)((P->per + MSD_VJP_TILE - 1) / MSD_VJP_TILE);
-  if (P->n_tiles > 65535) return fail(DSDF_E_INVALID, "mesh derivative: control net of %lld floats (the adjoint takes at most %lld)", (long long)P->per, 65535ll * MSD_VJP_TILE);
+  if (P->n_tiles > 65535) return fail(DSDF_E_INVALID, "%s: control net of %lld floats (the adjoint takes at most %lld)", what, (long long)P->per, 65535ll * MSD_VJP_TILE);
   P->part = (size_t)P->n_parts * (size_t)P->per * 4;
   WsCarver c(rec);
-  c.take("msd_vjp_part", -1, P->part);
+  c.take(N.region, -1, P->part);
   P->ws = c.finish(c.o);
   return 0;
 }
 
-int msd_setup(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, MsdMesh* M, MsdBand* B) {
-  if (!mesh || !band) return fail(DSDF_E_INVALID, "mesh derivative: NULL mesh or band");
-  if (mesh->n_verts < 0 || mesh->n_verts > INT32_MAX)
-    return fail(DSDF_E_INVALID, "mesh derivative: %lld vertices (0 .. %d)", (long long)mesh->n_verts, INT32_MAX);
-  M->npts = 1;
+int msd_plan_out(const MsdNames& N, int64_t n, int64_t ncp, int32_t L, size_t* bytes, int32_t* n_parts) {
+  MsdPlan P;
+  TRY(msd_plan(N, n, ncp, L, &P, &t_last_plan));
+  if (!bytes && !n_parts) return fail(DSDF_E_INVALID, "%s: every output is NULL", N.what);
+  if (bytes) *bytes = P.ws;
+  if (n_parts) *n_parts = P.n_parts;
+  return 0;
+}
+
+// The grid of either mesh type: vertex count, sizes and scale -> npts, stride[], scale[].
+int msd_grid(int64_t n_verts, const int32_t dims[3], const float scale[3], int64_t* npts, int64_t stride[3], float scale_out[3]) {
+  if (n_verts < 0 || n_verts > INT32_MAX)
+    return fail(DSDF_E_INVALID, "mesh derivative: %lld vertices (0 .. %d)", (long long)n_verts, INT32_MAX);
+  *npts = 1;
   for (int a = 0; a < 3; ++a) {
-    const int n = mesh->dims[a];
+    const int n = dims[a];
     if (n < 2 || n > MC_MAX_DIM) return fail(DSDF_E_INVALID, "mesh derivative: grid size %d outside 2 .. %d", n, MC_MAX_DIM);
-    if (!std::isfinite(mesh->scale[a])) return fail(DSDF_E_INVALID, "mesh derivative: scale %d is not finite", a);
-    M->npts *= n;
-    M->scale[a] = mesh->scale[a];
+    if (!std::isfinite(scale[a])) return fail(DSDF_E_INVALID, "mesh derivative: scale %d is not finite", a);
+    *npts *= n;
+    scale_out[a] = scale[a];
   }
-  M->stride[0] = (int64_t)mesh->dims[1] * mesh->dims[2]; M->stride[1] = mesh->dims[2]; M->stride[2] = 1;
+  stride[0] = (int64_t)dims[1] * dims[2]; stride[1] = dims[2]; stride[2] = 1;
+  return 0;
+}
+
+// The band of either mesh type; mesh_ptrs: every per-vertex and per-grid-point array of a mesh that has vertices is there.
+int msd_band(const DsdfMsdBand* band, bool has_verts, bool mesh_ptrs, MsdBand* B) {
   if (band->L < 1) return fail(DSDF_E_INVALID, "mesh derivative: %d latent columns", band->L);
   if (band->n_band < 0 || band->n_band > INT32_MAX) return fail(DSDF_E_INVALID, "mesh derivative: %lld band rows", (long long)band->n_band);
   if (band->ld_g < band->L) return fail(DSDF_E_INVALID, "mesh derivative: ld_g %lld < L %d", (long long)band->ld_g, band->L);
@@ -2632,27 +2654,49 @@ int msd_setup(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, MsdMesh* M, MsdB
     ncp *= n;
   }
   if (ncp * (int64_t)band->L > INT32_MAX) return fail(DSDF_E_INVALID, "mesh derivative: control net of %lld floats (at most %d)", (long long)(ncp * band->L), INT32_MAX);
-  if (mesh->n_verts > 0) {
-    if (!mesh->grid || !mesh->edge_point || !mesh->edge_axis || !mesh->band_of)
-      return fail(DSDF_E_INVALID, "mesh derivative: NULL grid, edge_point, edge_axis or band_of");
+  if (has_verts) {
+    if (!mesh_ptrs) return fail(DSDF_E_INVALID, "mesh derivative: NULL grid, edge_point, edge_axis or band_of");
     if (band->n_band > 0 && (!band->G || !band->weights || !band->base || !band->mask))
       return fail(DSDF_E_INVALID, "mesh derivative: NULL G, weights, base or mask");
   }
-  M->grid = mesh->grid; M->edge_point = mesh->edge_point; M->edge_axis = mesh->edge_axis; M->band_of = mesh->band_of;
-  M->V = mesh->n_verts; M->level = mesh->level;
   B->G = band->G; B->w = band->weights; B->base = band->base; B->m = band->mask;
   B->nb = band->n_band; B->ldg = band->ld_g; B->L = band->L; B->ncp_total = (int)ncp;
+  return 0;
+}
+
+int msd_setup(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, MsdMesh* M, MsdBand* B) {
+  if (!mesh || !band) return fail(DSDF_E_INVALID, "mesh derivative: NULL mesh or band");
+  TRY(msd_grid(mesh->n_verts, mesh->dims, mesh->scale, &M->npts, M->stride, M->scale));
+  TRY(msd_band(band, mesh->n_verts > 0, mesh->grid && mesh->edge_point && mesh->edge_axis && mesh->band_of, B));
+  M->grid = mesh->grid; M->edge_point = mesh->edge_point; M->edge_axis = mesh->edge_axis; M->band_of = mesh->band_of;
+  M->V = mesh->n_verts; M->level = mesh->level;
+  return 0;
+}
+
+// The adjoint of a mesh with a list of n vertices: plan, argument checks, `part` over (parts, tiles) into ws, then the parts summed in
+// part order.
+extern "C++" template <class Mesh>
+int msd_vjp_run(const MsdNames& N, void (*part)(Mesh, MsdBand, const float*, float*), const Mesh& M, int64_t n, const MsdBand& B,
+                const float* grad_verts, float* grad_cp, void* ws, size_t ws_bytes, void* stream) {
+  MsdPlan P;
+  TRY(msd_plan(N, n, B.ncp_total, B.L, &P, &t_last_plan));
+  if (!grad_cp) return fail(DSDF_E_INVALID, "%s: NULL grad_cp", N.what);
+  if (n > 0 && (!grad_verts || !ws)) return fail(DSDF_E_INVALID, "%s: NULL grad_verts or workspace", N.what);
+  if (n > 0 && ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", N.what, ws_bytes, P.ws);
+  hipStream_t st = (hipStream_t)stream;
+  if (P.n_parts > 0) {
+    hipLaunchKernelGGL(part, dim3((unsigned)P.n_parts, (unsigned)P.n_tiles), dim3(MSD_BLOCK), 0, st, M, B, grad_verts, (float*)ws);
+    LAUNCH_OK(N.part_kernel);
+  }
+  hipLaunchKernelGGL(msd_vjp_sum_kernel, dim3((unsigned)((P.per + MSD_BLOCK - 1) / MSD_BLOCK)), dim3(MSD_BLOCK), 0, st, (const float*)ws,
+                     P.n_parts, P.per, grad_cp);
+  LAUNCH_OK("msd_vjp_sum_kernel");
   return 0;
 }
 }  // namespace
 
 int dsdf_msd_vjp_workspace_bytes(int64_t n_verts, int64_t n_control_points, int32_t L, size_t* bytes, int32_t* n_parts) {
-  MsdPlan P;
-  TRY(msd_plan(n_verts, n_control_points, L, &P, &t_last_plan));
-  if (!bytes && !n_parts) return fail(DSDF_E_INVALID, "mesh derivative: every output is NULL");
-  if (bytes) *bytes = P.ws;
-  if (n_parts) *n_parts = P.n_parts;
-  return 0;
+  return msd_plan_out(MSD_NAMES, n_verts, n_control_points, L, bytes, n_parts);
 }
 
 int dsdf_msd_jacobian(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, int32_t full, float* jac, int32_t* axis, void* stream) {
@@ -2685,69 +2729,31 @@ int dsdf_msd_vjp(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, const float* 
                  void* stream) {
   MsdMesh M; MsdBand B;
   TRY(msd_setup(mesh, band, &M, &B));
-  MsdPlan P;
-  TRY(msd_plan(M.V, B.ncp_total, B.L, &P, &t_last_plan));
-  if (!grad_cp) return fail(DSDF_E_INVALID, "mesh derivative: NULL grad_cp");
-  if (M.V > 0 && (!grad_verts || !ws)) return fail(DSDF_E_INVALID, "mesh derivative: NULL grad_verts or workspace");
-  if (M.V > 0 && ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "mesh derivative: workspace %zu < %zu bytes", ws_bytes, P.ws);
-  hipStream_t st = (hipStream_t)stream;
-  if (P.n_parts > 0) {
-    hipLaunchKernelGGL(msd_vjp_part_kernel, dim3((unsigned)P.n_parts, (unsigned)P.n_tiles), dim3(MSD_BLOCK), 0, st, M, B, grad_verts,
-                       (float*)ws);
-    LAUNCH_OK("msd_vjp_part_kernel");
-  }
-  hipLaunchKernelGGL(msd_vjp_sum_kernel, dim3((unsigned)((P.per + MSD_BLOCK - 1) / MSD_BLOCK)), dim3(MSD_BLOCK), 0, st, (const float*)ws,
-                     P.n_parts, P.per, grad_cp);
-  LAUNCH_OK("msd_vjp_sum_kernel");
-  return 0;
+  return msd_vjp_run(MSD_NAMES, msd_vjp_part_kernel, M, M.V, B, grad_verts, grad_cp, ws, ws_bytes, stream);
 }
 
 // ---- volume mesh derivatives (voldiff.hpp) -------------------------------------------------------------------
 namespace {
-int vd_plan(int64_t n_moving, int64_t ncp, int32_t L, MsdPlan* P, WsTable* rec = nullptr) {
-  if (n_moving < 0 || n_moving > INT32_MAX) return fail(DSDF_E_INVALID, "volume derivative: %lld moving vertices (0 .. %d)", (long long)n_moving, INT32_MAX);
-  if (L < 1) return fail(DSDF_E_INVALID, "volume derivative: %d latent columns", L);
-  if (ncp < 1 || ncp * (int64_t)L > INT32_MAX)
-    return fail(DSDF_E_INVALID, "volume derivative: control net of %lld x %d floats (1 .. %d)", (long long)ncp, L, INT32_MAX);
-  P->per = ncp * L;
-  P->n_parts = (int32_t)((n_moving + MSD_VJP_VERTS - 1) / MSD_VJP_VERTS);
-  P->n_tiles = (int32_t)((P->per + MSD_VJP_TILE - 1) / MSD_VJP_TILE);
-  if (P->n_tiles > 65535) return fail(DSDF_E_INVALID, "volume derivative: control net of %lld floats (the adjoint takes at most %lld)", (long long)P->per, 65535ll * MSD_VJP_TILE);
-  P->part = (size_t)P->n_parts * (size_t)P->per * 4;
-  WsCarver c(rec);
-  c.take("vd_vjp_part", -1, P->part);
-  P->ws = c.finish(c.o);
-  return 0;
-}
-
-// grid, scale and band through msd_setup (the same checks and messages), then the volume mesh's own arrays
+// grid, scale and band through the surface's checks (the same messages), then the volume mesh's own arrays
 int vd_setup(const DsdfVdMesh* mesh, const DsdfMsdBand* band, VdMesh* M, MsdBand* B) {
   if (!mesh || !band) return fail(DSDF_E_INVALID, "volume derivative: NULL mesh or band");
   if (mesh->n_moving < 0 || mesh->n_moving > INT32_MAX)
     return fail(DSDF_E_INVALID, "volume derivative: %lld moving vertices (0 .. %d)", (long long)mesh->n_moving, INT32_MAX);
   if (!(mesh->t_clamp >= 0.f && mesh->t_clamp < 0.5f)) return fail(DSDF_E_INVALID, "volume derivative: t_clamp %g outside [0, 0.5)", (double)mesh->t_clamp);
-  DsdfMsdMesh m;
-  m.grid = mesh->grid; m.edge_point = mesh->vert_point; m.edge_axis = mesh->vert_class; m.band_of = mesh->band_of;
-  m.n_verts = mesh->n_verts; m.level = mesh->level;
-  for (int a = 0; a < 3; ++a) { m.dims[a] = mesh->dims[a]; m.scale[a] = mesh->scale[a]; }
-  MsdMesh S;
-  TRY(msd_setup(&m, band, &S, B));
+  TRY(msd_grid(mesh->n_verts, mesh->dims, mesh->scale, &M->npts, M->stride, M->scale));
+  TRY(msd_band(band, mesh->n_verts > 0, mesh->grid && mesh->vert_point && mesh->vert_class && mesh->band_of, B));
   if (mesh->n_moving > 0 && (!mesh->vert_index || mesh->n_verts == 0))
     return fail(DSDF_E_INVALID, "volume derivative: NULL vert_index, or moving vertices of an empty mesh");
-  M->grid = S.grid; M->vert_point = S.edge_point; M->vert_class = S.edge_axis; M->vert_index = mesh->vert_index; M->band_of = S.band_of;
-  M->npts = S.npts; M->V = S.V; M->Vm = mesh->n_moving; M->level = S.level; M->t_clamp = mesh->t_clamp;
-  for (int a = 0; a < 3; ++a) { M->stride[a] = S.stride[a]; M->dims[a] = mesh->dims[a]; M->scale[a] = S.scale[a]; }
+  M->grid = mesh->grid; M->vert_point = mesh->vert_point; M->vert_class = mesh->vert_class; M->vert_index = mesh->vert_index;
+  M->band_of = mesh->band_of;
+  M->V = mesh->n_verts; M->Vm = mesh->n_moving; M->level = mesh->level; M->t_clamp = mesh->t_clamp;
+  for (int a = 0; a < 3; ++a) M->dims[a] = mesh->dims[a];
   return 0;
 }
 }  // namespace
 
 int dsdf_vd_vjp_workspace_bytes(int64_t n_moving, int64_t n_control_points, int32_t L, size_t* bytes, int32_t* n_parts) {
-  MsdPlan P;
-  TRY(vd_plan(n_moving, n_control_points, L, &P, &t_last_plan));
-  if (!bytes && !n_parts) return fail(DSDF_E_INVALID, "volume derivative: every output is NULL");
-  if (bytes) *bytes = P.ws;
-  if (n_parts) *n_parts = P.n_parts;
-  return 0;
+  return msd_plan_out(VD_NAMES, n_moving, n_control_points, L, bytes, n_parts);
 }
 
 int dsdf_vd_jvp(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* d_cp, float* d_verts, void* stream) {
@@ -2769,21 +2775,7 @@ int dsdf_vd_vjp(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* gr
                 void* stream) {
   VdMesh M; MsdBand B;
   TRY(vd_setup(mesh, band, &M, &B));
-  MsdPlan P;
-  TRY(vd_plan(M.Vm, B.ncp_total, B.L, &P, &t_last_plan));
-  if (!grad_cp) return fail(DSDF_E_INVALID, "volume derivative: NULL grad_cp");
-  if (M.Vm > 0 && (!grad_verts || !ws)) return fail(DSDF_E_INVALID, "volume derivative: NULL grad_verts or workspace");
-  if (M.Vm > 0 && ws_bytes < P.ws) return fail(DSDF_E_WORKSPACE, "volume derivative: workspace %zu < %zu bytes", ws_bytes, P.ws);
-  hipStream_t st = (hipStream_t)stream;
-  if (P.n_parts > 0) {
-    hipLaunchKernelGGL(vd_vjp_part_kernel, dim3((unsigned)P.n_parts, (unsigned)P.n_tiles), dim3(MSD_BLOCK), 0, st, M, B, grad_verts,
-                       (float*)ws);
-    LAUNCH_OK("vd_vjp_part_kernel");
-  }
-  hipLaunchKernelGGL(msd_vjp_sum_kernel, dim3((unsigned)((P.per + MSD_BLOCK - 1) / MSD_BLOCK)), dim3(MSD_BLOCK), 0, st, (const float*)ws,
-                     P.n_parts, P.per, grad_cp);
-  LAUNCH_OK("msd_vjp_sum_kernel");
-  return 0;
+  return msd_vjp_run(VD_NAMES, vd_vjp_part_kernel, M, M.Vm, B, grad_verts, grad_cp, ws, ws_bytes, stream);
 }
 
 int dsdf_vd_dtheta(const DsdfVdMesh* mesh, const DsdfMsdBand* band, const float* normals, const float* stretch, float clip, float* out,

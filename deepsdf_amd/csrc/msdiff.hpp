@@ -16,9 +16,17 @@
 //   msd_jvp_kernel       one wave per vertex: the (slot, l) products of each endpoint over the lanes, a fixed xor-shuffle tree.
 //   msd_vjp_part_kernel  first stage of the adjoint: workgroup (part, tile) walks MSD_VJP_VERTS vertices in order and adds each
 //                        endpoint's (slot, l) products into its LDS tile of grad_cp -- the slots of one endpoint name distinct
-//                        control points, so the adds of one step never collide, and a barrier separates the steps: no atomics,
-//                        a fixed order.  msd_vjp_sum_kernel adds the parts in part order.
+//                        control points, so the adds of one step never collide, and a barrier separates the steps (a vertex with
+//                        no valid endpoint is skipped by the whole workgroup): no atomics, a fixed order.  msd_vjp_sum_kernel adds
+//                        the parts in part order.
 // A vertex whose edge, band row or base index is out of range contributes nothing (nothing is read or written out of bounds).
+//
+// Shared with the volume mesh's derivative (voldiff.hpp), defined here once: the endpoint record MsdEnd, msd_dt (the dt pair),
+// msd_ends (band row, mask, base, support check -> the two records; the caller has found p and q valid by its own rule and supplies
+// the coefficients), msd_walk (t -> (slot, l) -> weight * G and the control net's float), msd_split / msd_slot (control point ->
+// weight slot of an endpoint's support), msd_end_dot, msd_vjp_part (the first stage's body; the mesh type supplies msd_vjp_count and
+// msd_vjp_ends, its list and its per-vertex factor) and msd_vjp_sum_kernel.  Shared arithmetic uses common.hpp's rn_* helpers: the
+// same bits in every kernel it is inlined into.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,23 +61,26 @@ struct MsdBand {
   int L, ncp_total;
 };
 
-struct MsdEnd { float coef; int64_t row; int first[3]; };   // coef = scale * dt/ds_k; row < 0: the endpoint contributes nothing
+struct MsdEnd { float coef; int64_t row; int first[3]; };   // coef: the caller's factor of the endpoint; row < 0: it contributes nothing
 
-// Axis and the two endpoints of vertex v (the same for every lane of a workgroup / wave that shares v).
-__device__ __forceinline__ int msd_vertex(const MsdMesh& M, const MsdBand& B, int64_t v, MsdEnd e[2]) {
+__device__ __forceinline__ void msd_no_ends(MsdEnd e[2]) {
   e[0].row = e[1].row = -1;
   e[0].coef = e[1].coef = 0.f;
-  const int a = M.edge_axis[v];
-  const int64_t p = M.edge_point[v];
-  if (a < 0 || a > 2 || p < 0) return a < 0 || a > 2 ? 0 : a;
-  const int64_t q = p + M.stride[a];
-  if (q >= M.npts) return a;
-  const float s0 = M.grid[p], s1 = M.grid[q];
-  const float d = s1 - s0, dd = d * d;
-  const float dt[2] = {(M.level - s1) / dd, -(M.level - s0) / dd};
-  const int64_t g[2] = {p, q};
+}
+
+// dt/ds0, dt/ds1 of t = (level - s0) / (s1 - s0)
+__device__ __forceinline__ void msd_dt(float level, float s0, float s1, float dt[2]) {
+  const float d = rn_sub(s1, s0), dd = rn_mul(d, d);
+  dt[0] = rn_div(rn_sub(level, s1), dd);
+  dt[1] = -rn_div(rn_sub(level, s0), dd);
+}
+
+// The endpoints at grid points g of a vertex whose mesh found them valid: band row, mask, base control point, the first control
+// point per axis and the support check.  An endpoint that passes gets its row and the caller's coef[k]; the other stays as it was.
+__device__ __forceinline__ void msd_ends(const MsdBand& B, const int32_t* __restrict__ band_of, const int64_t g[2], const float coef[2],
+                                         MsdEnd e[2]) {
   for (int k = 0; k < 2; ++k) {
-    const int64_t r = M.band_of[g[k]];
+    const int64_t r = band_of[g[k]];
     if (r < 0 || r >= B.nb || !B.m[r]) continue;
     int b = B.base[r];
     if (b < 0 || b >= B.ncp_total) continue;
@@ -82,24 +93,72 @@ __device__ __forceinline__ int msd_vertex(const MsdMesh& M, const MsdBand& B, in
     }
     if (!ok) continue;
     e[k].row = r;
-    e[k].coef = M.scale[a] * dt[k];
+    e[k].coef = coef[k];
   }
+}
+
+// Axis and the two endpoints, coef = scale[a] * dt/ds_k, of vertex v (the same for every lane of a workgroup / wave that shares v).
+__device__ __forceinline__ int msd_vertex(const MsdMesh& M, const MsdBand& B, int64_t v, MsdEnd e[2]) {
+  msd_no_ends(e);
+  const int a = M.edge_axis[v];
+  const int64_t p = M.edge_point[v];
+  if (a < 0 || a > 2 || p < 0) return a < 0 || a > 2 ? 0 : a;
+  const int64_t q = p + M.stride[a];
+  if (q >= M.npts) return a;
+  float dt[2];
+  msd_dt(M.level, M.grid[p], M.grid[q], dt);
+  const int64_t g[2] = {p, q};
+  const float coef[2] = {rn_mul(M.scale[a], dt[0]), rn_mul(M.scale[a], dt[1])};
+  msd_ends(B, M.band_of, g, coef, e);
   return a;
+}
+
+// Control point c of the net -> its index on each axis.
+__device__ __forceinline__ void msd_split(const MsdBand& B, uint32_t c, int ci[3]) {
+  const int cr = (int)(c / (uint32_t)B.ncp[0]);
+  ci[0] = (int)(c % (uint32_t)B.ncp[0]);
+  ci[1] = cr % B.ncp[1];
+  ci[2] = cr / B.ncp[1];
+}
+
+// The weight slot of control point ci in endpoint e's support, -1: outside it.
+__device__ __forceinline__ int msd_slot(const MsdBand& B, const MsdEnd& e, const int ci[3]) {
+  const int i = ci[0] - e.first[0], j = ci[1] - e.first[1], kk = ci[2] - e.first[2];
+  if (i < 0 || i > B.deg[0] || j < 0 || j > B.deg[1] || kk < 0 || kk > B.deg[2]) return -1;
+  return (kk * 4 + j) * 4 + i;
+}
+
+// The walk over an endpoint's (slot, l) products, t = slot * L + l below msd_walk_total: -> rn(w[slot] * G[l]), *at the float of the
+// control net [ncp][L] the product belongs to.  w, G: the endpoint's rows (msd_row_w, msd_row_G), taken once before the loop.
+__device__ __forceinline__ int msd_walk_total(const MsdBand& B) { return (B.deg[0] + 1) * (B.deg[1] + 1) * (B.deg[2] + 1) * B.L; }
+
+__device__ __forceinline__ const float* msd_row_w(const MsdBand& B, const MsdEnd& e) { return B.w + e.row * MS_WEIGHTS; }
+__device__ __forceinline__ const float* msd_row_G(const MsdBand& B, const MsdEnd& e) { return B.G + e.row * B.ldg; }
+
+__device__ __forceinline__ float msd_walk(const MsdBand& B, const MsdEnd& e, const float* __restrict__ w, const float* __restrict__ G, int t,
+                                          int64_t* at) {
+  const int d0 = B.deg[0] + 1, d1 = B.deg[1] + 1, L = B.L;
+  const int s = t / L, l = t - s * L;
+  const int i = s % d0, sr = s / d0;
+  const int j = sr % d1, kk = sr / d1;
+  const int c = (e.first[0] + i) + B.ncp[0] * ((e.first[1] + j) + B.ncp[1] * (e.first[2] + kk));
+  *at = (int64_t)c * L + l;
+  return rn_mul(w[(kk * 4 + j) * 4 + i], G[l]);
 }
 
 // The VEC values of store q (control point q / (L / VEC), latent columns (q % (L / VEC)) * VEC ..) of a vertex with endpoints e.
 template <int VEC>
 __device__ __forceinline__ void msd_dense_store(const MsdBand& B, const MsdEnd* e, uint32_t q, uint32_t Lq, float* __restrict__ out) {
   const uint32_t c = q / Lq, l = (q - c * Lq) * VEC;
-  const int ci = (int)(c % (uint32_t)B.ncp[0]), cr = (int)(c / (uint32_t)B.ncp[0]);
-  const int cj = cr % B.ncp[1], ck = cr / B.ncp[1];
+  int ci[3];
+  msd_split(B, c, ci);
   float val[VEC];
   for (int x = 0; x < VEC; ++x) val[x] = 0.f;
   for (int k = 0; k < 2; ++k) {
     if (e[k].row < 0) continue;
-    const int i = ci - e[k].first[0], j = cj - e[k].first[1], kk = ck - e[k].first[2];
-    if (i < 0 || i > B.deg[0] || j < 0 || j > B.deg[1] || kk < 0 || kk > B.deg[2]) continue;
-    const float f = e[k].coef * B.w[e[k].row * MS_WEIGHTS + (kk * 4 + j) * 4 + i];
+    const int s = msd_slot(B, e[k], ci);
+    if (s < 0) continue;
+    const float f = rn_mul(e[k].coef, B.w[e[k].row * MS_WEIGHTS + s]);
     const float* __restrict__ G = B.G + e[k].row * B.ldg + l;
     for (int x = 0; x < VEC; ++x) val[x] = fmaf(f, G[x], val[x]);
   }
@@ -154,17 +213,14 @@ __global__ __launch_bounds__(MSD_BLOCK) void msd_dense_kernel(MsdMesh M, MsdBand
 
 // sum over the (slot, l) products of one endpoint: sum_s sum_l w[s] * G[l] * x[c(s)][l], this lane's share
 __device__ __forceinline__ float msd_end_dot(const MsdBand& B, const MsdEnd& e, const float* __restrict__ x, int lane, int step) {
-  const int d0 = B.deg[0] + 1, d1 = B.deg[1] + 1, d2 = B.deg[2] + 1;
-  const int L = B.L, total = d0 * d1 * d2 * L;
-  const float* __restrict__ w = B.w + e.row * MS_WEIGHTS;
-  const float* __restrict__ G = B.G + e.row * B.ldg;
+  const int total = msd_walk_total(B);
+  const float* __restrict__ w = msd_row_w(B, e);
+  const float* __restrict__ G = msd_row_G(B, e);
   float acc = 0.f;
   for (int t = lane; t < total; t += step) {
-    const int s = t / L, l = t - s * L;
-    const int i = s % d0, sr = s / d0;
-    const int j = sr % d1, kk = sr / d1;
-    const int c = (e.first[0] + i) + B.ncp[0] * ((e.first[1] + j) + B.ncp[1] * (e.first[2] + kk));
-    acc = fmaf(w[(kk * 4 + j) * 4 + i] * G[l], x[(int64_t)c * L + l], acc);
+    int64_t at;
+    const float wg = msd_walk(B, e, w, G, t, &at);
+    acc = fmaf(wg, x[at], acc);
   }
   return acc;
 }
@@ -186,8 +242,20 @@ __global__ __launch_bounds__(MSD_BLOCK) void msd_jvp_kernel(MsdMesh M, MsdBand B
   if (lane < 3) d_verts[v * 3 + lane] = lane == a ? tot : 0.f;
 }
 
-__global__ __launch_bounds__(MSD_BLOCK) void msd_vjp_part_kernel(MsdMesh M, MsdBand B, const float* __restrict__ grad_verts,
-                                                                 float* __restrict__ part) {
+// The surface's part of the adjoint's first stage: its list is every vertex, and endpoint k of vertex v adds
+// f = g * (scale[a] * dt/ds_k) times the walk's products, g = grad_verts[v, a]: f is left in e[k].coef.
+__device__ __forceinline__ int64_t msd_vjp_count(const MsdMesh& M) { return M.V; }
+
+__device__ __forceinline__ void msd_vjp_ends(const MsdMesh& M, const MsdBand& B, int64_t v, const float* __restrict__ grad_verts,
+                                             MsdEnd e[2]) {
+  const float g = grad_verts[v * 3 + msd_vertex(M, B, v, e)];
+  for (int k = 0; k < 2; ++k) e[k].coef = rn_mul(g, e[k].coef);
+}
+
+// First stage of the adjoint of a mesh type with msd_vjp_count and msd_vjp_ends (the surface above, the volume in voldiff.hpp).
+template <class Mesh>
+__device__ __forceinline__ void msd_vjp_part(const Mesh& M, const MsdBand& B, const float* __restrict__ grad_verts,
+                                             float* __restrict__ part) {
   __shared__ float acc[MSD_VJP_TILE];
   const int tid = threadIdx.x;
   const int64_t per = (int64_t)B.ncp_total * B.L;
@@ -195,26 +263,22 @@ __global__ __launch_bounds__(MSD_BLOCK) void msd_vjp_part_kernel(MsdMesh M, MsdB
   const int tn = (int)((per - tile0) < (int64_t)MSD_VJP_TILE ? (per - tile0) : (int64_t)MSD_VJP_TILE);
   for (int t = tid; t < tn; t += MSD_BLOCK) acc[t] = 0.f;
   __syncthreads();
-  const int64_t v0 = (int64_t)blockIdx.x * MSD_VJP_VERTS;
-  const int64_t v1 = v0 + MSD_VJP_VERTS < M.V ? v0 + MSD_VJP_VERTS : M.V;
-  const int d0 = B.deg[0] + 1, d1 = B.deg[1] + 1, d2 = B.deg[2] + 1;
-  const int L = B.L, total = d0 * d1 * d2 * L;
-  for (int64_t v = v0; v < v1; ++v) {                        // every bound and branch around the barriers is workgroup-uniform
+  const int64_t n = msd_vjp_count(M), i0 = (int64_t)blockIdx.x * MSD_VJP_VERTS;
+  const int64_t i1 = i0 + MSD_VJP_VERTS < n ? i0 + MSD_VJP_VERTS : n;
+  const int total = msd_walk_total(B);
+  for (int64_t i = i0; i < i1; ++i) {                        // every bound and branch around the barriers is workgroup-uniform
     MsdEnd e[2];
-    const int a = msd_vertex(M, B, v, e);
-    const float g = grad_verts[v * 3 + a];
+    msd_vjp_ends(M, B, i, grad_verts, e);
+    if (e[0].row < 0 && e[1].row < 0) continue;              // uniform: nothing to add, no barrier needed
     for (int k = 0; k < 2; ++k) {
       if (e[k].row >= 0) {
-        const float f = g * e[k].coef;
-        const float* __restrict__ w = B.w + e[k].row * MS_WEIGHTS;
-        const float* __restrict__ G = B.G + e[k].row * B.ldg;
+        const float* __restrict__ w = msd_row_w(B, e[k]);
+        const float* __restrict__ G = msd_row_G(B, e[k]);
         for (int t = tid; t < total; t += MSD_BLOCK) {
-          const int s = t / L, l = t - s * L;
-          const int i = s % d0, sr = s / d0;
-          const int j = sr % d1, kk = sr / d1;
-          const int c = (e[k].first[0] + i) + B.ncp[0] * ((e[k].first[1] + j) + B.ncp[1] * (e[k].first[2] + kk));
-          const int64_t at = (int64_t)c * L + l - tile0;
-          if (at >= 0 && at < tn) acc[at] = fmaf(f, w[(kk * 4 + j) * 4 + i] * G[l], acc[at]);
+          int64_t at;
+          const float wg = msd_walk(B, e[k], w, G, t, &at);
+          at -= tile0;
+          if (at >= 0 && at < tn) acc[at] = fmaf(e[k].coef, wg, acc[at]);
         }
       }
       __syncthreads();
@@ -222,6 +286,11 @@ __global__ __launch_bounds__(MSD_BLOCK) void msd_vjp_part_kernel(MsdMesh M, MsdB
   }
   float* __restrict__ out = part + (int64_t)blockIdx.x * per + tile0;
   for (int t = tid; t < tn; t += MSD_BLOCK) out[t] = acc[t];
+}
+
+__global__ __launch_bounds__(MSD_BLOCK) void msd_vjp_part_kernel(MsdMesh M, MsdBand B, const float* __restrict__ grad_verts,
+                                                                 float* __restrict__ part) {
+  msd_vjp_part(M, B, grad_verts, part);
 }
 
 __global__ __launch_bounds__(MSD_BLOCK) void msd_vjp_sum_kernel(const float* __restrict__ part, int n_parts, int64_t per,

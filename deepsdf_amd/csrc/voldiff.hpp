@@ -6,15 +6,19 @@
 // direction d = (c & 1, (c >> 1) & 1, (c >> 2) & 1), q = p + sum_b d[b] * stride[b], capped values s0 = grid[p], s1 = grid[q].
 //   t = (level - s0) / (s1 - s0) in tet_vertex_kernel's sequence; with t_clamp = tau > 0 the vertex moves iff tau <= t <= 1 - tau
 //   (1 - tau rounded to fp32): otherwise the clamp holds it and its derivative is exactly zero.  tau = 0 zeroes nothing.
-//   dt/ds0, dt/ds1: msd_vertex's fp32 expressions.  Every coordinate b with d[b] = 1 moves by the same t:
+//   dt/ds0, dt/ds1: msd_dt, the surface's.  Every coordinate b with d[b] = 1 moves by the same t:
 //   d verts[v, b] / d cp[k, l] = d[b] * scale[b] * sum_e dt/ds_e * m_e * G_e[l] * B_k(xo_e),   scale = voxel_size / 2
 // The band (MsdBand) is the volume mesh's own: an endpoint of a crossing diagonal need not lie on a crossing axis edge.
+//
+// This file holds what the volume mesh decides for itself: vd_vertex's rule for which list entries move (list entry, class, point,
+// the far endpoint per axis against the grid's size, the clamp) and the scalar in front of each endpoint.  Everything behind that --
+// the endpoint record, msd_ends, the index walk, the control-point split, the first stage of the adjoint -- is msdiff.hpp's, once.
 //
 //   vd_jvp_kernel       one wave per moving vertex (msd_jvp_kernel's form): msd_end_dot over the lanes, the fixed xor-shuffle tree,
 //                       then per flagged coordinate b  fma(scale[b] * dt1, dot1, fma(scale[b] * dt0, dot0, 0)): a class-1/2/4
 //                       vertex has msd_jvp_kernel's bits.  The entry zeroes d_verts first; rows off the list stay zero.
-//   vd_vjp_part_kernel  msd_vjp_part_kernel's form over the list: workgroup (part, tile), MSD_VJP_VERTS list entries in order, LDS
-//                       tile of MSD_VJP_TILE floats, a barrier per endpoint, no atomics.  The scalar of a vertex is
+//   vd_vjp_part_kernel  msd_vjp_part over the list (workgroup (part, tile), MSD_VJP_VERTS list entries in order, LDS tile of
+//                       MSD_VJP_TILE floats, a barrier per endpoint, no atomics) with the volume's factor: the scalar of a vertex is
 //                       gs = sum over flagged b, increasing, of scale[b] * grad[v, b] (each product and sum rounded on its own);
 //                       endpoint e adds fma(gs * dt_e, w * G[l], acc).  msd_vjp_sum_kernel adds the parts in part order.
 //   vd_dtheta_kernel    the dense normal-projected derivative of the moving vertices (include/dsdf.h states the sequence).
@@ -43,13 +47,10 @@ struct VdMesh {
   float level, t_clamp;
 };
 
-struct VdEnd { float dt; int64_t row; int first[3]; };      // row < 0: the endpoint contributes nothing
-
-// Vertex id (-1: list entry out of range), class (0: the vertex does not move) and the two endpoints of list entry i: the same
-// for every lane of a workgroup / wave that shares i.
-__device__ __forceinline__ int vd_vertex(const VdMesh& M, const MsdBand& B, int64_t i, VdEnd e[2], int64_t* vid) {
-  e[0].row = e[1].row = -1;
-  e[0].dt = e[1].dt = 0.f;
+// Vertex id (-1: list entry out of range), class (0: the vertex does not move) and the two endpoints, coef = dt/ds_k, of list
+// entry i: the same for every lane of a workgroup / wave that shares i.
+__device__ __forceinline__ int vd_vertex(const VdMesh& M, const MsdBand& B, int64_t i, MsdEnd e[2], int64_t* vid) {
+  msd_no_ends(e);
   const int64_t v = M.vert_index[i];
   *vid = v >= 0 && v < M.V ? v : -1;
   if (*vid < 0) return 0;
@@ -70,33 +71,11 @@ __device__ __forceinline__ int vd_vertex(const VdMesh& M, const MsdBand& B, int6
     const float t = rn_div(rn_sub(M.level, s0), rn_sub(s1, s0));
     if (!(t >= M.t_clamp && t <= rn_sub(1.f, M.t_clamp))) return 0;      // held by the clamp
   }
-  const float d = s1 - s0, dd = d * d;
-  const float dt[2] = {(M.level - s1) / dd, -(M.level - s0) / dd};
+  float dt[2];
+  msd_dt(M.level, s0, s1, dt);
   const int64_t g[2] = {p, q};
-  for (int k = 0; k < 2; ++k) {
-    const int64_t r = M.band_of[g[k]];
-    if (r < 0 || r >= B.nb || !B.m[r]) continue;
-    int b = B.base[r];
-    if (b < 0 || b >= B.ncp_total) continue;
-    bool ok = true;
-    for (int x = 0; x < 3; ++x) {
-      const int n = B.ncp[x];
-      e[k].first[x] = x < 2 ? b % n : b;
-      b /= n;
-      ok = ok && e[k].first[x] + B.deg[x] < n;
-    }
-    if (!ok) continue;
-    e[k].row = r;
-    e[k].dt = dt[k];
-  }
+  msd_ends(B, M.band_of, g, dt, e);
   return c;
-}
-
-__device__ __forceinline__ MsdEnd vd_as_msd(const VdEnd& e) {
-  MsdEnd m;
-  m.coef = e.dt; m.row = e.row;
-  m.first[0] = e.first[0]; m.first[1] = e.first[1]; m.first[2] = e.first[2];
-  return m;
 }
 
 __global__ __launch_bounds__(MSD_BLOCK) void vd_jvp_kernel(VdMesh M, MsdBand B, const float* __restrict__ d_cp,
@@ -104,65 +83,43 @@ __global__ __launch_bounds__(MSD_BLOCK) void vd_jvp_kernel(VdMesh M, MsdBand B, 
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * (MSD_BLOCK / 64) + (threadIdx.x >> 6);
   if (i >= M.Vm) return;                                     // (no barrier below)
-  VdEnd e[2];
+  MsdEnd e[2];
   int64_t v;
   const int c = vd_vertex(M, B, i, e, &v);
   if (v < 0) return;
   float dot[2] = {0.f, 0.f};
   for (int k = 0; k < 2; ++k) {
     if (e[k].row < 0) continue;                              // wave-uniform
-    float acc = msd_end_dot(B, vd_as_msd(e[k]), d_cp, lane, 64);
+    float acc = msd_end_dot(B, e[k], d_cp, lane, 64);
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     dot[k] = acc;
   }
   if (lane < 3) {
     float tot = 0.f;
     for (int k = 0; k < 2; ++k)
-      if (e[k].row >= 0) tot = fmaf(rn_mul(M.scale[lane], e[k].dt), dot[k], tot);
+      if (e[k].row >= 0) tot = fmaf(rn_mul(M.scale[lane], e[k].coef), dot[k], tot);
     d_verts[v * 3 + lane] = ((c >> lane) & 1) ? tot : 0.f;
   }
 }
 
+// The volume's part of msd_vjp_part: its list is the moving vertices, and endpoint k of entry i adds f = rn(gs * dt/ds_k) times
+// the walk's products, gs = sum over flagged b, increasing, of rn(scale[b] * grad_verts[v, b]).  An entry that does not move has
+// class 0 and no endpoint: nothing of grad_verts is read for it.
+__device__ __forceinline__ int64_t msd_vjp_count(const VdMesh& M) { return M.Vm; }
+
+__device__ __forceinline__ void msd_vjp_ends(const VdMesh& M, const MsdBand& B, int64_t i, const float* __restrict__ grad_verts,
+                                             MsdEnd e[2]) {
+  int64_t v;
+  const int c = vd_vertex(M, B, i, e, &v);
+  float gs = 0.f;
+  for (int b = 0; b < 3; ++b)
+    if ((c >> b) & 1) gs = rn_add(gs, rn_mul(M.scale[b], grad_verts[v * 3 + b]));
+  for (int k = 0; k < 2; ++k) e[k].coef = rn_mul(gs, e[k].coef);
+}
+
 __global__ __launch_bounds__(MSD_BLOCK) void vd_vjp_part_kernel(VdMesh M, MsdBand B, const float* __restrict__ grad_verts,
                                                                 float* __restrict__ part) {
-  __shared__ float acc[MSD_VJP_TILE];
-  const int tid = threadIdx.x;
-  const int64_t per = (int64_t)B.ncp_total * B.L;
-  const int64_t tile0 = (int64_t)blockIdx.y * MSD_VJP_TILE;
-  const int tn = (int)((per - tile0) < (int64_t)MSD_VJP_TILE ? (per - tile0) : (int64_t)MSD_VJP_TILE);
-  for (int t = tid; t < tn; t += MSD_BLOCK) acc[t] = 0.f;
-  __syncthreads();
-  const int64_t i0 = (int64_t)blockIdx.x * MSD_VJP_VERTS;
-  const int64_t i1 = i0 + MSD_VJP_VERTS < M.Vm ? i0 + MSD_VJP_VERTS : M.Vm;
-  const int d0 = B.deg[0] + 1, d1 = B.deg[1] + 1, d2 = B.deg[2] + 1;
-  const int L = B.L, total = d0 * d1 * d2 * L;
-  for (int64_t i = i0; i < i1; ++i) {                        // every bound and branch around the barriers is workgroup-uniform
-    VdEnd e[2];
-    int64_t v;
-    const int c = vd_vertex(M, B, i, e, &v);
-    if (e[0].row < 0 && e[1].row < 0) continue;              // uniform: nothing to add, no barrier needed
-    float gs = 0.f;
-    for (int b = 0; b < 3; ++b)
-      if ((c >> b) & 1) gs = rn_add(gs, rn_mul(M.scale[b], grad_verts[v * 3 + b]));
-    for (int k = 0; k < 2; ++k) {
-      if (e[k].row >= 0) {
-        const float f = rn_mul(gs, e[k].dt);
-        const float* __restrict__ w = B.w + e[k].row * MS_WEIGHTS;
-        const float* __restrict__ G = B.G + e[k].row * B.ldg;
-        for (int t = tid; t < total; t += MSD_BLOCK) {
-          const int s = t / L, l = t - s * L;
-          const int ii = s % d0, sr = s / d0;
-          const int j = sr % d1, kk = sr / d1;
-          const int cp = (e[k].first[0] + ii) + B.ncp[0] * ((e[k].first[1] + j) + B.ncp[1] * (e[k].first[2] + kk));
-          const int64_t at = (int64_t)cp * L + l - tile0;
-          if (at >= 0 && at < tn) acc[at] = fmaf(f, rn_mul(w[(kk * 4 + j) * 4 + ii], G[l]), acc[at]);
-        }
-      }
-      __syncthreads();
-    }
-  }
-  float* __restrict__ out = part + (int64_t)blockIdx.x * per + tile0;
-  for (int t = tid; t < tn; t += MSD_BLOCK) out[t] = acc[t];
+  msd_vjp_part(M, B, grad_verts, part);
 }
 
 struct VdProject { float stretch[3]; float clip; };
@@ -172,14 +129,14 @@ struct VdProject { float stretch[3]; float clip; };
 // consecutive columns of one plane.
 __global__ __launch_bounds__(MSD_BLOCK) void vd_dtheta_kernel(VdMesh M, MsdBand B, const float* __restrict__ normals, VdProject P,
                                                               float* __restrict__ out, int vpw) {
-  __shared__ VdEnd end_s[VD_DENSE_VERTS][2];
+  __shared__ MsdEnd end_s[VD_DENSE_VERTS][2];
   __shared__ int class_s[VD_DENSE_VERTS];
   __shared__ float n_s[VD_DENSE_VERTS][4];                   // the normal and n . n (0: the row is zero)
   const int tid = threadIdx.x;
   const int64_t i0 = (int64_t)blockIdx.x * vpw;
   const int nv = (int)((M.Vm - i0) < (int64_t)vpw ? (M.Vm - i0) : (int64_t)vpw);
   if (tid < nv) {
-    VdEnd e[2];
+    MsdEnd e[2];
     int64_t v;
     const int c = vd_vertex(M, B, i0 + tid, e, &v);
     end_s[tid][0] = e[0];
@@ -196,16 +153,16 @@ __global__ __launch_bounds__(MSD_BLOCK) void vd_dtheta_kernel(VdMesh M, MsdBand 
   for (uint32_t t = tid; t < total; t += MSD_BLOCK) {
     const uint32_t vl = t / R, r = t - vl * R;
     const uint32_t cpi = r / L, l = r - cpi * L;
-    const int ci = (int)(cpi % (uint32_t)B.ncp[0]), cr = (int)(cpi / (uint32_t)B.ncp[0]);
-    const int cj = cr % B.ncp[1], ck = cr / B.ncp[1];
+    int ci[3];
+    msd_split(B, cpi, ci);
     const int c = class_s[vl];
     float T = 0.f;
     for (int k = 0; k < 2; ++k) {
-      const VdEnd& e = end_s[vl][k];
+      const MsdEnd& e = end_s[vl][k];
       if (e.row < 0) continue;
-      const int ii = ci - e.first[0], j = cj - e.first[1], kk = ck - e.first[2];
-      if (ii < 0 || ii > B.deg[0] || j < 0 || j > B.deg[1] || kk < 0 || kk > B.deg[2]) continue;
-      T = rn_add(T, rn_mul(rn_mul(e.dt, B.w[e.row * MS_WEIGHTS + (kk * 4 + j) * 4 + ii]), B.G[e.row * B.ldg + l]));
+      const int s = msd_slot(B, e, ci);
+      if (s < 0) continue;
+      T = rn_add(T, rn_mul(rn_mul(e.coef, B.w[e.row * MS_WEIGHTS + s]), B.G[e.row * B.ldg + l]));
     }
     const float nn = n_s[vl][3];
     float nj = 0.f;

@@ -29,8 +29,9 @@ import contextlib
 import ctypes as C
 import logging
 import math
+import operator
 import time
-from typing import TypedDict
+from typing import NamedTuple, TypedDict
 
 import numpy as np
 import torch
@@ -705,27 +706,98 @@ def _free_device_memory(device):
     return torch.cuda.mem_get_info(device)[0]
 
 
-class MicrostructureMeshDiff:
-    """A microstructure mesh with its derivative with respect to the spline's control points (microstructure_mesh_diff).
+def _check_fits(device, what, shape, advice):
+    """Raise MemoryError, stating the size, when an fp32 array of `shape` would not fit the free device memory."""
+    need = 4 * int(np.prod(shape, dtype=np.int64))
+    free = _free_device_memory(device)
+    if need > free:
+        raise MemoryError(f"{what} {list(shape)} fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB), the device has {free} bytes "
+                          f"free: {advice}")
 
-    verts [V, 3] float64 and faces [F, 3] int32 (device) are create_mesh_microstructure's; edge_point [V] int64 / edge_axis [V] int32
-    name the padded-grid edge of every vertex.  Only coordinate edge_axis[v] of vertex v depends on the control points."""
 
-    def __init__(self, verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale,
-                 voxel_size=None):
-        self.verts, self.faces, self.edge_point, self.edge_axis = verts, faces, edge_point, edge_axis
-        self.voxel_size = None if voxel_size is None else [float(v) for v in voxel_size]      # the grid's spacing before (v - vs) / 2
-        self.grid, self.band, self.band_of = grid, band, band_of
-        self.G, self.weights, self.base, self.mask = G, weights, base, mask
-        self.n_control_points, self.latent_size = int(field.control_points.shape[0]), int(field.latent_size)
-        self._degrees = [int(d) for d in field.degrees]
-        self._n_cp = [int(n) for n in field.control_mesh_resolutions]
-        self._scale = scale
-        self._rows_of = None                                # microstructure_mesh_diff: band -> its rows, for for_tetmesh
+class _Band(NamedTuple):
+    """The grid points that carry an endpoint of a vertex's edge, and what the derivative reads at each (_band_rows)."""
+    band: torch.Tensor                                      # [nb] int64 grid indices, sorted
+    band_of: torch.Tensor                                   # [npts] int32 grid index -> band row, -1 off the band
+    G: torch.Tensor                                         # [nb, L] d sdf / d latent
+    weights: torch.Tensor                                   # [nb, 64] basis weights of the row kernel
+    base: torch.Tensor                                      # [nb] int32 first control point, -1: outside
+    mask: torch.Tensor                                      # [nb] uint8 inside and capped value == raw value
+
+
+class _MeshDiff:
+    """What the surface's and the volume's derivative share: the band's tensors as attributes, and the marshalling of vjp and jvp
+    around the entries dsdf_<_entry>_*.  A subclass has grid, _band, _degrees, _n_cp, _structs() -> (mesh struct, band struct),
+    _n_rows (the rows of grad_verts and d_verts) and _n_list (the vertices its adjoint walks)."""
+    band, band_of, G, weights, base, mask = (property(operator.attrgetter("_band." + k)) for k in _Band._fields)
 
     @property
     def device(self):
         return self.grid.device
+
+    def _band_struct(self):
+        b, G, L = _lib.DsdfMsdBand(), self.G, self.latent_size
+        b.G, b.weights, b.base, b.mask = (t.data_ptr() for t in (G, self.weights, self.base, self.mask))
+        b.n_band, b.ld_g, b.L = G.shape[0], G.stride(0) if G.shape[0] > 0 else L, L
+        for a in range(3):
+            b.degree[a], b.n_cp[a] = self._degrees[a], self._n_cp[a]
+        return b
+
+    def _call(self, entry, *args):
+        m, b = self._structs()
+        _lib.check(getattr(_lib.lib(), f"dsdf_{self._entry}_{entry}")(C.byref(m), C.byref(b), *args, _lib.stream()))
+
+    def _operand(self, x, name, shape):
+        x = torch.as_tensor(x).to(self.device, torch.float32).contiguous()
+        if x.shape != shape:
+            raise ValueError(f"{name} must be [{shape[0]}, {shape[1]}], got {tuple(x.shape)}")
+        return x
+
+    def vjp_plan(self):
+        """(scratch bytes, partial sums of the first stage) of vjp (dsdf_msd_ / dsdf_vd_vjp_workspace_bytes)."""
+        nbytes, parts = C.c_size_t(), C.c_int32()
+        plan = getattr(_lib.lib(), f"dsdf_{self._entry}_vjp_workspace_bytes")
+        _lib.check(plan(self._n_list, self.n_control_points, self.latent_size, C.byref(nbytes), C.byref(parts)))
+        return nbytes.value, parts.value
+
+    def vjp(self, grad_verts):
+        """grad_verts [V, 3] -> grad_cp [ncp, L] fp32 = sum_v sum_b grad_verts[v, b] * J[v, b]: a fixed-order two-stage sum.  The
+        surface: b is the vertex's edge axis.  The volume: over the moving vertices; rows of grid vertices are never read."""
+        gv = self._operand(grad_verts, "grad_verts", (self._n_rows, 3))
+        with torch.cuda.device(self.device):
+            ws = torch.empty(max(self.vjp_plan()[0], 256), dtype=torch.uint8, device=self.device)
+            out = torch.empty(self.n_control_points, self.latent_size, dtype=torch.float32, device=self.device)
+            self._call("vjp", _lib.ptr(gv), _lib.ptr(out), _lib.ptr(ws), ws.numel())
+        return out
+
+    def jvp(self, d_cp):
+        """d_cp [ncp, L] -> d_verts [V, 3] fp32.  The surface: zero off each vertex's edge axis.  The volume: every flagged
+        coordinate of a moving vertex, zero everywhere else."""
+        d = self._operand(d_cp, "d_cp", (self.n_control_points, self.latent_size))
+        with torch.cuda.device(self.device):
+            out = torch.empty(self._n_rows, 3, dtype=torch.float32, device=self.device)
+            self._call("jvp", _lib.ptr(d), _lib.ptr(out))
+        return out
+
+
+class MicrostructureMeshDiff(_MeshDiff):
+    """A microstructure mesh with its derivative with respect to the spline's control points (microstructure_mesh_diff).
+
+    verts [V, 3] float64 and faces [F, 3] int32 (device) are create_mesh_microstructure's; edge_point [V] int64 / edge_axis [V] int32
+    name the padded-grid edge of every vertex.  Only coordinate edge_axis[v] of vertex v depends on the control points.  band,
+    band_of, G, weights, base, mask: the band of the vertices' edges (_Band)."""
+    _entry = "msd"
+
+    def __init__(self, verts, faces, edge_point, edge_axis, grid, band, field, scale, voxel_size=None):
+        self.verts, self.faces, self.edge_point, self.edge_axis = verts, faces, edge_point, edge_axis
+        self.voxel_size = None if voxel_size is None else [float(v) for v in voxel_size]      # the grid's spacing before (v - vs) / 2
+        self.grid, self._band = grid, band
+        self.n_control_points, self.latent_size = int(field.control_points.shape[0]), int(field.latent_size)
+        self._degrees = [int(d) for d in field.degrees]
+        self._n_cp = [int(n) for n in field.control_mesh_resolutions]
+        self._scale = scale
+        self._n_rows = self._n_list = int(verts.shape[0])
+        self._rows_of = None                                # microstructure_mesh_diff: band indices -> _Band, for for_tetmesh
 
     def for_tetmesh(self, tet, t_clamp=0.0):
         """-> VolumeMeshDiff: the derivative of every moving vertex of `tet`, a TetMesh made from self.grid with
@@ -735,15 +807,12 @@ class MicrostructureMeshDiff:
         return _volume_mesh_diff(self, tet, t_clamp)
 
     def _structs(self):
-        m, b = _lib.DsdfMsdMesh(), _lib.DsdfMsdBand()
+        m = _lib.DsdfMsdMesh()
         m.grid, m.edge_point, m.edge_axis, m.band_of = (t.data_ptr() for t in (self.grid, self.edge_point, self.edge_axis, self.band_of))
         m.n_verts, m.level = self.verts.shape[0], 0.0
-        b.G, b.weights, b.base, b.mask = (t.data_ptr() for t in (self.G, self.weights, self.base, self.mask))
-        b.n_band, b.ld_g, b.L = self.G.shape[0], self.G.stride(0) if self.G.shape[0] > 0 else self.latent_size, self.latent_size
         for a in range(3):
             m.dims[a], m.scale[a] = self.grid.shape[a], self._scale[a]
-            b.degree[a], b.n_cp[a] = self._degrees[a], self._n_cp[a]
-        return m, b
+        return m, self._band_struct()
 
     def jacobian(self, dense=False):
         """dense=False: (jac [V, ncp, L] fp32, axis [V] int32), jac[v] = d verts[v, axis[v]] / d control points.  dense=True: the
@@ -751,49 +820,12 @@ class MicrostructureMeshDiff:
         array would not fit the free device memory."""
         V, ncp, L = self.verts.shape[0], self.n_control_points, self.latent_size
         shape = (V, 3, ncp, L) if dense else (V, ncp, L)
-        need = 4 * int(np.prod(shape, dtype=np.int64))
-        free = _free_device_memory(self.device)
-        if need > free:
-            raise MemoryError(f"the Jacobian {list(shape)} fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB), the device has {free} "
-                              f"bytes free: use vjp / jvp, or dense=False" + ("" if dense else " with a coarser grid"))
+        _check_fits(self.device, "the Jacobian", shape, "use vjp / jvp, or dense=False" + ("" if dense else " with a coarser grid"))
         with torch.cuda.device(self.device):
             jac = torch.empty(shape, dtype=torch.float32, device=self.device)
             axis = torch.empty(V, dtype=torch.int32, device=self.device)
-            m, b = self._structs()
-            _lib.check(_lib.lib().dsdf_msd_jacobian(C.byref(m), C.byref(b), int(bool(dense)), _lib.ptr(jac), _lib.ptr(axis), _lib.stream()))
+            self._call("jacobian", int(bool(dense)), _lib.ptr(jac), _lib.ptr(axis))
         return jac if dense else (jac, axis)
-
-    def vjp_plan(self):
-        """(scratch bytes, partial sums of the first stage) of vjp (dsdf_msd_vjp_workspace_bytes)."""
-        nbytes, parts = C.c_size_t(), C.c_int32()
-        _lib.check(_lib.lib().dsdf_msd_vjp_workspace_bytes(self.verts.shape[0], self.n_control_points, self.latent_size,
-                                                           C.byref(nbytes), C.byref(parts)))
-        return nbytes.value, parts.value
-
-    def vjp(self, grad_verts):
-        """grad_verts [V, 3] -> grad_cp [ncp, L] fp32 = sum_v grad_verts[v, a(v)] * J[v]: a fixed-order two-stage sum."""
-        gv = torch.as_tensor(grad_verts).to(self.device, torch.float32).contiguous()
-        V = self.verts.shape[0]
-        if gv.shape != (V, 3):
-            raise ValueError(f"grad_verts must be [{V}, 3], got {tuple(gv.shape)}")
-        with torch.cuda.device(self.device):
-            lib = _lib.lib()
-            ws = torch.empty(max(self.vjp_plan()[0], 256), dtype=torch.uint8, device=self.device)
-            out = torch.empty(self.n_control_points, self.latent_size, dtype=torch.float32, device=self.device)
-            m, b = self._structs()
-            _lib.check(lib.dsdf_msd_vjp(C.byref(m), C.byref(b), _lib.ptr(gv), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream()))
-        return out
-
-    def jvp(self, d_cp):
-        """d_cp [ncp, L] -> d_verts [V, 3] fp32 (zero off each vertex's edge axis)."""
-        d = torch.as_tensor(d_cp).to(self.device, torch.float32).contiguous()
-        if d.shape != (self.n_control_points, self.latent_size):
-            raise ValueError(f"d_cp must be [{self.n_control_points}, {self.latent_size}], got {tuple(d.shape)}")
-        with torch.cuda.device(self.device):
-            out = torch.empty(self.verts.shape[0], 3, dtype=torch.float32, device=self.device)
-            m, b = self._structs()
-            _lib.check(_lib.lib().dsdf_msd_jvp(C.byref(m), C.byref(b), _lib.ptr(d), _lib.ptr(out), _lib.stream()))
-        return out
 
 
 def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_border_dict=None, device=None, *, block=None,
@@ -837,18 +869,17 @@ def microstructure_mesh_diff(tiling, decoder, field, N, max_batch=32 ** 3, cap_b
 
         def rows_of(band):
             return _band_rows(band, dec, hip, field, tiling, n, max_batch, raw, grid)
-        band_of, G, weights, base, mask = rows_of(band)
+        band = rows_of(band)
     scale = [float(np.float32(v / 2)) for v in voxel_size]
-    d = MicrostructureMeshDiff(verts, faces, edge_point, edge_axis, grid, band, band_of, G, weights, base, mask, field, scale,
-                               voxel_size)
+    d = MicrostructureMeshDiff(verts, faces, edge_point, edge_axis, grid, band, field, scale, voxel_size)
     d._rows_of = rows_of                                   # for_tetmesh: the volume mesh's band goes through the same loop
     return d
 
 
 def _band_rows(band, dec, hip, field, tiling, n, max_batch, raw, grid):
-    """band [nb] sorted grid indices -> (band_of [npts] int32, G [nb, L], weights [nb, 64], base [nb], mask [nb] uint8): per chunk of
-    max_batch band points the rows at the band indices, the decoder's forward and its input gradient; mask = inside and capped
-    value == raw value (microstructure_mesh_diff's band loop; the volume mesh's band runs it again on its own points)."""
+    """band [nb] sorted grid indices -> _Band: per chunk of max_batch band points the rows at the band indices, the decoder's forward
+    and its input gradient; mask = inside and capped value == raw value (microstructure_mesh_diff's band loop; the volume mesh's
+    band runs it again on its own points)."""
     device, npts, L = raw.device, raw.numel(), int(field.latent_size)
     with torch.cuda.device(device):
         nb = band.numel()
@@ -875,10 +906,10 @@ def _band_rows(band, dec, hip, field, tiling, n, max_batch, raw, grid):
                     G[b:e] = torch.autograd.grad(y.sum(), x)[0][:, :L]
         flat_raw, flat = raw.view(-1), grid.view(-1)
         mask = ((base >= 0) & (flat[band] == flat_raw[band])).to(torch.uint8)
-    return band_of, G, weights, base, mask
+    return _Band(band, band_of, G, weights, base, mask)
 
 
-class VolumeMeshDiff:
+class VolumeMeshDiff(_MeshDiff):
     """The derivative of a volume mesh's vertices with respect to the spline's control points (csrc/voldiff.hpp, dsdf_vd_*;
     DESIGN 4.22): every class >= 1 vertex of tetmesh.tetrahedralize's mesh -- the marching-cubes vertices and those on the face and
     body diagonals -- moves along its edge; grid vertices do not.  Built by MicrostructureMeshDiff.for_tetmesh.
@@ -887,92 +918,45 @@ class VolumeMeshDiff:
     derivative).  band: the sorted unique endpoints of their edges, with its own G / weights / base / mask: an endpoint of a
     crossing diagonal need not be an endpoint of a crossing axis edge, so the surface's band is not enough.  Unstretched, in the
     coordinates of MicrostructureMeshDiff.verts (scale = voxel_size / 2)."""
+    _entry = "vd"
 
-    def __init__(self, diff, tet, t_clamp, band, band_of, G, weights, base, mask):
+    def __init__(self, diff, tet, t_clamp, band):
         self.diff, self.t_clamp = diff, float(t_clamp)
-        self.grid = diff.grid
+        self.grid, self._band = diff.grid, band
         self.vert_point, self.vert_class = tet.vert_point, tet.vert_class
         self.n_verts = int(tet.verts.shape[0])
         self.moving = torch.nonzero(self.vert_class > 0).reshape(-1).to(torch.int32)          # ascending
-        self.band, self.band_of, self.G, self.weights, self.base, self.mask = band, band_of, G, weights, base, mask
         self.n_control_points, self.latent_size = diff.n_control_points, diff.latent_size
-
-    @property
-    def device(self):
-        return self.grid.device
+        self._degrees, self._n_cp = diff._degrees, diff._n_cp
+        self._n_rows, self._n_list = self.n_verts, self.moving.numel()
 
     def _structs(self, index=None):
         index = self.moving if index is None else index
-        m, b = _lib.DsdfVdMesh(), _lib.DsdfMsdBand()
+        m = _lib.DsdfVdMesh()
         m.grid, m.vert_point, m.vert_class, m.vert_index, m.band_of = (t.data_ptr() for t in (self.grid, self.vert_point, self.vert_class,
                                                                                             index, self.band_of))
         m.n_verts, m.n_moving, m.level, m.t_clamp = self.n_verts, index.numel(), 0.0, self.t_clamp
-        b.G, b.weights, b.base, b.mask = (t.data_ptr() for t in (self.G, self.weights, self.base, self.mask))
-        b.n_band, b.ld_g, b.L = self.G.shape[0], self.G.stride(0) if self.G.shape[0] > 0 else self.latent_size, self.latent_size
         for a in range(3):
             m.dims[a], m.scale[a] = self.grid.shape[a], self.diff._scale[a]
-            b.degree[a], b.n_cp[a] = self.diff._degrees[a], self.diff._n_cp[a]
-        return m, b
-
-    def vjp_plan(self):
-        """(scratch bytes, partial sums of the first stage) of vjp (dsdf_vd_vjp_workspace_bytes)."""
-        nbytes, parts = C.c_size_t(), C.c_int32()
-        _lib.check(_lib.lib().dsdf_vd_vjp_workspace_bytes(self.moving.numel(), self.n_control_points, self.latent_size,
-                                                          C.byref(nbytes), C.byref(parts)))
-        return nbytes.value, parts.value
-
-    def vjp(self, grad_verts):
-        """grad_verts [V, 3] -> grad_cp [ncp, L] fp32 = sum_v sum_b grad_verts[v, b] * J[v, b]: a fixed-order two-stage sum over
-        the moving vertices; rows of grid vertices are never read."""
-        gv = torch.as_tensor(grad_verts).to(self.device, torch.float32).contiguous()
-        if gv.shape != (self.n_verts, 3):
-            raise ValueError(f"grad_verts must be [{self.n_verts}, 3], got {tuple(gv.shape)}")
-        with torch.cuda.device(self.device):
-            ws = torch.empty(max(self.vjp_plan()[0], 256), dtype=torch.uint8, device=self.device)
-            out = torch.empty(self.n_control_points, self.latent_size, dtype=torch.float32, device=self.device)
-            m, b = self._structs()
-            _lib.check(_lib.lib().dsdf_vd_vjp(C.byref(m), C.byref(b), _lib.ptr(gv), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream()))
-        return out
-
-    def jvp(self, d_cp):
-        """d_cp [ncp, L] -> d_verts [V, 3] fp32: every flagged coordinate of a moving vertex, zero everywhere else."""
-        d = torch.as_tensor(d_cp).to(self.device, torch.float32).contiguous()
-        if d.shape != (self.n_control_points, self.latent_size):
-            raise ValueError(f"d_cp must be [{self.n_control_points}, {self.latent_size}], got {tuple(d.shape)}")
-        with torch.cuda.device(self.device):
-            out = torch.empty(self.n_verts, 3, dtype=torch.float32, device=self.device)
-            m, b = self._structs()
-            _lib.check(_lib.lib().dsdf_vd_jvp(C.byref(m), C.byref(b), _lib.ptr(d), _lib.ptr(out), _lib.stream()))
-        return out
+        return m, self._band_struct()
 
     def dtheta_moving(self, normals, stretch=(1.0, 1.0, 1.0), clip=0.0):
         """[Vm, 3, ncp * L] fp32: the (stretched, clipped) Jacobian of every moving vertex projected onto its normal
         (dsdf_vd_dtheta); normals [V, 3].  Raises MemoryError, stating the size, when the array would not fit the device."""
-        n = torch.as_tensor(normals).to(self.device, torch.float32).contiguous()
-        if n.shape != (self.n_verts, 3):
-            raise ValueError(f"normals must be [{self.n_verts}, 3], got {tuple(n.shape)}")
+        n = self._operand(normals, "normals", (self.n_verts, 3))
         Vm, R = self.moving.numel(), self.n_control_points * self.latent_size
-        need = 4 * Vm * 3 * R
-        free = _free_device_memory(self.device)
-        if need > free:
-            raise MemoryError(f"dtheta [{Vm}, 3, {R}] fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB), the device has {free} bytes "
-                              f"free: use vjp / jvp, or a coarser grid")
+        _check_fits(self.device, "dtheta", (Vm, 3, R), "use vjp / jvp, or a coarser grid")
         with torch.cuda.device(self.device):
             out = torch.empty(Vm, 3, R, dtype=torch.float32, device=self.device)
-            m, b = self._structs()
             st = (C.c_float * 3)(*[float(s) for s in stretch])
-            _lib.check(_lib.lib().dsdf_vd_dtheta(C.byref(m), C.byref(b), _lib.ptr(n), st, float(clip), _lib.ptr(out), _lib.stream()))
+            self._call("dtheta", _lib.ptr(n), st, float(clip), _lib.ptr(out))
         return out
 
     def jacobian(self):
         """[V, 3, ncp, L] fp32, for small meshes: one tangent (jvp) per column, so ncp * L launches.  Raises MemoryError, stating
         the size, when the array would not fit the free device memory."""
         V, ncp, L = self.n_verts, self.n_control_points, self.latent_size
-        need = 4 * V * 3 * ncp * L
-        free = _free_device_memory(self.device)
-        if need > free:
-            raise MemoryError(f"the Jacobian {[V, 3, ncp, L]} fp32 takes {need} bytes ({need / 2 ** 30:.2f} GiB), the device has {free} "
-                              f"bytes free: use vjp / jvp")
+        _check_fits(self.device, "the Jacobian", (V, 3, ncp, L), "use vjp / jvp")
         jac = torch.empty(V, 3, ncp * L, dtype=torch.float32, device=self.device)
         unit = torch.zeros(ncp * L, dtype=torch.float32, device=self.device)
         for r in range(ncp * L):
@@ -1001,8 +985,8 @@ def _volume_mesh_diff(diff, tet, t_clamp=0.0):
         band = torch.unique(torch.cat([p, q]))                                                  # sorted
         if band.numel() and (int(band[0]) < 0 or int(band[-1]) >= diff.grid.numel()):
             raise ValueError("the TetMesh's vertex edges leave the grid of this MicrostructureMeshDiff")
-        band_of, G, weights, base, mask = diff._rows_of(band)
-    return VolumeMeshDiff(diff, tet, t_clamp, band, band_of, G, weights, base, mask)
+        band = diff._rows_of(band)
+    return VolumeMeshDiff(diff, tet, t_clamp, band)
 
 
 def create_mesh_microstructure_diff(tiling, decoder, latent_vec_interpolation, N=256, max_batch=32 ** 3, offset=None, scale=None,
