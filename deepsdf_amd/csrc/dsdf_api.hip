@@ -2670,6 +2670,7 @@ int msd_setup(const DsdfMsdMesh* mesh, const DsdfMsdBand* band, MsdMesh* M, MsdB
   TRY(msd_band(band, mesh->n_verts > 0, mesh->grid && mesh->edge_point && mesh->edge_axis && mesh->band_of, B));
   M->grid = mesh->grid; M->edge_point = mesh->edge_point; M->edge_axis = mesh->edge_axis; M->band_of = mesh->band_of;
   M->V = mesh->n_verts; M->level = mesh->level;
+  for (int o = 0; o < 2; ++o) msd_magic(M->stride[o], &M->magic[o], &M->shift[o]);
   return 0;
 }
 

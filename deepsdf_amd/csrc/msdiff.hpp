@@ -19,7 +19,11 @@
 //                        control points, so the adds of one step never collide, and a barrier separates the steps (a vertex with
 //                        no valid endpoint is skipped by the whole workgroup): no atomics, a fixed order.  msd_vjp_sum_kernel adds
 //                        the parts in part order.
-// A vertex whose edge, band row or base index is out of range contributes nothing (nothing is read or written out of bounds).
+// A vertex whose edge, band row or base index is out of range contributes nothing (nothing is read or written out of bounds).  An
+// edge (p, a) is in range iff 0 <= a <= 2, 0 <= p < npts and p's index along a is below dims[a] - 1 -- the volume's rule
+// (vd_vertex): an edge at the last index of axis 1 or 2, whose p + stride[a] is the first point of the next row, is refused like
+// one that leaves the grid.  An endpoint is in range iff its band_of row lies in 0 .. nb - 1, its mask is set, 0 <= base < ncp and
+// first[x] + deg[x] < n_cp[x] on every axis.
 //
 // Shared with the volume mesh's derivative (voldiff.hpp), defined here once: the endpoint record MsdEnd, msd_dt (the dt pair),
 // msd_ends (band row, mask, base, support check -> the two records; the caller has found p and q valid by its own rule and supplies
@@ -47,9 +51,21 @@ struct MsdMesh {
   const int32_t* edge_axis;            // [V]
   const int32_t* band_of;              // [npts] grid index -> band row, < 0: not in the band
   int64_t npts, stride[3], V;
+  uint32_t magic[2];                   // floor(p / stride[o]) = (p * magic[o]) >> shift[o] for every 0 <= p < 2^30, o = 0, 1 (msd_magic)
+  int shift[2];
   float scale[3];                      // voxel_size / 2
   float level;
 };
+
+// The multiplier and shift of an exact division of a 30-bit number by d, 2 <= d <= 2^30 [host]: with l = ceil(log2 d), k = 30 + l and
+// m = ceil(2^k / d) one has 2^k <= m d < 2^k + 2^l = 2^k + 2^(k - 30), so floor(p m / 2^k) = floor(p / d) for 0 <= p < 2^30
+// (Granlund and Montgomery 1994, theorem 4.2); m <= 2^31, and p m < 2^61 fits 64 bits.
+inline void msd_magic(int64_t d, uint32_t* magic, int* shift) {
+  int l = 0;
+  while (((int64_t)1 << l) < d) ++l;
+  *shift = 30 + l;
+  *magic = (uint32_t)((((uint64_t)1 << *shift) + (uint64_t)d - 1) / (uint64_t)d);
+}
 
 struct MsdBand {
   const float* G;                      // [nb][ldg]: the first L columns are d sdf / d latent
@@ -102,9 +118,17 @@ __device__ __forceinline__ int msd_vertex(const MsdMesh& M, const MsdBand& B, in
   msd_no_ends(e);
   const int a = M.edge_axis[v];
   const int64_t p = M.edge_point[v];
-  if (a < 0 || a > 2 || p < 0) return a < 0 || a > 2 ? 0 : a;
+  if (a < 0 || a > 2 || p < 0 || p >= M.npts) return a < 0 || a > 2 ? 0 : a;
+  // The volume's rule (vd_vertex): the far endpoint lies past the grid along a iff p's index along a is the last one, that is iff
+  // p's offset within one step of the next slower axis (the whole grid for a = 0) plus stride[a] leaves that step.  The offset
+  // p mod stride[a - 1] comes from the host's multiplier (MsdMesh::magic): a division per vertex on this path, the head of the chain
+  // of dependent reads that sets the adjoint's time per vertex, cost the surface adjoint 3 %.
+  const int o = a > 0 ? a - 1 : 0;
+  const uint32_t pu = (uint32_t)p, d = (uint32_t)M.stride[o];                                      // npts <= 2^30
+  const uint32_t outer = a > 0 ? d : (uint32_t)M.npts;
+  const uint32_t off = a > 0 ? pu - (uint32_t)(((uint64_t)pu * M.magic[o]) >> M.shift[o]) * d : pu;
+  if (off + (uint32_t)M.stride[a] >= outer) return a;
   const int64_t q = p + M.stride[a];
-  if (q >= M.npts) return a;
   float dt[2];
   msd_dt(M.level, M.grid[p], M.grid[q], dt);
   const int64_t g[2] = {p, q};

@@ -525,7 +525,11 @@ int dsdf_ms_rows_at(const DsdfMsSpline* spline, const DsdfMsGrid* grid, const in
  *   dt/ds0 = (level - s1) / (s1 - s0)^2,  dt/ds1 = -(level - s0) / (s1 - s0)^2  (fp32, from the two values marching cubes read)
  * where k names the band row band_of[p] / band_of[p + e_a].  Band row r carries G [r][0 .. L) = d sdf / d latent at the row the
  * forward decoded, the weights and base of dsdf_ms_rows_at, and mask (1: inside and the caps left the decoder's value).
- * A vertex whose edge, band row or base is out of range gets zeros; nothing is read out of bounds for in-range arrays.
+ * A vertex whose edge, band row or base is out of range gets zeros; nothing is read out of bounds for in-range arrays.  In range:
+ * an edge with 0 <= a <= 2, 0 <= p < npts and p's index along axis a below dims[a] - 1 (the rule of dsdf_vd_* below: an edge at
+ * the last index of an axis is refused on every axis, also where p + e_a would be the first point of the next row); an endpoint
+ * whose band_of row lies in 0 .. n_band - 1, with mask != 0, 0 <= base < ncp and base's index + degree < n_cp on every axis.  A
+ * vertex out of range reports axis a when 0 <= a <= 2 and axis 0 otherwise.
  *   dsdf_msd_jacobian  jac [n_verts][ncp][L] and axis [n_verts] (may be NULL); full != 0: jac [n_verts][3][ncp][L], the two other
  *                      coordinates' planes written as zeros (the reference's layout)
  *   dsdf_msd_jvp       d_cp [ncp][L] -> d_verts [n_verts][3] (zeros off the edge axis)

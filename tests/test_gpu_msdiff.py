@@ -1,7 +1,11 @@
 """-m gpu: d(mesh vertices) / d(spline control points) of a microstructure mesh.  The vertex edges of marching cubes, the rows at a
 list of grid indices, the input gradient without weight gradients, the assembled Jacobian against the fp64 reference of
 tests/msdiff_numpy.py (whose formula tests/test_msdiff_cpu.py pins against autograd), an analytic module, the adjoint and the
-tangent against the GPU's own dense Jacobian, and the public interface."""
+tangent against the GPU's own dense Jacobian, and the public interface.
+
+The kernel level -- dsdf_msd_jacobian / dsdf_msd_jvp / dsdf_msd_vjp on a synthetic band against an fp64 specification of their own, entry
+by entry at bounds counted from the kernels, every form of the dense kernel, part and tile boundaries of the adjoint, entries out of
+range -- is tests/test_gpu_msdiff_kernels.py."""
 import ctypes as C
 import math
 import os

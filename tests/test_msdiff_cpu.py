@@ -203,3 +203,119 @@ def test_public_names_and_signature():
     assert sig.parameters["N"].default == 256 and sig.parameters["max_batch"].default == 32 ** 3
     with pytest.raises(NotImplementedError):
         create_mesh_microstructure_diff([1, 1, 1], None, None, output_tetmesh=True)
+
+
+# ---- the kernel-level tests' oracle, inputs and wrong variants (tests/test_gpu_msdiff_kernels.py runs them on the GPU) ----------------
+SCALE = np.asarray(msdiff_numpy.SPACING, dtype=np.float32) / 2
+
+
+@pytest.fixture(scope="module")
+def surface_cases():
+    """{case: (degrees, n_cp, L, sb, spec, contractions)} on the 6 x 5 x 4 grid, computed once and left unchanged."""
+    grid = msdiff_numpy.seeded_grid()
+    ep, ea = msdiff_numpy.edges(grid)
+    out = {}
+    for case, (degrees, n_cp, L) in msdiff_numpy.CASES.items():
+        sb = msdiff_numpy.surface_band(grid.shape, ep, ea, degrees, n_cp, L)
+        spec = msdiff_numpy.surface_spec(grid, ep, ea, sb, degrees, n_cp, SCALE)
+        w, dcp = msdiff_numpy.contraction_inputs(len(ep), int(np.prod(n_cp)), L)
+        out[case] = (degrees, n_cp, L, sb, spec, msdiff_numpy.contractions(spec, w, dcp))
+    return grid, ep, ea, out
+
+
+@pytest.mark.parametrize("case", list(msdiff_numpy.CASES))
+def test_the_two_fp64_oracles_agree(surface_cases, case):
+    """msdiff_numpy.jacobian (the formula pinned against autograd above) and scale * voldiff_numpy.tangent on classes 1 << axis (what
+    the kernel-level tests compare the GPU with): a few fp64 operations per entry on both sides."""
+    grid, ep, ea, cases = surface_cases
+    degrees, n_cp, L, sb, spec, _ = cases[case]
+    band, _, _ = msdiff_numpy.band(ep, ea, grid.shape)
+    assert np.array_equal(band, sb["band"])
+    B, support = msdiff_numpy.scatter_weights(sb["weights"], sb["base"], sb["base"] >= 0, degrees, n_cp)
+    assert np.array_equal(B, sb["B"]) and np.array_equal(support, sb["support"])
+    J, axis = msdiff_numpy.jacobian(grid, ep, ea, msdiff_numpy.SPACING, sb["G"], sb["B"], sb["mask"])
+    assert np.array_equal(axis, spec["axis"]) and J.shape == spec["J"].shape == (len(ep), int(np.prod(n_cp)), L)
+    worst = float(np.abs(J - spec["J"]).max() / np.abs(J).max())
+    print(f"{case}: jacobian against scale * tangent, worst difference {worst:.2e} of max |J| (bound 1e-14)")
+    assert worst <= 1e-14
+    assert not spec["J"][spec["Jabs"] == 0].any() and (np.abs(spec["J"]) <= spec["Jabs"]).all()
+
+
+@pytest.mark.parametrize("case", list(msdiff_numpy.CASES))
+def test_the_kernel_level_inputs_carry_the_edges(surface_cases, case):
+    from tests import ws_guard
+    grid, ep, ea, cases = surface_cases
+    degrees, n_cp, L, sb, spec, _ = cases[case]
+    V = len(ep)
+    assert grid.shape == (6, 5, 4) and V == 143 and np.bincount(ea).tolist() == [51, 44, 48]
+    _, r0, r1 = msdiff_numpy.band(ep, ea, grid.shape)
+    one_masked = (sb["mask"][r0] == 0) != (sb["mask"][r1] == 0)
+    outside = (sb["base"][r0] < 0) | (sb["base"][r1] < 0)
+    none = ~spec["end"].any(1)
+    print(f"{case}: {int(one_masked.sum())} vertices with one masked endpoint, {int(outside.sum())} with an endpoint outside the domain, "
+          f"{int(none.sum())} with no valid endpoint")
+    assert one_masked.sum() >= 18 and outside.sum() >= 13 and none.sum() >= 3
+    assert not spec["Jabs"][none].any() and spec["vert"].all()
+    assert sb["weights"][sb["base"] < 0].any(1).all()                       # rows outside the domain carry weights nobody may read
+    K = ws_guard.constants()
+    assert (K["MSD_DENSE_STORES"], K["MSD_DENSE_VERTS"], K["MSD_VJP_VERTS"], K["MSD_VJP_TILE"]) == (2048, 64, 512, 8192)
+    assert V % 34 == 7 and V % 64 == 15 and V % 21 == 17                    # the dense kernel's last workgroup is short (vpw 34, 64, 21)
+    if case == "deg313_L128":
+        assert int(np.prod(n_cp)) * L == 10240 > K["MSD_VJP_TILE"]
+    big = msdiff_numpy.edges(msdiff_numpy.seeded_grid((9, 9, 9)))[0]
+    assert len(big) == 966 > K["MSD_VJP_VERTS"]
+
+
+def _misses(grid, ep, ea, sb, degrees, n_cp, L, variant):
+    """How far a wrong variant lies from the specification, in units of the GPU bound at the entry, for dense / jvp / vjp; computed
+    from the oracle alone."""
+    spec = msdiff_numpy.surface_spec(grid, ep, ea, sb, degrees, n_cp, SCALE)
+    wrong = msdiff_numpy.surface_spec(grid, ep, ea, sb, degrees, n_cp, SCALE, variant=variant)
+    w, dcp = msdiff_numpy.contraction_inputs(len(ep), int(np.prod(n_cp)), L)
+    c, cw = msdiff_numpy.contractions(spec, w, dcp), msdiff_numpy.contractions(wrong, w, dcp)
+    parts = -(-len(ep) // 512)
+    pairs = {"dense": (wrong["J"], spec["J"], msdiff_numpy.dense_bound(spec["Jabs"])),
+             "jvp": (cw["jvp"][0], c["jvp"][0], msdiff_numpy.jvp_bound(degrees, L, c["jvp"][1])),
+             "vjp": (cw["vjp"][0], c["vjp"][0], msdiff_numpy.vjp_bound(c["n_terms"], parts, c["vjp"][1]))}
+    out = {}
+    for what, (a, b, bound) in pairs.items():
+        d = np.abs(a - b)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[what] = float(np.max(np.where(d > 0, d / bound, 0.0)))       # a miss where the bound is zero: inf
+    return out
+
+
+@pytest.mark.parametrize("case", list(msdiff_numpy.CASES))
+def test_every_wrong_variant_misses_the_specification(surface_cases, case):
+    grid, ep, ea, cases = surface_cases
+    degrees, n_cp, L, sb, _, _ = cases[case]
+    bad = msdiff_numpy.invalid_entries(grid, ep, ea, sb, degrees, n_cp)
+    for variant in msdiff_numpy.VARIANTS:
+        healthy = _misses(grid, ep, ea, sb, degrees, n_cp, L, variant)
+        invalid = _misses(grid, bad[0], bad[1], bad[2], degrees, n_cp, L, variant)
+        print(f"{case} {variant}: worst miss / bound on the healthy input {healthy}, with entries out of range {invalid}")
+        if variant == "wrapped_edge_counts":
+            assert set(healthy.values()) == {0.0}                           # marching cubes emits no such edge: the same on valid meshes
+        else:
+            assert min(healthy.values()) > 1e3, (variant, healthy)
+        assert min(invalid.values()) > 1e3, (variant, invalid)
+
+
+@pytest.mark.parametrize("case", list(msdiff_numpy.CASES))
+def test_entries_out_of_range_in_the_oracle(surface_cases, case):
+    """The input of the GPU test of entries out of range: what is written over, and what the entry rule makes of it."""
+    grid, ep, ea, cases = surface_cases
+    degrees, n_cp, L, sb, spec, _ = cases[case]
+    bp, ba, bsb, touched, zero = msdiff_numpy.invalid_entries(grid, ep, ea, sb, degrees, n_cp)
+    npts, nb, ncp = grid.size, len(sb["band"]), int(np.prod(n_cp))
+    assert zero.sum() == 7 and set(ba[zero].tolist()) == {-1, 0, 1, 2, 3} and {-1, npts + 5} <= set(bp[zero].tolist())
+    idx = np.stack(np.unravel_index(np.clip(bp, 0, npts - 1), grid.shape), 1)
+    for a in range(3):
+        assert ((ba == a) & zero & (idx[:, a] == grid.shape[a] - 1) & (bp >= 0) & (bp < npts)).sum() >= 1
+    assert {-1, nb, nb + 7} <= set(bsb["band_of"].tolist()) and {-2, ncp, n_cp[0] - degrees[0]} <= set(bsb["base"].tolist())
+    assert 7 < touched.sum() < len(ep) // 2 and (~touched).sum() > 100
+    got = msdiff_numpy.surface_spec(grid, bp, ba, bsb, degrees, n_cp, SCALE)
+    assert not got["J"][zero].any() and not got["vert"][zero].any() and got["vert"][~zero].all()
+    assert np.array_equal(got["J"][~touched], spec["J"][~touched]) and np.abs(got["J"][touched & ~zero]).max() > 0
+    assert (got["end"][touched & ~zero].sum(1) < spec["end"][touched & ~zero].sum(1)).all()        # each lost an endpoint
+    assert np.array_equal(got["axis"][zero], np.where((ba[zero] >= 0) & (ba[zero] <= 2), ba[zero], 0))

@@ -85,10 +85,13 @@ def band(grid_shape, vert_point, vert_class):
     return b, np.minimum(np.searchsorted(b, p), len(b) - 1), np.minimum(np.searchsorted(b, q), len(b) - 1)
 
 
-def tangent(grid, vert_point, vert_class, t_clamp, band_idx, G_band, B_band, m_band, level=0.0, variant=None):
+def tangent(grid, vert_point, vert_class, t_clamp, band_idx, G_band, B_band, m_band, level=0.0, variant=None, swap_dt=False):
     """(T [V, ncp, L] fp64, dm [V, 3], ends: (valid0 [V], valid1 [V], row0, row1), Tabs: the sum of the two endpoints' magnitudes,
-    for the bounds).  An endpoint outside band_idx contributes nothing (a wrong variant's q can leave the band)."""
+    for the bounds).  An endpoint outside band_idx contributes nothing (a wrong variant's q can leave the band).  swap_dt: WRONG on
+    purpose, each endpoint takes the other's dt factor (tests/msdiff_numpy.py's "swapped_dt")."""
     q, dm, d0, d1, mv = grid_factors(grid, vert_point, vert_class, t_clamp, level, variant)
+    if swap_dt:
+        d0, d1 = d1, d0
     p = np.asarray(vert_point, dtype=np.int64)
     G, B, m = (np.asarray(x, dtype=np.float64) for x in (G_band, B_band, m_band))
     T = np.zeros((len(p), B.shape[1], G.shape[1]))
