@@ -149,7 +149,14 @@ __global__ __launch_bounds__(TET_BLOCK) void tet_vertex_kernel(McGrid g, TetWs w
       // v0 and v1 lie on different sides of the level, so v1 != v0.  Every operation rounds on its own (the rn_* helpers of
       // common.hpp), in mc_vertex_kernel's sequence: a class-1/2/4 vertex has that kernel's bits.
       t = rn_div(rn_sub(g.level, v0), rn_sub(v1, v0));
-      if (o.t_clamp > 0.f) t = fminf(fmaxf(t, o.t_clamp), rn_sub(1.f, o.t_clamp));
+      // The clamp is compare-and-select, not fminf(fmaxf()): those return the other operand for a NaN, and a NaN t (a NaN grid
+      // value, an edge from -inf to +inf) has to stay NaN under every t_clamp, as in ms_caps_kernel.  For every other t the two
+      // forms give the same bits.
+      if (o.t_clamp > 0.f) {
+        const float hi = rn_sub(1.f, o.t_clamp);
+        t = t < o.t_clamp ? o.t_clamp : t;
+        t = t > hi ? hi : t;
+      }
     }
     if (id < o.nv) {
       float* out = o.verts + id * 3;

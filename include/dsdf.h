@@ -349,6 +349,15 @@ int dsdf_sample_batch_seq(const float* data, int32_t geom_dim, const int64_t* po
  * on its own) and origin[b] + p[b] * spacing[b] on the other two.  Order, without atomics (two runs give identical bytes):
  * vertices by grid-point linear index, then axis x, y, z; faces by cell linear index, then case-table order.  Faces are
  * counter-clockwise seen from increasing sdf (right-hand normals point outward).  Ambiguous cube faces separate the inside corners.
+ * Ties, zeros, non-finite values (the rules of dsdf_mc_*, dsdf_tet_*, dsdf_msd_* and dsdf_vd_* alike; tests/grid_values.py):
+ *   the fp32 comparison v < level alone decides inside and outside.  A value equal to the level is outside, whichever the sign of
+ *   either zero: -0.0f is 0.0f, level = -0.0f is level = 0.0f.  NaN and +inf are outside, -inf is inside.  The faces / elements and
+ *   the order and ids of the vertices are functions of that inside pattern alone.
+ *   A vertex's coordinates are what the stated sequence gives in IEEE fp32 arithmetic, subnormal numbers included (nothing is
+ *   flushed).  A tie gives t = 0 or t = 1 exactly and the vertex sits on the grid point; the sign of a zero t never reaches a
+ *   coordinate (p[a] >= +0, and (+0) + (-0) = +0).  A non-finite value changes only the vertices on its own edges: t and the
+ *   coordinates along the edge's axes are what the sequence says -- NaN for a NaN value, for an infinite v0 and for -inf against
+ *   +inf; t = 0 for a finite v0 against an infinite v1.  Which NaN (sign, payload) is not specified.
  * Use: dsdf_mc_count (writes {n_verts, n_faces} as int64 to device memory), read the totals, allocate, dsdf_mc_emit with the
  * SAME grid, level and workspace (the emit pass reads what the count pass left there).  Totals above INT32_MAX are refused
  * (DSDF_E_INVALID) before anything is written. */
@@ -530,6 +539,11 @@ int dsdf_ms_rows_at(const DsdfMsSpline* spline, const DsdfMsGrid* grid, const in
  * the last index of an axis is refused on every axis, also where p + e_a would be the first point of the next row); an endpoint
  * whose band_of row lies in 0 .. n_band - 1, with mask != 0, 0 <= base < ncp and base's index + degree < n_cp on every axis.  A
  * vertex out of range reports axis a when 0 <= a <= 2 and axis 0 otherwise.
+ * Ties: the comparison rules are dsdf_mc_*'s ("Ties, zeros, non-finite values", above); an endpoint whose value equals the level
+ * (either zero) gives the OTHER endpoint the factor dt/ds = 0 exactly.  Not part of the contract: what a difference s1 - s0 outside
+ * fp32's normal range gives.  Today the dt pair is formed as d = s1 - s0, d * d, the numerator, the quotient, so a subnormal d gives
+ * +-inf or NaN and an overflowed d gives 0 (observed, tests/test_gpu_grid_values.py); only that such a vertex leaves every other
+ * vertex's results untouched is promised.
  *   dsdf_msd_jacobian  jac [n_verts][ncp][L] and axis [n_verts] (may be NULL); full != 0: jac [n_verts][3][ncp][L], the two other
  *                      coordinates' planes written as zeros (the reference's layout)
  *   dsdf_msd_jvp       d_cp [ncp][L] -> d_verts [n_verts][3] (zeros off the edge axis)
@@ -687,7 +701,9 @@ int dsdf_sg_caps_at(const DsdfMsGrid* grid, const int64_t* indices, int64_t n, c
  *   origin[b] + (idx[b] + t) * spacing[b] where d[b] = 1 and origin[b] + idx[b] * spacing[b] elsewhere, fp32, every operation
  *   rounded on its own, in dsdf_mc_emit's sequence: the class-1/2/4 vertices are, in order and bit for bit, dsdf_mc_emit's vertices.
  *   t_clamp = tau in [0, 0.5): when tau > 0, t is clamped to [tau, 1 - tau] (1 - tau in fp32) before it is used; tau = 0 does not
- *   touch t.  The clamp bounds how thin a cut element can get and moves the surface by at most tau of an edge.
+ *   touch t.  The clamp bounds how thin a cut element can get and moves the surface by at most tau of an edge.  It is
+ *   compare-and-select: t = t < tau ? tau : t, then t = t > hi ? hi : t with hi = 1 - tau.  A NaN t fails both comparisons and
+ *   stays NaN under every t_clamp ("a NaN sdf stays", as dsdf_ms_caps has it); fminf / fmaxf would turn it into tau.
  * Elements of a Kuhn tetrahedron by its inside corners (corner numbers in increasing order within "inside" and within "outside";
  *   XY is the vertex on edge XY): none: nothing; all four: (q0, q1, q2, q3); one, A: (A, AB, AC, AD); three, D outside: the prism
  *   (A, B, C | AD, BD, CD); two, A and B: the prism (A, AC, AD | B, BC, BD).  A prism (a0, a1, a2 | b0, b1, b2) with vertical edges
@@ -703,8 +719,12 @@ int dsdf_sg_caps_at(const DsdfMsGrid* grid, const int64_t* indices, int64_t n, c
  * Order, without atomics (two runs give identical bytes): elements by cell (linear index of its lower corner), permutation, then
  *   the order above; boundary triangles by cell, permutation, cut faces, then the low-plane face (q0, q1, q2), then the high-plane
  *   face (q1, q2, q3).
- * Degenerate input: a value equal to level is outside, so t can be exactly 0 or 1; the elements touching that point then have zero
- *   volume and are still emitted (the topology stays conforming).  With tau > 0 there are none.
+ * Degenerate input: a value equal to level is outside (of either sign of zero; level = -0.0f is level = 0.0f), so t can be exactly
+ *   0 or 1; the vertex then sits on the grid point, the elements touching that point have zero volume and are still emitted (the
+ *   topology stays conforming).  With tau > 0 there are none.  Non-finite values: dsdf_mc_*'s rules above -- NaN and +inf are
+ *   outside, -inf is inside; tets, bfaces, bface_kind, vert_point, vert_class and the vertex ids are functions of the inside
+ *   pattern alone, and a non-finite value changes nothing in verts but the vertices on its own edges.  dsdf_tet_components uses
+ *   the same comparison.
  * Use: dsdf_tet_count (writes {n_verts, n_tets, n_bfaces} as int64 to device memory), read the totals, allocate, dsdf_tet_emit with
  * the SAME grid, level and workspace.  Totals above INT32_MAX and a t_clamp outside [0, 0.5) are refused (DSDF_E_INVALID) before
  * anything is launched; nothing is written past n_verts / n_tets / n_bfaces entries.  The workspace (about 11 bytes per grid point,
@@ -814,7 +834,10 @@ int dsdf_fem_boundary_gradient(const double* verts, int64_t n_verts, const int32
  * (an endpoint of a crossing diagonal need not lie on a crossing axis edge: the surface's band is not enough).
  * t_clamp = tau: t = (level - s0) / (s1 - s0) in dsdf_tet_emit's fp32 sequence; when tau > 0 the vertex moves iff
  * tau <= t <= 1 - tau (1 - tau in fp32), i.e. iff the clamp left t unchanged; otherwise its derivative is exactly zero.  tau = 0
- * zeroes nothing.
+ * zeroes nothing.  Both ends are included: t == tau and t == 1 - tau move, one ulp outside is held; a NaN t fails the comparisons
+ * and is held when tau > 0.  Inside and outside, ties and non-finite grid values: dsdf_mc_*'s rules ("Ties, zeros, non-finite
+ * values").  An endpoint equal to the level gives the OTHER endpoint a factor dt/ds of exactly zero.  A difference s1 - s0 outside
+ * fp32's normal range: as for dsdf_msd_* above -- observed behaviour, not a guarantee, except that every other vertex is untouched.
  * The entries work on a compacted list vert_index [n_moving] int32 of ids into the mesh's n_verts vertices (any subset, ascending
  * for a reproducible order; deepsdf_amd passes the class >= 1 vertices): grid vertices, most of a volume mesh, cost nothing.
  * grad_verts / d_verts / normals are [n_verts][3] and are addressed through vert_index.  A list entry outside 0 .. n_verts - 1, a

@@ -74,6 +74,15 @@ def cases():
            "degenerate": Case("degenerate", tetrahedralize(cuda(F.degenerate_grid()))),
            "large": Case("large", tetrahedralize(cuda(F.inside_grid(large_n()))), assemble=False)}
     assert out["degenerate"].skipped.sum() > 0 and not out["cut"].skipped.any()
+    # the device mesh of the tied grid is the numpy mesher's, array for array and bit for bit: the zero-volume elements the solver
+    # skips are the specification's, not an accident of the kernel's
+    from tests import tet_numpy
+    want, got = tet_numpy.tetrahedralize(F.degenerate_grid()), out["degenerate"]
+    assert got.t.shape == want.tets.shape and np.array_equal(got.t, want.tets)
+    assert got.bf.shape == want.bfaces.shape and np.array_equal(got.bf, want.bfaces)
+    assert np.array_equal(got.mesh.bface_kind.cpu().numpy(), want.bface_kind)
+    assert got.v.dtype == np.float32 and got.v.shape == want.verts.shape and got.v.tobytes() == want.verts.tobytes()
+    assert (tet_numpy.volumes(want.verts, want.tets) == 0).sum() > 0
     assert out["cut"].nv > 2 * 256 and len(out["cut"].t) > 2 * 256          # several workgroups of vertices and of elements
     return out
 

@@ -91,10 +91,14 @@ class Band:
         return T, dm * self.scale.astype(np.float64), n_terms, (ok0, ok1, r0, r1), Tabs
 
 
-def _check_contractions(B, tag):
+def _check_contractions(B, tag, keep=None):
     """jvp and vjp against the oracle's fp64 contraction at the bounds counted in tests/voldiff_numpy.py; returns (worst jvp error /
-    bound, worst vjp error / bound)."""
-    T, ds, n_terms, _, Tabs = B.oracle()
+    bound, worst vjp error / bound).  keep [V] bool: the caller has listed only these vertices in B.index, and only their terms are in
+    the oracle's sums; the rows of the others must be exact zeros (dsdf_vd_jvp zeroes all of d_verts before it writes a listed row)."""
+    T, ds, n_terms, (ok0, ok1, r0, r1), Tabs = B.oracle()
+    if keep is not None:
+        T[~keep], Tabs[~keep] = 0, 0
+        n_terms = ((ok0 & keep)[:, None] & B.sb["support"][r0]).sum(0) + ((ok1 & keep)[:, None] & B.sb["support"][r1]).sum(0)
     V = len(B.vp)
     rng = np.random.default_rng(3)
     w = rng.standard_normal((V, 3)).astype(np.float32)

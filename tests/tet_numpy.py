@@ -27,10 +27,50 @@ def _dir(c):
     return np.array([c & 1, (c >> 1) & 1, (c >> 2) & 1], dtype=np.int64)
 
 
-def records(sdf, level=0.0):
+# WRONG variants (`variant=`), for tests/test_grid_values_cpu.py: each is a mistake a kernel could make that no continuous random grid
+# shows, and exists so that a test can prove that its inputs tell it from the specification.
+#     "le_inside"     inside = sdf <= level: a value equal to the level counted inside
+#     "fminmax_clamp" the clamp as fmin(fmax(t, tau), 1 - tau): a NaN t becomes tau
+#     "abs_t"         t taken as |t|: the sign of a zero t (and of a NaN) lost
+VARIANTS = ("le_inside", "fminmax_clamp", "abs_t")
+
+
+def is_inside(sdf, level=0.0, variant=None):
+    """The specification's comparison v < level in the grid's own type: a value equal to the level (of either sign of zero), NaN and
+    +inf are outside, -inf is inside."""
+    sdf = np.asarray(sdf)
+    with np.errstate(invalid="ignore"):
+        return sdf <= sdf.dtype.type(level) if variant == "le_inside" else sdf < sdf.dtype.type(level)
+
+
+def clamp_t(t, t_clamp, dtype=np.float32, variant=None):
+    """The specification's clamp, compare-and-select: t < tau ? tau : t, then t > hi ? hi : t, hi = 1 - tau in `dtype`.  A NaN t
+    fails both comparisons and stays NaN under every tau; tau = 0 does not touch t."""
+    if not t_clamp > 0:
+        return t
+    tau = dtype(t_clamp)
+    hi = dtype(1) - tau
+    with np.errstate(invalid="ignore"):
+        if variant == "fminmax_clamp":
+            return np.fmin(np.fmax(t, tau), hi)
+        t = np.where(t < tau, tau, t)
+        return np.where(t > hi, hi, t)
+
+
+def edge_t(v0, v1, level, t_clamp=0.0, dtype=np.float32, variant=None):
+    """t of an edge from value v0 to value v1 in the mesher's sequence: (level - v0) / (v1 - v0), every operation rounded on its own
+    in `dtype`, then the clamp."""
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        t = (dtype(level) - v0) / (v1 - v0)
+    if variant == "abs_t":
+        t = np.abs(t)
+    return clamp_t(t, t_clamp, dtype, variant)
+
+
+def records(sdf, level=0.0, variant=None):
     """(inside [nx, ny, nz] bool, rec [npts, 8] bool: slot 0 = inside, slot c = edge (p, class c) crosses)."""
     sdf = np.asarray(sdf)
-    inside = sdf < sdf.dtype.type(level)
+    inside = is_inside(sdf, level, variant)
     nx, ny, nz = sdf.shape
     rec = np.zeros((nx, ny, nz, 8), dtype=bool)
     rec[..., 0] = inside
@@ -40,14 +80,14 @@ def records(sdf, level=0.0):
     return inside, rec.reshape(-1, 8)
 
 
-def vertices(sdf, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0), t_clamp=0.0, dtype=np.float32, contracted=False):
+def vertices(sdf, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0), t_clamp=0.0, dtype=np.float32, contracted=False, variant=None):
     """(verts [V, 3], vbase [npts] id of the first vertex of every grid point, vert_point [V] int64, vert_class [V] int32).
 
     contracted=True replaces the last step by fma(x, spacing, origin) (formed in fp64 from the fp32 operands, rounded once): NOT the
     specification; it exists so that a test can prove that its inputs tell the two apart."""
     sdf = np.ascontiguousarray(sdf, dtype=dtype)
     nx, ny, nz = sdf.shape
-    _, rec = records(sdf, level)
+    _, rec = records(sdf, level, variant)
     flat = rec.reshape(-1)
     sel = np.nonzero(flat)[0]
     p, c = sel // 8, sel % 8
@@ -55,21 +95,16 @@ def vertices(sdf, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0), t_clamp=0.0, d
     stride = np.array([ny * nz, nz, 1], dtype=np.int64)
     d = np.stack([c & 1, (c >> 1) & 1, (c >> 2) & 1], 1)
     f = sdf.reshape(-1)
-    lvl = dtype(level)
-    v0, v1 = f[p], f[p + d @ stride]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t = (lvl - v0) / (v1 - v0)                  # every operation rounded on its own
-    if t_clamp > 0:
-        tau = dtype(t_clamp)
-        t = np.minimum(np.maximum(t, tau), dtype(1) - tau)
+    t = edge_t(f[p], f[p + d @ stride], level, t_clamp, dtype, variant)      # every operation rounded on its own
     t = np.where(c == 0, dtype(0), t).astype(dtype)
     idx = np.stack(np.unravel_index(p, (nx, ny, nz)), 1).astype(dtype)
-    pos = np.where(d == 1, idx + t[:, None], idx).astype(dtype)
     sp, org = np.asarray(spacing, dtype), np.asarray(origin, dtype)
-    if contracted:
-        verts = (org.astype(np.float64) + pos.astype(np.float64) * sp.astype(np.float64)).astype(dtype)
-    else:
-        verts = (org + (pos * sp).astype(dtype)).astype(dtype)
+    with np.errstate(invalid="ignore", over="ignore"):
+        pos = np.where(d == 1, idx + t[:, None], idx).astype(dtype)
+        if contracted:
+            verts = (org.astype(np.float64) + pos.astype(np.float64) * sp.astype(np.float64)).astype(dtype)
+        else:
+            verts = (org + (pos * sp).astype(dtype)).astype(dtype)
     return verts.reshape(-1, 3), vbase, p.astype(np.int64), c.astype(np.int32)
 
 
@@ -110,15 +145,15 @@ def _split_poly(u):
     return [(u[0], u[1], u[2]), (u[0], u[2], u[3])]
 
 
-def tetrahedralize(sdf, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0), t_clamp=0.0, dtype=np.float32, stats=None):
+def tetrahedralize(sdf, level=0.0, spacing=(1, 1, 1), origin=(0, 0, 0), t_clamp=0.0, dtype=np.float32, stats=None, variant=None):
     """The mesh of the specification: a namespace of verts [V, 3], tets [T, 4] int32, bfaces [M, 3] int32, bface_kind [M] int8,
     vert_point [V] int64, vert_class [V] int32.  stats (a dict) receives the (permutation, inside mask) pairs met and the outcomes
     of the pyramid's diagonal."""
     sdf = np.ascontiguousarray(sdf, dtype=dtype)
     nx, ny, nz = sdf.shape
     dims = (nx, ny, nz)
-    inside, rec = records(sdf, level)
-    verts, vbase, vert_point, vert_class = vertices(sdf, level, spacing, origin, t_clamp, dtype)
+    inside, rec = records(sdf, level, variant)
+    verts, vbase, vert_point, vert_class = vertices(sdf, level, spacing, origin, t_clamp, dtype, variant=variant)
     ins = inside.reshape(-1)
     bits = (rec * (1 << np.arange(8))).sum(1).astype(np.int64)          # the point byte
     stride = (ny * nz, nz, 1)
@@ -223,12 +258,12 @@ def counts(sdf, level=0.0):
     return V, T, M
 
 
-def components(sdf, level=0.0):
+def components(sdf, level=0.0, variant=None):
     """(label [npts] int32: the lowest linear index of the point's solid component, -1 outside; size [npts] int32: the component's
     inside-point count at its root, 0 elsewhere).  Union-find over the 14-neighbour graph of the Kuhn edges."""
     sdf = np.asarray(sdf)
     nx, ny, nz = sdf.shape
-    ins = (sdf < sdf.dtype.type(level)).reshape(-1)
+    ins = is_inside(sdf, level, variant).reshape(-1)
     parent = np.arange(ins.size)
 
     def find(x):
@@ -259,7 +294,7 @@ def component_depth(sdf, level=0.0):
     further per round (a point takes the lowest label its neighbours held when the round began), so it needs at most this many
     rounds to converge and one more to see that nothing changes."""
     sdf = np.asarray(sdf)
-    ins = (sdf < sdf.dtype.type(level))
+    ins = is_inside(sdf, level)
     label, _ = components(sdf, level)
     dist = np.full(sdf.shape, -1, dtype=np.int64)
     roots = np.unique(label[label >= 0])

@@ -11,13 +11,16 @@ Four WRONG variants (`variant=`) exist so that the tests can show their inputs t
     "q_lowest_axis"  q taken along the lowest flagged axis only
     "no_clamp"       the clamp ignored
     "reversed_bits"  class bits mapped to axes in reverse (bit 0 -> z)
+and a fifth for tests/test_grid_values_cpu.py, which no continuous random grid shows:
+    "strict_clamp"   the vertex moves iff tau < t < 1 - tau: a t exactly on a clamp boundary held
 Also: the seeded synthetic band of the kernel-level tests, the bounds counted from the kernels, and the fp32 restatement of
 dsdf_vd_dtheta's stated sequence."""
 import numpy as np
 
-from tests import msdiff_numpy
+from tests import msdiff_numpy, tet_numpy
 
 VARIANTS = ("lowest_coord", "q_lowest_axis", "no_clamp", "reversed_bits")
+TIE_VARIANTS = ("strict_clamp",)
 U = 2.0 ** -24
 
 
@@ -48,7 +51,8 @@ def far_point(grid_shape, vert_point, vert_class, variant=None):
 
 
 def moves(grid, vert_point, vert_class, t_clamp, level=0.0, variant=None, dtype=np.float32):
-    """[V] bool: class >= 1 and the clamp leaves t unchanged (t in the mesher's sequence in `dtype`)."""
+    """[V] bool: class >= 1 and the clamp leaves t unchanged (t in the mesher's sequence in `dtype`): tau <= t <= 1 - tau, both ends
+    included; a NaN t fails the comparisons and is held."""
     g = np.ascontiguousarray(grid, dtype=dtype).reshape(-1)
     c = np.asarray(vert_class)
     p = np.asarray(vert_point, dtype=np.int64)
@@ -56,9 +60,9 @@ def moves(grid, vert_point, vert_class, t_clamp, level=0.0, variant=None, dtype=
     mv = (c > 0) & ok
     if t_clamp > 0 and variant != "no_clamp":
         tau = dtype(t_clamp)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t = (dtype(level) - g[p]) / (g[q] - g[p])
-        mv = mv & (t >= tau) & (t <= dtype(1) - tau)
+        t = tet_numpy.edge_t(g[p], g[q], level, 0.0, dtype)
+        with np.errstate(invalid="ignore"):
+            mv = mv & ((t > tau) & (t < dtype(1) - tau) if variant == "strict_clamp" else (t >= tau) & (t <= dtype(1) - tau))
     return mv
 
 
@@ -226,12 +230,9 @@ def vertices_from_edges(grid, vert_point, vert_class, t_clamp, level=0.0, spacin
     p, c = np.asarray(vert_point, dtype=np.int64), np.asarray(vert_class, dtype=np.int64)
     d, _ = directions(c)
     f = g.reshape(-1)
-    v0, v1 = f[p], f[p + d @ strides(g.shape)]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t = (F(level) - v0) / (v1 - v0)
-    if t_clamp > 0:
-        t = np.minimum(np.maximum(t, F(t_clamp)), F(1) - F(t_clamp))
+    t = tet_numpy.edge_t(f[p], f[p + d @ strides(g.shape)], level, t_clamp, F)         # the select-form clamp: a NaN t stays NaN
     t = np.where(c == 0, F(0), t).astype(F)
     idx = np.stack(np.unravel_index(p, g.shape), 1).astype(F)
-    pos = np.where(d == 1, idx + t[:, None], idx).astype(F)
-    return (np.asarray(origin, F) + (pos * np.asarray(spacing, F)).astype(F)).astype(F)
+    with np.errstate(invalid="ignore", over="ignore"):
+        pos = np.where(d == 1, idx + t[:, None], idx).astype(F)
+        return (np.asarray(origin, F) + (pos * np.asarray(spacing, F)).astype(F)).astype(F)
