@@ -87,18 +87,25 @@ class CantileverBeam:
         vol_der = None if dTheta is None else self._contract(s.volume_shape_gradient(), dTheta)
         return s.volume(), np.array(vol_der)
 
-    def compute_volume_gradient(self, geometry):
+    def compute_volume_gradient(self, geometry, discrete=False):
         """d volume / d control points [ncp * L] fp64 through ``geometry.shape_gradient`` (a DeepSDFMesh whose volume_mesh is this
         problem's mesh): the adjoint of compute_volume(dTheta)[1] with dTheta = geometry.get_dTheta(), without the dense array and
-        without its outlier clipping."""
+        without its outlier clipping.  discrete=True: the same vertex gradient (it is the exact derivative of the volume already)
+        through the plain Jacobian, not projected onto the normals."""
         if self.ElasticitySolver is None:
             raise ValueError("No solver found. Call set_up first.")
-        g = geometry.shape_gradient(self.ElasticitySolver.volume_shape_gradient())
+        g = geometry.shape_gradient(self.ElasticitySolver.volume_shape_gradient(), project=not discrete)
         return g.double().reshape(-1).cpu().numpy()
 
-    def compute_compliance_gradient(self, geometry, nodal="mean"):
-        """d compliance / d control points [ncp * L] fp64, the adjoint counterpart of compute_compliance(dTheta)[1]."""
+    def compute_compliance_gradient(self, geometry, nodal="mean", discrete=False):
+        """d compliance / d control points [ncp * L] fp64, the adjoint counterpart of compute_compliance(dTheta)[1].  discrete=True:
+        the exact derivative of the discrete compliance (LinearElasticity.compliance_discrete_gradient) through the plain Jacobian;
+        an exact vertex gradient has tangential parts that count, so it is not projected onto the normals (``nodal`` plays no part)."""
         if self.u_data is None:
             raise ValueError("No solution found. Compute solution first to get Compliance.")
-        g = geometry.shape_gradient(self.ElasticitySolver.compliance_shape_gradient(nodal))
+        s = self.ElasticitySolver
+        if discrete:
+            g = geometry.shape_gradient(s.compliance_discrete_gradient(), project=False)
+        else:
+            g = geometry.shape_gradient(s.compliance_shape_gradient(nodal))
         return g.double().reshape(-1).cpu().numpy()

@@ -217,6 +217,8 @@ PROTOTYPES = {
     "dsdf_fem_solve": [_FEM, _P, _P, _D, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_D), _P, _SZ, _P],
     "dsdf_fem_energy": [_FEM, _P, _P, _I32, _P, _P, _P, _SZ, _P],
     "dsdf_fem_boundary_gradient": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P],
+    "dsdf_fem_stiffness_gradient": [_FEM, _P, _P, _P, _P, _SZ, _P],
+    "dsdf_fem_load_gradient": [_P, _I64, _P, _I64, _P, _P, _P, C.POINTER(_D), _P, _P, _P, _P],
 }
 
 _lib = None

@@ -3512,6 +3512,33 @@ int dsdf_fem_energy(const DsdfFemOp* op, const double* u, double* we, int32_t no
   return 0;
 }
 
+int dsdf_fem_stiffness_gradient(const DsdfFemOp* op, const double* u, double* emt, double* grad, void* ws, size_t ws_bytes, void* stream) {
+  FemPlan P; FemMesh m;
+  TRY(fem_op("fem stiffness gradient", op, ws, ws_bytes, &P, &m));
+  if (!u || !emt || !grad) return fail(DSDF_E_INVALID, "fem stiffness gradient: NULL u, emt or grad");
+  if (u == grad || u == emt || emt == grad) return fail(DSDF_E_INVALID, "fem stiffness gradient: u == grad, u == emt or emt == grad");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(fem_emt_kernel, fem_grid(m.nt), dim3(FEM_BLOCK), 0, st, m, u, emt);
+  LAUNCH_OK("fem_emt_kernel");
+  hipLaunchKernelGGL(fem_emt_gather_kernel, fem_grid(m.nv), dim3(FEM_BLOCK), 0, st, m, (const double*)emt, grad);
+  LAUNCH_OK("fem_emt_gather_kernel");
+  return 0;
+}
+
+int dsdf_fem_load_gradient(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
+                           const int64_t* bvstart, const uint8_t* face_sel, const double* traction, const uint8_t* mask, const double* u,
+                           double* grad, void* stream) {
+  TRY(fem_boundary_args("fem load gradient", verts, n_verts, bfaces, n_bfaces, bcorner_order, bvstart, grad));
+  if (!u) return fail(DSDF_E_INVALID, "fem load gradient: NULL u");
+  if (u == grad) return fail(DSDF_E_INVALID, "fem load gradient: u == grad");
+  if (!traction || !std::isfinite(traction[0]) || !std::isfinite(traction[1]) || !std::isfinite(traction[2]))
+    return fail(DSDF_E_INVALID, "fem load gradient: NULL or non-finite traction");
+  hipLaunchKernelGGL(fem_load_gradient_kernel, fem_grid(n_verts), dim3(FEM_BLOCK), 0, (hipStream_t)stream, verts, n_verts, bfaces, n_bfaces,
+                     bcorner_order, bvstart, face_sel, traction[0], traction[1], traction[2], mask, u, grad);
+  LAUNCH_OK("fem_load_gradient_kernel");
+  return 0;
+}
+
 }  // extern "C"
 
 // Last function of the translation unit's device code: warm_own_code (common.hpp) clamps its reads to this address.

@@ -445,4 +445,110 @@ __global__ __launch_bounds__(FEM_BLOCK) void fem_boundary_kernel(const double* _
   for (int k = 0; k < 3; ++k) out[v * 3 + k] = s[k];
 }
 
+// ---- the exact discrete gradient of the compliance with respect to the vertices ------------------------------------
+// Pi(X, u) = 2 f(X) . u - u^T K(X) u is the compliance at the solution and stationary in the free components of u, so
+// d compliance / dX = dPi/dX at fixed u = gK + 2 sum over the tractions of gL.  Two passes shaped like the operator's, one boundary pass.
+//
+// Pass 1, per element: E = V (w I - 2 H^T S), H = grad u (no mask: u is what the caller hands in), S = lam tr(H) I + mu (H + H^T),
+// w as in fem_energy_elem_kernel, (H^T S)_kj = sum_i H_ik S_ij; emt[3 k + j][e] (geom's layout).  d(V w)/dx_b = E g_b, from
+// dV/dx_b = V g_b and d g_a,j / d x_b,k = -g_b,j g_a,k.  E is not symmetric.  A skipped element stores nine exact zeros.
+__global__ __launch_bounds__(FEM_BLOCK) void fem_emt_kernel(FemMesh m, const double* __restrict__ u, double* __restrict__ emt) {
+  const int64_t e = (int64_t)blockIdx.x * FEM_BLOCK + threadIdx.x;
+  if (e >= m.nt) return;
+  double g[4][3], H[3][3], E[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const double V = fem_grads(m.geom, m.nt, e, g);
+  if (V > 0.0) {
+    fem_grad_field(m, e, u, false, g, H);
+    const double tr = (H[0][0] + H[1][1]) + H[2][2];
+    double q = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) q += H[i][j] * (H[i][j] + H[j][i]);
+    const double w = m.lam * tr * tr + m.mu * q, lt = m.lam * tr;
+    double S[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) S[i][j] = (i == j ? lt : 0.0) + m.mu * (H[i][j] + H[j][i]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double hs = (H[0][k] * S[0][j] + H[1][k] * S[1][j]) + H[2][k] * S[2][j];
+        E[3 * k + j] = V * ((k == j ? w : 0.0) - 2.0 * hs);
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) emt[(int64_t)k * m.nt + e] = E[k];
+}
+
+// Pass 2, per vertex: gK_v = -sum over its corners (e, a) of E_e g_a, in corner_order's order; masked vertices included (a clamped
+// vertex moves with the mesh like any other).
+__global__ __launch_bounds__(FEM_BLOCK) void fem_emt_gather_kernel(FemMesh m, const double* __restrict__ emt, double* __restrict__ grad) {
+  const int64_t v = (int64_t)blockIdx.x * FEM_BLOCK + threadIdx.x;
+  if (v >= m.nv) return;
+  int64_t lo, hi;
+  fem_corner_range(m.vstart, v, 4 * m.nt, lo, hi);
+  double a[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = lo; i < hi; ++i) {
+    const int64_t c = clamp_index(m.corder[i], 4 * m.nt);
+    const int64_t e = c >> 2;
+    double g[3], E[9];
+    fem_grad_of(m.geom, m.nt, e, (int)(c & 3), g);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = emt[(int64_t)k * m.nt + e];
+    a[0] += (E[0] * g[0] + E[1] * g[1]) + E[2] * g[2];
+    a[1] += (E[3] * g[0] + E[4] * g[1]) + E[5] * g[2];
+    a[2] += (E[6] * g[0] + E[7] * g[1]) + E[8] * g[2];
+  }
+  grad[v * 3] = -a[0]; grad[v * 3 + 1] = -a[1]; grad[v * 3 + 2] = -a[2];
+}
+
+// Boundary pass, per vertex: gL_v = sum over its boundary corners on selected faces (a, b, c), in bcorner_order's order, of
+// c_f dA_f/dx_v: N = (b - a) x (c - a) as in fem_boundary_kernel, |N| = sqrt((N.x^2 + N.y^2) + N.z^2), n^ = N / |N|,
+// c_f = ((u~_a + u~_b) + u~_c) . t / 3 with u~ = u zeroed at masked vertices, dA/dx_a = n^ x (x_c - x_b) / 2,
+// dA/dx_b = n^ x (x_a - x_c) / 2, dA/dx_c = n^ x (x_b - x_a) / 2.  Every operation rounded on its own.  A face with |N| == 0 or a
+// non-finite n^ adds exact zeros: the area is not differentiable there (the boundary's counterpart of a skipped element).
+__global__ __launch_bounds__(FEM_BLOCK) void fem_load_gradient_kernel(const double* __restrict__ X, int64_t nv, const int32_t* __restrict__ F,
+                                                                      int64_t nb, const int64_t* __restrict__ border,
+                                                                      const int64_t* __restrict__ bvstart, const uint8_t* __restrict__ sel,
+                                                                      double t0, double t1, double t2, const uint8_t* __restrict__ mask,
+                                                                      const double* __restrict__ u, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t v = (int64_t)blockIdx.x * FEM_BLOCK + threadIdx.x;
+  if (v >= nv) return;
+  int64_t lo, hi;
+  fem_corner_range(bvstart, v, 3 * nb, lo, hi);
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = lo; i < hi; ++i) {
+    const int64_t bc = clamp_index(border[i], 3 * nb);
+    const int64_t f = bc / 3;
+    const int k = (int)(bc - 3 * f);
+    if (sel && !sel[f]) continue;
+    const int64_t id[3] = {clamp_index(F[f * 3], nv), clamp_index(F[f * 3 + 1], nv), clamp_index(F[f * 3 + 2], nv)};
+    double x[3][3], e1[3], e2[3], n[3];
+    for (int c = 0; c < 3; ++c)
+      for (int j = 0; j < 3; ++j) x[c][j] = X[id[c] * 3 + j];
+    for (int j = 0; j < 3; ++j) { e1[j] = x[1][j] - x[0][j]; e2[j] = x[2][j] - x[0][j]; }
+    fem_cross_rn(e1, e2, n);
+    const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    const double nh[3] = {n[0] / len, n[1] / len, n[2] / len};
+    if (!(len != 0.0) || !isfinite(nh[0]) || !isfinite(nh[1]) || !isfinite(nh[2])) continue;
+    double us[3][3];
+    for (int c = 0; c < 3; ++c) {
+      const bool held = mask && mask[id[c]];
+      for (int j = 0; j < 3; ++j) us[c][j] = held ? 0.0 : u[id[c] * 3 + j];
+    }
+    const double s0 = (us[0][0] + us[1][0]) + us[2][0], s1 = (us[0][1] + us[1][1]) + us[2][1], s2 = (us[0][2] + us[1][2]) + us[2][2];
+    const double cf = ((s0 * t0 + s1 * t1) + s2 * t2) / 3.0;
+    const int p = k == 0 ? 2 : (k == 1 ? 0 : 1), q = k == 0 ? 1 : (k == 1 ? 2 : 0);      // corner k: n^ x (x_p - x_q) / 2
+    double d[3], dA[3];
+    for (int j = 0; j < 3; ++j) d[j] = x[p][j] - x[q][j];
+    fem_cross_rn(nh, d, dA);
+    for (int j = 0; j < 3; ++j) s[j] += cf * (dA[j] * 0.5);
+  }
+  for (int j = 0; j < 3; ++j) out[v * 3 + j] = s[j];
+}
+
 }  // namespace dsdf

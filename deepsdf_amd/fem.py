@@ -6,6 +6,7 @@ analysis/MFEMLinearElasticity.py, for order-1 tetrahedra and constant Lame coeff
         solve                                           preconditioned CG with MFEM's stopping rule; the scalars stay on the device
         work / compliance / strain_energy_density       f . u, u^T K u, w per element or per vertex
         compliance_shape_gradient / volume / volume_shape_gradient      per-vertex [V, 3] gradients of the Hadamard boundary formulas
+        stiffness_gradient / load_gradient / compliance_discrete_gradient   the exact derivative of compliance() w.r.t. the vertices
 
 fp64 throughout, no floating-point atomics, every sum in a fixed order: two runs give identical bytes.  There is no CPU path."""
 import ctypes as C
@@ -56,6 +57,7 @@ class LinearElasticity:
             self.f = torch.zeros(self.nv, 3, dtype=torch.float64, device=dev)
             self.u = torch.zeros(self.nv, 3, dtype=torch.float64, device=dev)
         self._n_fixed = 0
+        self.tractions = []         # (selection [M] uint8, t): what add_traction summed into f, kept for load_gradient
         self.n_skipped_elements = self.n_held_vertices = None
         self._set_up()
 
@@ -101,6 +103,7 @@ class LinearElasticity:
             out = torch.empty(self.nv, 3, dtype=torch.float64, device=self.device)
             _lib.check(_lib.lib().dsdf_fem_load(*self._boundary_args(), _lib.ptr(sel), (C.c_double * 3)(*t), None, _lib.ptr(out), _lib.stream()))
             self.f += out
+            self.tractions.append((sel, tuple(t)))
         return self
 
     def add_nodal_forces(self, f):
@@ -178,3 +181,34 @@ class LinearElasticity:
         if nodal not in NODAL:
             raise ValueError(f"nodal must be 'mean' or 'last', got {nodal!r}")
         return self._boundary_gradient((-self._energy(nodal)[1]).contiguous())
+
+    # ---- the exact discrete gradient ----------------------------------------------------------------------------
+    def stiffness_gradient(self, u=None):
+        """(gK [V, 3], emt [9, T]): gK_v = -sum over the vertex's corners of E_e g_a, E = V (w I - 2 H^T S) per element (nine exact
+        zeros for a skipped one): the derivative of -u^T K(X) u with respect to the vertices at fixed u (default: the solved one)."""
+        u = self.u if u is None else self._vec(u, "u")
+        with torch.cuda.device(self.device):
+            emt = torch.empty(9, self.nt, dtype=torch.float64, device=self.device)
+            g = torch.empty(self.nv, 3, dtype=torch.float64, device=self.device)
+            op = self._op()
+            _lib.check(_lib.lib().dsdf_fem_stiffness_gradient(C.byref(op), _lib.ptr(u), _lib.ptr(emt), _lib.ptr(g), _lib.ptr(self.ws),
+                                                              self.ws.numel(), _lib.stream()))
+        return g, emt
+
+    def load_gradient(self, u=None):
+        """gL [V, 3], summed over the tractions in the order they were added: the derivative of f(X) . u with respect to the vertices
+        at fixed u, the loaded faces' areas moving with the mesh.  Nodal forces are constants and add nothing."""
+        u = self.u if u is None else self._vec(u, "u")
+        with torch.cuda.device(self.device):
+            total = torch.zeros(self.nv, 3, dtype=torch.float64, device=self.device)
+            g = torch.empty_like(total)
+            for sel, t in self.tractions:
+                _lib.check(_lib.lib().dsdf_fem_load_gradient(*self._boundary_args(), _lib.ptr(sel), (C.c_double * 3)(*t), _lib.ptr(self.mask),
+                                                             _lib.ptr(u), _lib.ptr(g), _lib.stream()))
+                total += g
+        return total
+
+    def compliance_discrete_gradient(self):
+        """gC [V, 3] = gK + 2 gL for the solved u: the derivative of the number compliance() returns with respect to the vertices,
+        exact for the discrete problem (Pi = 2 f . u - u^T K u is stationary in the free components of u: no new solve)."""
+        return self.stiffness_gradient()[0] + 2.0 * self.load_gradient()

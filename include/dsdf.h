@@ -820,6 +820,28 @@ int dsdf_fem_energy(const DsdfFemOp* op, const double* u, double* we, int32_t no
  * clcComplianceShapeDerivative, :343-369). */
 int dsdf_fem_boundary_gradient(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
                                const int64_t* bvstart, const double* weight, double* grad, void* stream);
+/* The exact discrete derivative of the compliance with respect to the vertices (numpy restatement:
+ * tests/femgrad_numpy.py).  Replaces nothing in the reference, whose clcComplianceShapeDerivative is the boundary formula above.
+ * Pi(X, u) = 2 f(X) . u - u^T K(X) u equals the compliance at the solution and is stationary in the free components of u (masked
+ * components are zero and stay zero), so d compliance / dX = dPi/dX at fixed u = gK + 2 * sum over the tractions of gL; nodal forces
+ * are constants and add nothing.  No new solve.  Additions only: DSDF_ABI_VERSION and dsdf_fem_plan's size and regions are unchanged.
+ *
+ * Stiffness term.  Per element that counts: H_ij = sum_a u_a,i g_a,j (u as handed in, no mask, as in dsdf_fem_energy),
+ *   S = lam tr(H) I + mu (H + H^T), w = lam tr(H)^2 + mu sum_ij H_ij (H_ij + H_ji), E = V (w I - 2 H^T S) with
+ *   (H^T S)_kj = sum_i H_ik S_ij (E is not symmetric): d(V w)/dx_b = E g_b, from dV/dx_b = V g_b and
+ *   d g_a,j / d x_b,k = -g_b,j g_a,k.  emt [9][n_tets] (the caller's, like we of dsdf_fem_energy) receives E row-major, 3 k + j, in
+ *   geom's layout; a skipped element stores nine exact zeros.  grad [n_verts][3]: gK_v = -sum of E_e g_a over the vertex's corners
+ *   (e, a) in corner_order's order, at masked vertices too.  u, emt and grad must be three different arrays. */
+int dsdf_fem_stiffness_gradient(const DsdfFemOp* op, const double* u, double* emt, double* grad, void* ws, size_t ws_bytes, void* stream);
+/* Load term of one traction ([host] 3 finite doubles) on the faces with face_sel[f] != 0 (NULL: all).  Face (a, b, c) in its stored
+ *   order: N = (b - a) x (c - a), |N| = sqrt((N.x^2 + N.y^2) + N.z^2), n^ = N / |N|, c_f = ((u~_a + u~_b) + u~_c) . t / 3 with
+ *   u~ = u zeroed where mask[v] != 0 (NULL: nowhere), dA_f/dx_a = n^ x (x_c - x_b) / 2, dA_f/dx_b = n^ x (x_a - x_c) / 2,
+ *   dA_f/dx_c = n^ x (x_b - x_a) / 2, every operation rounded on its own.  grad [n_verts][3]: gL_v = sum of c_f dA_f/dx_v over the
+ *   vertex's boundary corners on selected faces in bcorner_order's order.  A face with |N| == 0 or a non-finite n^ adds exact zeros:
+ *   the area is not differentiable there.  u != grad.  Both entries refuse their arguments before any launch. */
+int dsdf_fem_load_gradient(const double* verts, int64_t n_verts, const int32_t* bfaces, int64_t n_bfaces, const int64_t* bcorner_order,
+                           const int64_t* bvstart, const uint8_t* face_sel, const double* traction, const uint8_t* mask, const double* u,
+                           double* grad, void* stream);
 
 /* ---- derivative of a volume mesh with respect to the spline's control points (csrc/voldiff.hpp; fp64 restatement:
  * tests/voldiff_numpy.py).  The reference differentiates its volume mesh through the surface's Jacobian only

@@ -20,6 +20,7 @@ from analysis.problems.CantileverBeam import CantileverBeam
 from optimization import config
 
 METHODS = ("BFGS", "COBYLA", "MMA")                  # what config.json may name; MMA is refused when it is run
+GRADIENTS = ("boundary", "discrete")                 # general.gradient: the reference's Hadamard formula (default) or the exact one
 
 
 @dataclasses.dataclass
@@ -41,7 +42,9 @@ def _key(x):
 class struct_optimization:
     """An optimisation folder holding ``config.json`` with the sections ``mesh`` (DeepSDFMesh's options), ``optimization``
     (``method`` and scipy's options, optional ``x0`` and ``bounds``) and ``general`` (``volume_constraint``; optional ``t_clamp``
-    of the volume mesh, default 0; optional ``dense_dtheta``, default false)."""
+    of the volume mesh, default 0; optional ``dense_dtheta``, default false; optional ``gradient``: "boundary" (default, the
+    reference's Hadamard formula projected onto the normals) or "discrete" (the exact derivative of the discrete compliance and
+    volume through the plain Jacobian; not with ``dense_dtheta``))."""
 
     def __init__(self, optimization_folder, experiment_location=None, device="cuda"):
         self.optimization_folder = pathlib.Path(optimization_folder)
@@ -72,6 +75,12 @@ class struct_optimization:
         method = self.options["optimization"]["method"]
         if method not in METHODS:
             raise ValueError(f"optimization.method {method!r} is not one of {list(METHODS)}")
+        gradient = self.options["general"].get("gradient", "boundary")
+        if gradient not in GRADIENTS:
+            raise ValueError(f"general.gradient {gradient!r} is not one of {list(GRADIENTS)}")
+        if gradient == "discrete" and bool(self.options["general"].get("dense_dtheta", False)):
+            raise ValueError("general.gradient 'discrete' goes through the adjoint of the plain Jacobian: dense_dtheta (the dense, "
+                             "clipped, normal-projected dTheta) cannot carry it")
 
     def set_x0(self):
         shape = (self.geometry.get_n_control_points(), self.geometry.get_latent_shape())
@@ -95,16 +104,17 @@ class struct_optimization:
         beam.set_mesh(mesh)
         beam.set_up()
         dense = bool(general.get("dense_dtheta", False))
+        discrete = general.get("gradient", "boundary") == "discrete"
         dTheta = geo.get_dTheta() if dense else None
         volume, der_vol = beam.compute_volume(dTheta)
         if not dense:
-            der_vol = beam.compute_volume_gradient(geo)
+            der_vol = beam.compute_volume_gradient(geo, discrete=discrete)
         if np.any(np.isnan(der_vol)):
             self.logger.warning("the volume gradient holds a NaN")
         beam.solve()
         compliance, der_compliance = beam.compute_compliance(dTheta)
         if not dense:
-            der_compliance = beam.compute_compliance_gradient(geo)
+            der_compliance = beam.compute_compliance_gradient(geo, discrete=discrete)
         self.problem = beam
         self.cache[_key(x)] = {"objective": (compliance, der_compliance),
                                "constraint": (volume - general["volume_constraint"], der_vol)}

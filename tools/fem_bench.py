@@ -7,7 +7,8 @@ The structure of tools/ms_bench.py (degree-1 field, 2 x 2 x 2 seeded codes, L = 
 t_clamp = 0.05, its largest component kept, and shifted so that its lowest corner is the origin; then the reference's problem
 (CantileverBeam.set_up): the reference's boundary attributes, attribute 1 (the low-x face) clamped, the traction (0, 0, -0.01) on
 attribute 2 (the top), lam = 0, mu = 105.  Timed with HIP events after one warm-up, medians of --reps: one operator application
-(dsdf_fem_apply through LinearElasticity.apply), one CG iteration (the difference of two solves of 50 and 250 iterations at rel_tol = 0,
+(dsdf_fem_apply through LinearElasticity.apply), the two terms of the exact discrete gradient the same way (stiffness_gradient: two
+passes and two allocations; load_gradient: the boundary pass of the one traction and the sum), one CG iteration (the difference of two solves of 50 and 250 iterations at rel_tol = 0,
 one host read each), and the whole solve to 1e-10 with its iteration count.  Bytes per iteration are DESIGN 4.21.4's two counts: what
 the kernels request (612 T + 353 V) and what has to cross HBM at least once (304 T + 378 V); the rates divide them by the iteration
 time.  On the smallest mesh the oracle's scipy PCG (tests/fem_numpy.py) runs --host-iters iterations on the host, for scale."""
@@ -97,6 +98,10 @@ def main():
         x = torch.randn(V, 3, dtype=torch.float64, device="cuda")
         s.apply(x)
         apply_ms = [events_ms(lambda: [s.apply(x) for _ in range(20)])[0] / 20 for _ in range(args.reps)]
+        s.stiffness_gradient(x)
+        s.load_gradient(x)
+        stiffness_gradient_ms = [events_ms(lambda: [s.stiffness_gradient(x) for _ in range(20)])[0] / 20 for _ in range(args.reps)]
+        load_gradient_ms = [events_ms(lambda: [s.load_gradient(x) for _ in range(20)])[0] / 20 for _ in range(args.reps)]
         s.solve(rel_tol=0.0, max_iter=50, check_every=10 ** 6)
         iter_ms = []
         for _ in range(args.reps):
@@ -109,7 +114,8 @@ def main():
             solve_ms.append(t)
         it_s = statistics.median(iter_ms) * 1e-3
         line = dict(what="tiled structure", dims=n, V=V, T=T, M=mesh.n_bfaces, skipped=s.n_skipped_elements, held=s.n_held_vertices,
-                    reps=args.reps, setup_ms=round(t_setup, 3), apply_ms=med(apply_ms), cg_iteration_ms=med(iter_ms), solve_ms=med(solve_ms),
+                    reps=args.reps, setup_ms=round(t_setup, 3), apply_ms=med(apply_ms), stiffness_gradient_ms=med(stiffness_gradient_ms),
+                    load_gradient_ms=med(load_gradient_ms), cg_iteration_ms=med(iter_ms), solve_ms=med(solve_ms),
                     iterations=res[0], converged=res[1], ratio=res[2], compliance=s.compliance(), work=s.work(), volume=s.volume(),
                     requested_mb_per_iteration=round(requested_bytes(V, T) / 1e6, 2),
                     compulsory_mb_per_iteration=round(compulsory_bytes(V, T) / 1e6, 2),
